@@ -10,12 +10,21 @@ first restores the filters' pristine state on the device (a D2D copy that is
 counted inside the timed region) so every step does identical work.
 
   python bench.py [--gpus N --steps K --warmup W --batch B --N 30 --F 200 --dtype fp32]
+                  [--dump-outputs DIR] [--full]
 
-The JSON line carries the headline (fp32 context, BASELINE config 2) and,
-unless --no-fp64, the same workload in the fp64 context (the precision the
-north-star's 1e-6 tolerance is stated at) as ``fp64``; ``accuracy`` compares
-the GPU's updated filters with the CPU oracle's (computed in the
-cpu_baseline leg, as the checker).
+A plain run does only what the headline needs: it builds the batch, warms up,
+times exactly --steps steps and prints the JSON line (fp32 context, BASELINE
+config 2).  --dump-outputs DIR then writes what the last timed step computed
+(dump_outputs below) so that two builds can be compared output for output:
+the problems are seeded, the inputs identical from run to run.
+
+--full adds every other measurement and check to the line: the per-stage
+profiled pass and the dominant stage's roofline, the CPU baseline and the
+``accuracy`` block (the GPU's updated filters against the CPU oracle's,
+computed in the cpu_baseline leg, as the checker), the run without
+triangulation, the IMU-propagation leg, the ATE replay and, unless --no-fp64,
+the same workload in the fp64 context (the precision the north-star's 1e-6
+tolerance is stated at) as ``fp64``.  The --no-* switches trim a --full run.
 
 --gpus N > 1: N ranks, one process per GPU -- spawned by this script (its
 parent process never touches the GPU) or by an external launcher
@@ -45,6 +54,8 @@ HBM_PEAK_GBS = 8000.0
 FP32_PEAK_TFLOPS = 157.3      # MI355X dense FP32 (vector = MFMA f32 rate), MI355X_MICROARCH.md
 FP64_PEAK_TFLOPS = 78.6
 N_CHECK = 4                   # distinct problems the accuracy block compares with the oracle
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs writes at most this much in all
+DUMP_STATES = 64              # filters whose updated state and covariance are dumped
 
 
 def parse():
@@ -61,6 +72,11 @@ def parse():
     ap.add_argument("--rccl-timeout", type=float, default=1800.0,
                     help="deadline (s) of every replica collective once RCCL is up (rank 0 runs the accuracy / "
                          "ATE legs while the others wait in a barrier)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: profiled pass + roofline, CPU baseline + accuracy, "
+                         "no-triangulation, propagation, fp64 and ATE legs (each --no-* switch below drops one)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-fp64", action="store_true", help="skip the fp64-context leg")
     ap.add_argument("--no-ate", action="store_true", help="skip the ATE replay leg")
@@ -255,27 +271,30 @@ def accuracy(ctx, refs, acc, feat_off):
 
 
 # ------------------------------------------------------------------- legs --
-def timed_update(ctx, args, grp):
-    """Warm-up; a profiled pass of args.steps steps (every stage timed with HIP
-    events, outside the timed region: the per-stage breakdown and the dominant
-    stage); then exactly args.steps timed steps between barriers, the device
-    synchronised on both sides, with HIP events around the dominant stage only
-    (two event packets per step instead of two per stage).  Returns
-    (max-over-ranks seconds, per-stage times of the profiled pass, the
-    dominant stage's times from the timed region)."""
+def timed_update(ctx, args, grp, profile=True):
+    """Warm-up; with ``profile`` a profiled pass of args.steps steps (every
+    stage timed with HIP events, outside the timed region: the per-stage
+    breakdown and the dominant stage); then exactly args.steps timed steps
+    between barriers, the device synchronised on both sides, with HIP events
+    around the dominant stage only (two event packets per step instead of two
+    per stage) if profiled.  Returns (max-over-ranks seconds, per-stage times
+    of the profiled pass, the dominant stage's times from the timed region);
+    the last two are None without ``profile``."""
     for _ in range(args.warmup):
         ctx.restore()
         ctx.batch_update(row_cap=0, triangulate=True)
     ctx.sync()
-    ctx.set_profiling(True)
-    for _ in range(args.steps):
-        ctx.restore()
-        ctx.batch_update(row_cap=0, triangulate=True)
-    ctx.sync()
-    stages = ctx.kernel_times()
-    ctx.set_profiling(False)
-    dom = max((k for k in stages if k != "restore"), key=lambda k: stages[k][0])
-    ctx.set_profiling_stage(dom)
+    stages = None
+    if profile:
+        ctx.set_profiling(True)
+        for _ in range(args.steps):
+            ctx.restore()
+            ctx.batch_update(row_cap=0, triangulate=True)
+        ctx.sync()
+        stages = ctx.kernel_times()
+        ctx.set_profiling(False)
+        dom = max((k for k in stages if k != "restore"), key=lambda k: stages[k][0])
+        ctx.set_profiling_stage(dom)
     grp.barrier()
     ctx.sync()
     t0 = time.perf_counter()
@@ -285,9 +304,50 @@ def timed_update(ctx, args, grp):
     ctx.sync()
     grp.barrier()
     el = time.perf_counter() - t0
-    timed = ctx.kernel_times()
-    ctx.set_profiling(False)
+    timed = None
+    if profile:
+        timed = ctx.kernel_times()
+        ctx.set_profiling(False)
     return grp.max_over_ranks(el), stages, timed
+
+
+def dump_outputs(ctx, args, results, out_dir, rank):
+    """--dump-outputs: what a caller of the timed path receives after its last
+    step, as <name>.npy (rank r > 0 of a multi-GPU run: rank<r>_<name>.npy).
+    The per-feature results of the batch (accepted, gamma, the triangulated
+    positions, valid; rows of feature_index, every feature if they fit) and
+    the stacked row count of the filters (rows of rows_index); and, of a fixed
+    seeded sample of DUMP_STATES filters (state_filters), the updated IMU
+    state, cam states and covariance.  float32 for flags and counts, float64
+    otherwise; DUMP_MAX_BYTES in all, the samples fixed by the seed."""
+    acc, gam, pw, valid, rows = results
+    rng = np.random.default_rng(20240229)
+
+    def pick_rows(n, row_bytes, budget):
+        if n * row_bytes <= budget:
+            return np.arange(n)
+        return np.sort(rng.choice(n, size=max(1, budget // row_bytes), replace=False))
+
+    feat = pick_rows(len(acc), 8 + 4 + 8 + 24 + 4, DUMP_MAX_BYTES // 2 - (1 << 20))   # half for these and rows
+    filt = pick_rows(len(rows), 8 + 4, 1 << 20)
+    arrays = {"feature_index": feat.astype(np.float64), "accepted": acc[feat].astype(np.float32),
+              "gamma": gam[feat].astype(np.float64), "positions": pw[feat].astype(np.float64),
+              "valid": valid[feat].astype(np.float32),
+              "rows_index": filt.astype(np.float64), "rows": rows[filt].astype(np.float32)}
+    D = 21 + 6 * args.N
+    per_filter = 8 * (D * D + 64 + 16 * args.N)         # P, IMU vector and cam states, generously
+    n = max(1, min(args.batch, DUMP_STATES, (DUMP_MAX_BYTES // 2) // per_filter))
+    pick = np.sort(rng.choice(args.batch, size=n, replace=False))
+    states = [ctx.get_state(int(b)) for b in pick]
+    arrays["state_filters"] = pick.astype(np.float64)
+    arrays["imu"] = np.stack([st[0] for st in states]).astype(np.float64)
+    arrays["cams"] = np.stack([st[1] for st in states]).astype(np.float64)
+    arrays["cov"] = np.stack([st[2] for st in states]).astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = "" if rank == 0 else "rank%d_" % rank
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
 
 
 def roofline_of(times, fl, args, dtype):
@@ -445,7 +505,7 @@ def stub_main(args, grp):
     device (index = local rank, bus id 'stub:<local rank>')."""
     devs = gather_devices(grp, (grp.local_rank, "stub:%d" % grp.local_rank))
     cpu = None
-    if grp.rank == 0 and not args.no_cpu:
+    if grp.rank == 0 and args.full and not args.no_cpu:
         cpu = {"value": None, "unit": "updates/s", "cores": 1, "kind": "port", "sample": "stub (not a measurement)"}
     grp.barrier()
     t0 = time.perf_counter()
@@ -477,16 +537,17 @@ def main():
     dtype = np.float32 if args.dtype == "fp32" else np.float64
     probs = make_problems(args, rank, min(args.unique, args.batch))
     cpu, refs = None, []
-    if rank == 0 and not args.no_cpu:   # before this process initialises the GPU (any world size)
+    if rank == 0 and args.full and not args.no_cpu:   # before this process initialises the GPU (any world size)
         cpu, refs = cpu_baseline(args, probs[:N_CHECK])
 
     ctx, feat_off = build_batch(args, probs, dtype, grp.local_rank)
     transport = grp.attach_rccl(ctx.device_info()[0], collective_timeout_s=args.rccl_timeout)   # barriers / max / gathers over RCCL from here on
     devs = gather_devices(grp, ctx.device_info())
-    el, times, timed = timed_update(ctx, args, grp)
+    el, times, timed = timed_update(ctx, args, grp, profile=args.full)
     value = replicas.whole_job_rate(args.batch, grp.world, args.steps, el)
     acc, gam, pw, valid, rows = ctx.batch_results()
-    fl = flops_model(probs, args.batch, acc, valid, feat_off)
+    if args.dump_outputs:       # before any other leg restores the filters
+        dump_outputs(ctx, args, (acc, gam, pw, valid, rows), args.dump_outputs, rank)
     out = {
         "metric": metric_name(args), "value": round(value, 2), "unit": "updates/s", "n_gpus": grp.world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 3),
@@ -501,22 +562,25 @@ def main():
                    "stacked_rows_mean": float(np.mean(rows)), "parallelism": "replicas%d" % grp.world},
         "devices": devs,
         "replicas": transport,
-        "roofline": roofline_of(timed, fl, args, args.dtype),
-        # per-stage HIP-event times of the profiled pass before the timed region
-        "kernel_ms_per_step": {k: round(v[0] / args.steps, 3) for k, v in sorted(times.items(), key=lambda kv: -kv[1][0])},
-        "canonical_gflop_per_update": round(fl["canonical"] / args.batch / 1e9, 4),
     }
-    if refs:
-        out["accuracy"] = accuracy(ctx, refs, acc, feat_off)
-    if cpu is not None:
-        out["cpu_baseline"] = cpu
-    out["without_triangulation"] = no_triangulation_leg(ctx, args, grp)
-    if not args.no_prop:
-        out["propagation"] = propagation_leg(ctx, args)
+    if args.full:
+        fl = flops_model(probs, args.batch, acc, valid, feat_off)
+        out["roofline"] = roofline_of(timed, fl, args, args.dtype)
+        # per-stage HIP-event times of the profiled pass before the timed region
+        out["kernel_ms_per_step"] = {k: round(v[0] / args.steps, 3)
+                                     for k, v in sorted(times.items(), key=lambda kv: -kv[1][0])}
+        out["canonical_gflop_per_update"] = round(fl["canonical"] / args.batch / 1e9, 4)
+        if refs:
+            out["accuracy"] = accuracy(ctx, refs, acc, feat_off)
+        if cpu is not None:
+            out["cpu_baseline"] = cpu
+        out["without_triangulation"] = no_triangulation_leg(ctx, args, grp)
+        if not args.no_prop:
+            out["propagation"] = propagation_leg(ctx, args)
     ctx.close()
-    if args.dtype == "fp32" and not args.no_fp64:
+    if args.full and args.dtype == "fp32" and not args.no_fp64:
         out["fp64"] = fp64_leg(args, grp, probs, refs)
-    if rank == 0 and not args.no_ate:
+    if args.full and rank == 0 and not args.no_ate:
         out["ate"] = ate_leg()
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -70,7 +70,9 @@ _WORKER = textwrap.dedent("""
     mine = replicas.shard(list(range(11)), grp.rank, grp.world)
     total = grp.sum_over_ranks(len(mine))
     grp.barrier()
-    print(json.dumps({"rank": grp.rank, "world": grp.world, "max": mx, "total": total, "mine": mine}))
+    # one write per rank: the ranks share a stdout, and an unbuffered print writes its newline separately
+    sys.stdout.write(json.dumps({"rank": grp.rank, "world": grp.world, "max": mx, "total": total, "mine": mine}) + "\\n")
+    sys.stdout.flush()
     grp.close()
 """) % ROOT
 
@@ -115,9 +117,10 @@ def test_bench_spawns_ranks():
 
 @pytest.mark.timeout(120)
 def test_bench_keeps_cpu_baseline_at_world2():
-    """Rank 0 computes the CPU baseline before it touches the GPU whatever
-    the world size, so an N > 1 line carries it too."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub", "--steps", "2"],
+    """Rank 0 computes the CPU baseline (a --full leg) before it touches the
+    GPU whatever the world size, so an N > 1 line carries it too."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub", "--steps", "2",
+                          "--full"],
                          capture_output=True, text=True, timeout=100,
                          env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert out.returncode == 0, out.stderr

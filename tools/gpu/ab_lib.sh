@@ -6,9 +6,9 @@ OUT=gpurun_out/$1; EXPS=$2; shift 2; mkdir -p $OUT
 COMMON="--no-cpu --no-ate --no-prop --no-fp64"
 for cfg in "$@"; do
   name=${cfg%%:*}; args=${cfg#*:}
-  timeout -k 10 400 python3 -u bench.py $args $COMMON > $OUT/${name}_base.json 2> $OUT/${name}_base.err || { tail -20 $OUT/${name}_base.err; exit 1; }
+  timeout -k 10 400 python3 -u bench.py --full $args $COMMON > $OUT/${name}_base.json 2> $OUT/${name}_base.err || { tail -20 $OUT/${name}_base.err; exit 1; }
   for e in $EXPS; do
-    timeout -k 10 400 python3 -u tools/exp_bench.py tools/exp/libmsckf_$e.so $args $COMMON > $OUT/${name}_$e.json 2> $OUT/${name}_$e.err || { tail -20 $OUT/${name}_$e.err; exit 1; }
+    timeout -k 10 400 python3 -u tools/exp_bench.py tools/exp/libmsckf_$e.so --full $args $COMMON > $OUT/${name}_$e.json 2> $OUT/${name}_$e.err || { tail -20 $OUT/${name}_$e.err; exit 1; }
   done
 done
 for f in $OUT/*.json; do

@@ -4,9 +4,9 @@
 set -o pipefail
 OUT=gpurun_out/${1:-exp}; shift; mkdir -p $OUT
 ARGS="--no-cpu --no-ate --no-prop --no-fp64"
-timeout -k 10 300 python -u bench.py $ARGS > $OUT/base.json 2> $OUT/base.err || { tail -20 $OUT/base.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full $ARGS > $OUT/base.json 2> $OUT/base.err || { tail -20 $OUT/base.err; exit 1; }
 for e in "$@"; do
-  timeout -k 10 300 python -u tools/exp_bench.py tools/exp/libmsckf_$e.so $ARGS > $OUT/$e.json 2> $OUT/$e.err || { tail -20 $OUT/$e.err; exit 1; }
+  timeout -k 10 300 python -u tools/exp_bench.py tools/exp/libmsckf_$e.so --full $ARGS > $OUT/$e.json 2> $OUT/$e.err || { tail -20 $OUT/$e.err; exit 1; }
 done
 for f in $OUT/*.json; do
   python3 -c "

@@ -5,9 +5,9 @@ set -o pipefail
 OUT=gpurun_out/${1:-exp}; R=${2:-2}; shift 2; mkdir -p $OUT
 ARGS=${BENCH_ARGS:-"--no-cpu --no-ate --no-prop --no-fp64"}
 for r in $(seq 1 $R); do
-  timeout -k 10 300 python -u bench.py $ARGS > $OUT/base_$r.json 2> $OUT/base_$r.err || { tail -20 $OUT/base_$r.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full $ARGS > $OUT/base_$r.json 2> $OUT/base_$r.err || { tail -20 $OUT/base_$r.err; exit 1; }
   for e in "$@"; do
-    timeout -k 10 300 python -u tools/exp_bench.py tools/exp/libmsckf_$e.so $ARGS > $OUT/${e}_$r.json 2> $OUT/${e}_$r.err || { tail -20 $OUT/${e}_$r.err; exit 1; }
+    timeout -k 10 300 python -u tools/exp_bench.py tools/exp/libmsckf_$e.so --full $ARGS > $OUT/${e}_$r.json 2> $OUT/${e}_$r.err || { tail -20 $OUT/${e}_$r.err; exit 1; }
   done
 done
 for f in $OUT/*.json; do

@@ -34,12 +34,12 @@ for step in "$@"; do
     tests) run tests 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread; tail -2 $OUT/tests.out ;;
     tests:*) run tests_k 600 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread -k "${step#tests:}"; tail -2 $OUT/tests_k.out ;;
     smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()"; tail -1 $OUT/smoke.out ;;
-    bench) run bench 600 python -u bench.py; line bench ;;
-    quick) run quick 300 python -u bench.py $NB --no-fp64; line quick ;;
-    b50) run b50 600 python -u bench.py --N 50 --F 400 $NB --no-fp64; line b50 ;;
-    b80) run b80 600 python -u bench.py --N 80 --F 1000 --batch 512 $NB --no-fp64; line b80 ;;
-    b50d) run b50d 600 python -u bench.py --N 50 --F 400 --dtype fp64 $NB; line b50d ;;
-    b80d) run b80d 600 python -u bench.py --N 80 --F 1000 --dtype fp64 --batch 512 $NB; line b80d ;;
+    bench) run bench 600 python -u bench.py --full; line bench ;;
+    quick) run quick 300 python -u bench.py --full $NB --no-fp64; line quick ;;
+    b50) run b50 600 python -u bench.py --full --N 50 --F 400 $NB --no-fp64; line b50 ;;
+    b80) run b80 600 python -u bench.py --full --N 80 --F 1000 --batch 512 $NB --no-fp64; line b80 ;;
+    b50d) run b50d 600 python -u bench.py --full --N 50 --F 400 --dtype fp64 $NB; line b50d ;;
+    b80d) run b80d 600 python -u bench.py --full --N 80 --F 1000 --dtype fp64 --batch 512 $NB; line b80d ;;
     stats) bash tools/gpu/stats.sh $TAG/st --no-fp64 || exit 1 ;;
     sq) bash tools/gpu/sq.sh $TAG/sq "k_gate|k_info|k_kal|k_feature|k_prop|k_triang" || exit 1 ;;
     pmc) bash tools/profile_round.sh $TAG 3 || exit 1 ;;

@@ -7,4 +7,4 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 CTR="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_MFMA SQ_LDS_BANK_CONFLICT"
 timeout -s KILL 90 rocprofv3 --pmc $CTR --kernel-include-regex "$RE" -d $OUT/sq -o run --output-format csv -- \
-    python3 bench.py --steps 1 --warmup 0 --no-cpu --no-ate --no-prop --no-fp64 "$@" > $OUT/sq.log 2>&1
+    python3 bench.py --full --steps 1 --warmup 0 --no-cpu --no-ate --no-prop --no-fp64 "$@" > $OUT/sq.log 2>&1

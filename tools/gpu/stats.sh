@@ -5,4 +5,4 @@ OUT=gpurun_out/${1:-stats}; shift
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- \
-    python3 bench.py --steps 3 --warmup 1 --no-cpu --no-ate --no-prop "$@" > $OUT/stats.log 2>&1
+    python3 bench.py --full --steps 3 --warmup 1 --no-cpu --no-ate --no-prop "$@" > $OUT/stats.log 2>&1

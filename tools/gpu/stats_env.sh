@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for v in $VALS; do
   export $VAR=$v
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/s_$v -o run --output-format csv -- \
-      python3 bench.py --steps 2 --warmup 0 --no-cpu --no-ate --no-prop --no-fp64 $ARGS > $OUT/s_$v.log 2>&1 \
+      python3 bench.py --full --steps 2 --warmup 0 --no-cpu --no-ate --no-prop --no-fp64 $ARGS > $OUT/s_$v.log 2>&1 \
       || { echo "value $v failed"; tail -20 $OUT/s_$v.log; exit 1; }
   python3 - $OUT/s_$v/run_kernel_stats.csv $v <<'PY'
 import csv, sys

@@ -10,5 +10,5 @@ i=0
 for ctr in "${SETS[@]}"; do
   i=$((i+1))
   timeout -s KILL 90 rocprofv3 --pmc $ctr --kernel-include-regex "$RE" -d $OUT/ph7_$i -o run --output-format csv -- \
-      python3 bench.py --steps 1 --warmup 0 --no-cpu --no-ate --no-prop > $OUT/ph7_$i.log 2>&1 || exit 1
+      python3 bench.py --full --steps 1 --warmup 0 --no-cpu --no-ate --no-prop > $OUT/ph7_$i.log 2>&1 || exit 1
 done

@@ -4,7 +4,7 @@
 
 FETCH.csv / WRITE.csv are the counter_collection CSVs of two separate
 `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` runs of the same
-`bench.py --steps K --warmup 0` command (the two TCC counters do not fit in
+`bench.py --full --steps K --warmup 0` command (the two TCC counters do not fit in
 one pass on gfx950).  Counter values are KiB per dispatch.  Kernels are
 grouped into the bench's timer stages; bytes_per_step = (FETCH + WRITE) * 1024
 per dispatch, summed over the stage's kernels (each runs once per step).  Per MI355X_MICROARCH.md, FETCH_SIZE on
