@@ -97,6 +97,16 @@ FRONTEND_SIGS = {
 }
 FRONTEND_EXPORTED = tuple(FRONTEND_SIGS)
 
+_U32 = C.POINTER(C.c_uint32)
+# two-point RANSAC of the front-end (include/msckf_ransac.h), same library and context
+RANSAC_INFO_LEN = 12
+RANSAC_MAX_SET_POINTS = 4096
+RANSAC_MAX_HYP = 256
+FRONTEND_RANSAC_SIGS = {
+    "mfe_two_point_ransac": (C.c_int, [_P, C.c_int, _I, _D, _D, _D, _D, _I, _D, C.c_double, C.c_int, _U32, _U8, _D]),
+}
+FRONTEND_RANSAC_EXPORTED = tuple(FRONTEND_RANSAC_SIGS)
+
 # multi-GPU replica transport, RCCL (include/msckf_replicas.h), same library
 REPLICA_SIGS = {
     "msckf_rccl_unique_id": (C.c_int, [_U8]),
@@ -122,7 +132,8 @@ def load_library(path: str = LIB_PATH):
             raise MsckfError("HIP extension %s is missing -- build it with `make` "
                              "(or __graft_entry__.build()); there is no CPU fallback" % path)
         lib = C.CDLL(path)
-        for name, (res, args) in list(_SIGS.items()) + list(FRONTEND_SIGS.items()) + list(REPLICA_SIGS.items()):
+        for name, (res, args) in (list(_SIGS.items()) + list(FRONTEND_SIGS.items()) +
+                                  list(FRONTEND_RANSAC_SIGS.items()) + list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -19,6 +19,8 @@
 //               bilinear weights, window sums of the integer products reduced
 //               exactly (int64) across the wave
 //   k_undistort / k_distort   radtan and equidistant camera models, fp64
+//   k_two_point_ransac   temporal outlier rejection (include/msckf_ransac.h): one
+//               workgroup per point set, one wave per hypothesis
 // Images are 8-bit, small (752 x 480 for EuRoC) and read through the cache:
 // these kernels are latency-class work, not HBM-bound.
 #include <hip/hip_runtime.h>
@@ -31,6 +33,7 @@
 #include <vector>
 
 #include "../../include/msckf_frontend.h"
+#include "../../include/msckf_ransac.h"
 
 namespace {
 
@@ -376,12 +379,12 @@ struct CamModel {
     int model;
 };
 
-__global__ void __launch_bounds__(256) k_undistort(CamModel c, int n, const double* __restrict__ in,
-                                                   double* __restrict__ out) {
+// Pixel -> normalised, undistorted coordinates (before any rectification);
+// false = the fisheye solution was rejected.  Shared by k_undistort and
+// k_two_point_ransac.
+__device__ __forceinline__ bool undistort_norm(const CamModel& c, double px, double py, double& xo, double& yo) {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
-    double x = (in[2 * t] - c.cx) / c.fx, y = (in[2 * t + 1] - c.cy) / c.fy;
+    double x = (px - c.cx) / c.fx, y = (py - c.cy) / c.fy;
     if (c.model == MFE_EQUIDISTANT) {
         // cv2.fisheye.undistortPoints (4.x) with its default criteria (COUNT +
         // EPS, 10, 1e-8): theta_d clamped to the model's 180-degree field of
@@ -403,11 +406,7 @@ __global__ void __launch_bounds__(256) k_undistort(CamModel c, int n, const doub
         } else {
             conv = true;
         }
-        if (!conv || th < 0) {
-            out[2 * t] = -1000000.0;
-            out[2 * t + 1] = -1000000.0;
-            return;
-        }
+        if (!conv || th < 0) return false;
         x = x * scale;
         y = y * scale;
     } else {   // cv2.undistortPoints: 5 fixed-point iterations
@@ -420,6 +419,22 @@ __global__ void __launch_bounds__(256) k_undistort(CamModel c, int n, const doub
             x = (x0 - dx) * icdist;
             y = (y0 - dy) * icdist;
         }
+    }
+    xo = x;
+    yo = y;
+    return true;
+}
+
+__global__ void __launch_bounds__(256) k_undistort(CamModel c, int n, const double* __restrict__ in,
+                                                   double* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    double x, y;
+    if (!undistort_norm(c, in[2 * t], in[2 * t + 1], x, y)) {
+        out[2 * t] = -1000000.0;
+        out[2 * t + 1] = -1000000.0;
+        return;
     }
     const double X = c.R[0] * x + c.R[1] * y + c.R[2];
     const double Y = c.R[3] * x + c.R[4] * y + c.R[5];
@@ -453,6 +468,221 @@ __global__ void __launch_bounds__(256) k_distort(CamModel c, int n, const double
     out[2 * t + 1] = c.fy * yd + c.cy;
 }
 
+// ------------------------------------------------------- two-point RANSAC --
+// include/msckf_ransac.h states the algorithm.  One workgroup of 8 waves per
+// point set; the set's c_i (compacted to the raw list), |d_i|, the raw ->
+// point index map and the markers live in LDS (148 KB of the CU's 160 KB at
+// the 4096-point cap).  The per-point passes spread the points over the 512
+// threads; the hypotheses go one per wave, the raw list over its 64 lanes.
+// Every sum is a per-thread partial in index order, an xor butterfly over the
+// wave and the 8 wave partials added in wave order: the same bits every run.
+constexpr int RS_THREADS = 512, RS_WAVES = RS_THREADS / 64, RS_MAXN = MFE_RANSAC_MAX_SET_POINTS;
+
+struct RansacArgs {
+    const int32_t* set_off;
+    const double *pts_prev, *pts_curr, *R, *intr, *coeffs;
+    const int32_t* model;
+    const uint32_t* draws;
+    double* work;   // [total][4]: compensated previous point, current point (normalised)
+    uint8_t* inlier;
+    double* info;
+    double inlier_error;
+    int n_hyp;
+};
+
+template <int K>
+__device__ __forceinline__ void block_sum(double (&v)[K], double* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) v[k] += __shfl_xor(v[k], m, 64);
+    __syncthreads();   // red may still be read by the reduction before
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[wave * K + k] = v[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < RS_WAVES; ++w) s += red[w * K + k];
+        v[k] = s;
+    }
+}
+
+__device__ __forceinline__ double pick3(double v0, double v1, double v2, int k) {
+    return k == 0 ? v0 : (k == 1 ? v1 : v2);
+}
+
+__global__ void __launch_bounds__(RS_THREADS) k_two_point_ransac(RansacArgs a) {
+#pragma clang fp contract(off)
+    __shared__ double s_c0[RS_MAXN], s_c1[RS_MAXN], s_c2[RS_MAXN], s_dist[RS_MAXN];
+    __shared__ int s_ridx[RS_MAXN];
+    __shared__ uint8_t s_mark[RS_MAXN];   // by point index
+    __shared__ double s_red[RS_WAVES * 5];
+    __shared__ int s_wcnt[2][RS_WAVES];
+    __shared__ double s_bm[RS_WAVES][3];
+    __shared__ int s_bi[RS_WAVES][3];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int o0 = a.set_off[s], n = a.set_off[s + 1] - o0;
+    const double nan = __builtin_nan("");
+    CamModel cam{};
+    cam.fx = a.intr[4 * s]; cam.fy = a.intr[4 * s + 1]; cam.cx = a.intr[4 * s + 2]; cam.cy = a.intr[4 * s + 3];
+    for (int i = 0; i < 4; ++i) cam.k[i] = a.coeffs[4 * s + i];
+    cam.model = a.model[s];
+    const double* R = a.R + 9 * s;
+    const double r0 = R[0], r1 = R[1], r2 = R[2], r3 = R[3], r4 = R[4], r5 = R[5];
+    double unit = 2.0 / (cam.fx + cam.fy);
+
+    // steps 2-3: undistort, rotation-compensate, sum of the norms
+    double nsum[1] = {0.0};
+    for (int i = tid; i < n; i += RS_THREADS) {
+        const size_t g = (size_t)(o0 + i);
+        double xp, yp, xc, yc;
+        if (!undistort_norm(cam, a.pts_prev[2 * g], a.pts_prev[2 * g + 1], xp, yp)) xp = yp = -1000000.0;
+        if (!undistort_norm(cam, a.pts_curr[2 * g], a.pts_curr[2 * g + 1], xc, yc)) xc = yc = -1000000.0;
+        const double xr = r0 * xp + r1 * yp + r2, yr = r3 * xp + r4 * yp + r5;
+        a.work[4 * g] = xr; a.work[4 * g + 1] = yr; a.work[4 * g + 2] = xc; a.work[4 * g + 3] = yc;
+        nsum[0] += sqrt(xr * xr + yr * yr) + sqrt(xc * xc + yc * yc);
+    }
+    block_sum(nsum, s_red);
+    const double scale = M_SQRT2 * (double)(2 * n) / nsum[0];   // step 4 (NaN for an empty set)
+    unit = unit * scale;
+
+    // steps 5-6 and 9: each thread re-reads the points it wrote; the kept ones are
+    // compacted in index order, 512 at a time (ballot rank within the wave, the wave
+    // counts of the chunk through LDS)
+    const double pre_thr = 50.0 * unit;
+    double dsum[1] = {0.0};
+    int n_raw = 0;
+    for (int c0 = 0, it = 0; c0 < n; c0 += RS_THREADS, ++it) {
+        const int i = c0 + tid;
+        bool keep = false;
+        double cx = 0.0, cy = 0.0, cz = 0.0, dist = 0.0;
+        if (i < n) {
+            const size_t g = (size_t)(o0 + i);
+            const double xp = a.work[4 * g] * scale, yp = a.work[4 * g + 1] * scale;
+            const double xc = a.work[4 * g + 2] * scale, yc = a.work[4 * g + 3] * scale;
+            const double dx = xp - xc, dy = yp - yc;
+            dist = sqrt(dx * dx + dy * dy);
+            keep = !(dist > pre_thr);
+            cx = dy; cy = -dx; cz = xp * yc - yp * xc;
+            s_mark[i] = 0;
+        }
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) s_wcnt[it & 1][wave] = __popcll(bal);
+        __syncthreads();
+        int off = n_raw, tot = 0;
+#pragma unroll
+        for (int w = 0; w < RS_WAVES; ++w) {
+            const int cw = s_wcnt[it & 1][w];
+            if (w < wave) off += cw;
+            tot += cw;
+        }
+        if (keep) {
+            const int r = off + __popcll(bal & ((1ull << lane) - 1ull));   // r <= i < RS_MAXN
+            s_c0[r] = cx; s_c1[r] = cy; s_c2[r] = cz; s_dist[r] = dist; s_ridx[r] = i;
+            dsum[0] += dist;
+        }
+        n_raw += tot;
+    }
+    block_sum(dsum, s_red);   // its barriers also publish the LDS lists
+    const double mean_dist = n_raw > 0 ? dsum[0] / (double)n_raw : nan;
+    const double thr = a.inlier_error * unit;
+
+    double status, best_h = -1.0, best_cnt = 0.0, mr0 = nan, mr1 = nan, mr2 = nan, refit_err = nan;
+    if (n_raw < 3) {   // step 7
+        status = 2.0;
+    } else if (mean_dist < unit) {   // step 8
+        double cnt[1] = {0.0};
+        for (int r = tid; r < n_raw; r += RS_THREADS) {
+            const bool mk = !(s_dist[r] > thr);
+            if (mk) s_mark[s_ridx[r]] = 1;
+            cnt[0] += mk ? 1.0 : 0.0;
+        }
+        block_sum(cnt, s_red);
+        best_cnt = cnt[0];
+        status = 1.0;
+    } else {   // step 10
+        const double need = 0.2 * (double)n;
+        int bc = -1, bh = -1, bk = 0;
+        double bm0 = 0.0, bm1 = 0.0, bm2 = 0.0;
+        for (int h = wave; h < a.n_hyp; h += RS_WAVES) {
+            const size_t dq = ((size_t)s * a.n_hyp + h) * 2;
+            const uint32_t i1 = a.draws[dq] % (uint32_t)n_raw;
+            const uint32_t i2 = (i1 + 1u + a.draws[dq + 1] % (uint32_t)(n_raw - 1)) % (uint32_t)n_raw;
+            const double a0 = s_c0[i1], a1 = s_c1[i1], a2 = s_c2[i1], b0 = s_c0[i2], b1 = s_c1[i2], b2 = s_c2[i2];
+            const double t0 = fabs(a0) + fabs(b0), t1 = fabs(a1) + fabs(b1), t2 = fabs(a2) + fabs(b2);
+            int k = 0;
+            double tm = t0;
+            if (t1 < tm) { k = 1; tm = t1; }
+            if (t2 < tm) k = 2;
+            const int ka = k == 0 ? 1 : 0, kb = k == 2 ? 1 : 2;   // the other two columns, ascending
+            const double pa = pick3(a0, a1, a2, ka), qa = pick3(a0, a1, a2, kb), ra = pick3(a0, a1, a2, k);
+            const double pb = pick3(b0, b1, b2, ka), qb = pick3(b0, b1, b2, kb), rb = pick3(b0, b1, b2, k);
+            const double det = pa * qb - qa * pb;
+            if (det == 0.0 || !isfinite(det)) continue;   // wave-uniform
+            const double x0 = (qa * rb - ra * qb) / det, x1 = (ra * pb - pa * rb) / det;
+            const double m0 = k == 0 ? 1.0 : x0, m1 = k == 1 ? 1.0 : (k == 0 ? x0 : x1), m2 = k == 2 ? 1.0 : x1;
+            int cnt = 0;
+            for (int r = lane; r < n_raw; r += 64)
+                cnt += fabs(s_c0[r] * m0 + s_c1[r] * m1 + s_c2[r] * m2) < thr ? 1 : 0;
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m, 64);
+            if ((double)cnt >= need && cnt > bc) {   // h ascends within the wave: the lowest h keeps a tie
+                bc = cnt; bh = h; bk = k; bm0 = m0; bm1 = m1; bm2 = m2;
+            }
+        }
+        if (lane == 0) {
+            s_bi[wave][0] = bc; s_bi[wave][1] = bh; s_bi[wave][2] = bk;
+            s_bm[wave][0] = bm0; s_bm[wave][1] = bm1; s_bm[wave][2] = bm2;
+        }
+        __syncthreads();
+        int ww = 0;   // the largest set; among equals the lowest h
+        for (int w = 1; w < RS_WAVES; ++w)
+            if (s_bi[w][0] > s_bi[ww][0] || (s_bi[w][0] == s_bi[ww][0] && s_bi[w][1] < s_bi[ww][1])) ww = w;
+        bc = s_bi[ww][0]; bh = s_bi[ww][1]; bk = s_bi[ww][2];
+        bm0 = s_bm[ww][0]; bm1 = s_bm[ww][1]; bm2 = s_bm[ww][2];
+        if (bc < 0) {
+            status = 3.0;
+        } else {
+            status = 0.0;
+            best_h = (double)bh;
+            best_cnt = (double)bc;
+            const int ka = bk == 0 ? 1 : 0, kb = bk == 2 ? 1 : 2;
+            double ne[5] = {0.0, 0.0, 0.0, 0.0, 0.0};   // Spp Spq Sqq Spr Sqr of the best set
+            for (int r = tid; r < n_raw; r += RS_THREADS) {
+                const double c0 = s_c0[r], c1 = s_c1[r], c2 = s_c2[r];
+                if (fabs(c0 * bm0 + c1 * bm1 + c2 * bm2) < thr) {
+                    s_mark[s_ridx[r]] = 1;
+                    const double p = pick3(c0, c1, c2, ka), q = pick3(c0, c1, c2, kb), rr = pick3(c0, c1, c2, bk);
+                    ne[0] += p * p; ne[1] += p * q; ne[2] += q * q; ne[3] += p * rr; ne[4] += q * rr;
+                }
+            }
+            block_sum(ne, s_red);
+            const double det = ne[0] * ne[2] - ne[1] * ne[1];
+            if (det != 0.0 && isfinite(det)) {
+                const double x0 = (ne[1] * ne[4] - ne[3] * ne[2]) / det, x1 = (ne[3] * ne[1] - ne[0] * ne[4]) / det;
+                mr0 = bk == 0 ? 1.0 : x0; mr1 = bk == 1 ? 1.0 : (bk == 0 ? x0 : x1); mr2 = bk == 2 ? 1.0 : x1;
+                double es[1] = {0.0};
+                for (int r = tid; r < n_raw; r += RS_THREADS)   // s_mark[..] here is the thread's own store
+                    if (s_mark[s_ridx[r]]) es[0] += fabs(s_c0[r] * mr0 + s_c1[r] * mr1 + s_c2[r] * mr2);
+                block_sum(es, s_red);
+                refit_err = es[0] / (double)bc;
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += RS_THREADS) a.inlier[o0 + i] = s_mark[i];
+    if (tid == 0) {
+        double* info = a.info + (size_t)s * MFE_RANSAC_INFO_LEN;
+        info[0] = status; info[1] = (double)n_raw; info[2] = scale; info[3] = unit; info[4] = mean_dist;
+        info[5] = best_h; info[6] = best_cnt; info[7] = mr0; info[8] = mr1; info[9] = mr2; info[10] = refit_err;
+        info[11] = 0.0;
+    }
+}
+
 }  // namespace
 
 // ================================================================ C-ABI ====
@@ -469,6 +699,11 @@ struct mfe_ctx {
     float* pts = nullptr;  // [2][max_points][2]
     uint8_t* st = nullptr;
     double* dpts = nullptr;   // [2][max_points][2]
+    // mfe_two_point_ransac: one device block (inputs | work | outputs) and one pinned
+    // host block (inputs | outputs), grown to the largest call seen
+    unsigned char* rs_dev = nullptr;
+    unsigned char* rs_host = nullptr;
+    size_t rs_dev_cap = 0, rs_host_cap = 0;
 };
 
 namespace {
@@ -558,6 +793,8 @@ int mfe_destroy(mfe_ctx_t* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (void* p : c->allocs) (void)hipFree(p);
+    if (c->rs_dev) (void)hipFree(c->rs_dev);
+    if (c->rs_host) (void)hipHostFree(c->rs_host);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return 0;
@@ -673,6 +910,85 @@ int mfe_distort(mfe_ctx_t* c, int n, const double* pts_in, double* pts_out, cons
                 const double* coeffs) {
     if (!intrinsics) MFE_FAIL(-1, "null intrinsics");
     return cam_call(c, n, pts_in, pts_out, make_model(intrinsics, model, coeffs, nullptr, nullptr), false);
+}
+
+int mfe_two_point_ransac(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const double* pts_prev,
+                         const double* pts_curr, const double* R_p_c, const double* intrinsics, const int32_t* model,
+                         const double* coeffs, double inlier_error, int n_hyp, const uint32_t* draws,
+                         uint8_t* inlier_out, double* info_out) {
+    if (!c) MFE_FAIL(-1, "null context");
+    if (n_sets < 0) MFE_FAIL(-1, "n_sets = %d is negative", n_sets);
+    if (n_sets == 0) return 0;
+    if (!set_off) MFE_FAIL(-1, "null set_off");
+    if (set_off[0] != 0) MFE_FAIL(-1, "set_off[0] = %d, must be 0", set_off[0]);
+    for (int s = 0; s < n_sets; ++s) {
+        const long long ns = (long long)set_off[s + 1] - set_off[s];
+        if (ns < 0) MFE_FAIL(-1, "set_off is not monotone at set %d", s);
+        if (ns > MFE_RANSAC_MAX_SET_POINTS)
+            MFE_FAIL(-1, "set %d has %lld points, above the cap of %d", s, ns, MFE_RANSAC_MAX_SET_POINTS);
+    }
+    const size_t T = (size_t)set_off[n_sets], S = (size_t)n_sets;
+    if (T == 0) return 0;
+    if (!pts_prev || !pts_curr || !R_p_c || !intrinsics || !model || !coeffs || !draws || !inlier_out || !info_out)
+        MFE_FAIL(-1, "null argument");
+    if (n_hyp < 1 || n_hyp > MFE_RANSAC_MAX_HYP) MFE_FAIL(-1, "n_hyp %d outside [1, %d]", n_hyp, MFE_RANSAC_MAX_HYP);
+    for (int s = 0; s < n_sets; ++s)
+        if (model[s] != MFE_RADTAN && model[s] != MFE_EQUIDISTANT)
+            MFE_FAIL(-1, "unknown distortion model %d (set %d)", model[s], s);
+    MFE_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // byte offsets; the fp64 sections first, so that every section is aligned to its element
+    const size_t H = (size_t)n_hyp;
+    const size_t o_prev = 0, o_curr = o_prev + 16 * T, o_R = o_curr + 16 * T, o_intr = o_R + 72 * S,
+                 o_coef = o_intr + 32 * S, o_off = o_coef + 32 * S, o_model = o_off + 4 * (S + 1),
+                 o_draw = o_model + 4 * S, in_bytes = (o_draw + 8 * S * H + 7) & ~(size_t)7;
+    const size_t o_work = in_bytes, o_info = o_work + 32 * T, o_inl = o_info + 8 * MFE_RANSAC_INFO_LEN * S,
+                 out_bytes = 8 * MFE_RANSAC_INFO_LEN * S + T, dev_bytes = o_inl + T;
+    if (dev_bytes > c->rs_dev_cap) {   // nothing is in flight: every call ends with a synchronisation
+        if (c->rs_dev) (void)hipFree(c->rs_dev);
+        c->rs_dev = nullptr;
+        c->rs_dev_cap = 0;
+        MFE_HIP(hipMalloc((void**)&c->rs_dev, dev_bytes));
+        c->rs_dev_cap = dev_bytes;
+    }
+    if (in_bytes + out_bytes > c->rs_host_cap) {
+        if (c->rs_host) (void)hipHostFree(c->rs_host);
+        c->rs_host = nullptr;
+        c->rs_host_cap = 0;
+        MFE_HIP(hipHostMalloc((void**)&c->rs_host, in_bytes + out_bytes, hipHostMallocDefault));
+        c->rs_host_cap = in_bytes + out_bytes;
+    }
+    unsigned char *hin = c->rs_host, *hout = c->rs_host + in_bytes, *d = c->rs_dev;
+    memcpy(hin + o_prev, pts_prev, 16 * T);
+    memcpy(hin + o_curr, pts_curr, 16 * T);
+    memcpy(hin + o_R, R_p_c, 72 * S);
+    memcpy(hin + o_intr, intrinsics, 32 * S);
+    memcpy(hin + o_coef, coeffs, 32 * S);
+    memcpy(hin + o_off, set_off, 4 * (S + 1));
+    memcpy(hin + o_model, model, 4 * S);
+    memcpy(hin + o_draw, draws, 8 * S * H);
+    MFE_HIP(hipMemcpyAsync(d, hin, in_bytes, hipMemcpyHostToDevice, st));
+    RansacArgs a;
+    a.set_off = (const int32_t*)(d + o_off);
+    a.pts_prev = (const double*)(d + o_prev);
+    a.pts_curr = (const double*)(d + o_curr);
+    a.R = (const double*)(d + o_R);
+    a.intr = (const double*)(d + o_intr);
+    a.coeffs = (const double*)(d + o_coef);
+    a.model = (const int32_t*)(d + o_model);
+    a.draws = (const uint32_t*)(d + o_draw);
+    a.work = (double*)(d + o_work);
+    a.info = (double*)(d + o_info);
+    a.inlier = d + o_inl;
+    a.inlier_error = inlier_error;
+    a.n_hyp = n_hyp;
+    hipLaunchKernelGGL(k_two_point_ransac, dim3(n_sets), dim3(RS_THREADS), 0, st, a);
+    MFE_HIP(hipGetLastError());
+    MFE_HIP(hipMemcpyAsync(hout, d + o_info, out_bytes, hipMemcpyDeviceToHost, st));
+    MFE_HIP(hipStreamSynchronize(st));
+    memcpy(info_out, hout, 8 * MFE_RANSAC_INFO_LEN * S);
+    memcpy(inlier_out, hout + 8 * MFE_RANSAC_INFO_LEN * S, T);
+    return 0;
 }
 
 }  // extern "C"

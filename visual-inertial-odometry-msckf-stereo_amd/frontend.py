@@ -12,15 +12,22 @@ published message -- and every image operator runs in the HIP kernels of
                                                             built by mfe_upload)
   undistortPoints / fisheye (image.py:640-674)  mfe_undistort
   projectPoints / fisheye (image.py:676-702)    mfe_distort
+  RANSAC stub (image.py:292-293)                mfe_two_point_ransac (k_two_point_ransac,
+                                                include/msckf_ransac.h), opt-in
 
 cv2 is absent here and on the GPU box: the kernels restate the published
 OpenCV 4.x algorithms (oracle/frontend_oracle.py), parity unpinned against cv2
 itself.  Method names, arguments and the message layout follow the reference
 (including its spelling ``stareo_callback``), so ``vio.py`` can construct this
-class in place of its own.  The reference's stubs are kept as they are: RANSAC
-marks every match an inlier (image.py:292-293) and ``rescale_points`` is unused.
-There is no CPU fallback: without the HIP library or a GPU the constructor
-raises.
+class in place of its own.  The reference's stubs are kept as they are by
+default: RANSAC marks every match an inlier (image.py:292-293) and
+``rescale_points`` is unused.  ``FrontendConfig.ransac_enabled = True`` puts
+the two-point RANSAC the stub stands for (Sun et al., msckf_vio) in its place:
+one device call per frame over the cam0 and cam1 temporal matches with the
+IMU-predicted rotations, ``ransac_threshold`` its inlier error in pixels, the
+hypothesis draws from a seeded generator (``ransac_seed``) so that a replay
+repeats.  There is no CPU fallback: without the HIP library or a GPU the
+constructor raises.
 """
 from __future__ import annotations
 
@@ -38,6 +45,26 @@ RADTAN, EQUIDISTANT = 0, 1
 
 FeatureMeasurement = namedtuple("FeatureMeasurement", ["id", "u0", "v0", "u1", "v1"])
 FeatureMsg = namedtuple("vio_feature_msg__", ["timestamp", "vio_features"])
+
+
+class RansacInfo(namedtuple("RansacInfo", ["status", "n_raw", "scale", "unit", "mean_dist", "best_h", "best_count",
+                                           "m_refit", "refit_err"])):
+    """One set's info record of mfe_two_point_ransac (msckf_ransac.h).  status:
+    0 = RANSAC ran, 1 = degenerate motion, 2 = fewer than 3 points after the
+    pre-filter, 3 = no hypothesis qualified; undefined fields are NaN."""
+    __slots__ = ()
+
+    @classmethod
+    def from_row(cls, row):
+        r = np.asarray(row, float)
+        return cls(int(r[0]), int(r[1]), float(r[2]), float(r[3]), float(r[4]), int(r[5]), int(r[6]),
+                   r[7:10].copy(), float(r[10]))
+
+
+def ransac_hypotheses(success_probability):
+    """Number of two-point hypotheses for the given success probability at an
+    assumed inlier share of 0.7 (msckf_vio): 7 at 0.99."""
+    return int(np.ceil(np.log(1.0 - success_probability) / np.log(1.0 - 0.7 * 0.7)))
 
 
 def _default_T_imu_cam1():
@@ -75,6 +102,11 @@ class FrontendConfig:
         default_factory=lambda: np.array([-0.28368365, 0.07451284, -0.00010473, -3.55590700e-05]))
     cam1_intrinsics: np.ndarray = field(default_factory=lambda: np.array([457.587, 456.134, 379.999, 255.238]))
     cam1_resolution: np.ndarray = field(default_factory=lambda: np.array([752, 480]))
+    # not in the reference: the two-point RANSAC its track_features stubs (off = the stub);
+    # ransac_threshold above is its inlier error in pixels
+    ransac_enabled: bool = False
+    ransac_success_probability: float = 0.99
+    ransac_seed: int = 0
 
     @property
     def grid_num(self):
@@ -212,6 +244,42 @@ class Frontend:
         f64 = lambda a: np.ascontiguousarray(np.asarray(a, float).ravel())
         return self._cam(self.lib.mfe_distort, pts, f64(intrinsics), int(model), f64(coeffs))
 
+    def two_point_ransac(self, sets, inlier_error, n_hyp, draws):
+        """mfe_two_point_ransac (include/msckf_ransac.h) over a list of point
+        sets in one launch.  ``sets``: (pts_prev, pts_curr, R_p_c, intrinsics,
+        model, coeffs) per set, points in pixels; ``draws``: uint32 (n_sets,
+        n_hyp, 2).  Returns one (inliers bool array, RansacInfo) per set."""
+        S = len(sets)
+        prev = [np.asarray(s[0], float).reshape(-1, 2) for s in sets]
+        curr = [np.asarray(s[1], float).reshape(-1, 2) for s in sets]
+        for p, q in zip(prev, curr):
+            if len(p) != len(q):
+                raise ValueError("a set's point lists differ in length (%d, %d)" % (len(p), len(q)))
+        off = np.zeros(S + 1, np.int32)
+        off[1:] = np.cumsum([len(p) for p in prev])
+        T = int(off[-1])
+        draws = np.ascontiguousarray(draws, np.uint32)
+        if draws.shape != (S, int(n_hyp), 2):
+            raise ValueError("draws of shape %s, expected %s" % (draws.shape, (S, int(n_hyp), 2)))
+        cat = lambda a, w: np.ascontiguousarray(np.concatenate(a).reshape(-1, w)) if a else np.zeros((0, w))
+        pp, pc = cat(prev, 2), cat(curr, 2)
+        R = cat([np.asarray(s[2], float).reshape(1, 9) for s in sets], 9)
+        K = cat([np.asarray(s[3], float).reshape(1, 4) for s in sets], 4)
+        model = np.array([int(s[4]) for s in sets], np.int32)
+        k = cat([np.asarray(s[5], float).reshape(1, 4) for s in sets], 4)
+        inl = np.zeros(T, np.uint8)
+        # the record of an empty set; a call without points launches nothing and leaves it
+        info = np.full((S, _lib.RANSAC_INFO_LEN), np.nan)
+        info[:, [0, 1, 5, 6, 11]] = [2.0, 0.0, -1.0, 0.0, 0.0]
+        dp = C.POINTER(C.c_double)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.mfe_two_point_ransac(
+            self.h, S, off.ctypes.data_as(ip), pp.ctypes.data_as(dp), pc.ctypes.data_as(dp), R.ctypes.data_as(dp),
+            K.ctypes.data_as(dp), model.ctypes.data_as(ip), k.ctypes.data_as(dp), float(inlier_error), int(n_hyp),
+            draws.ctypes.data_as(C.POINTER(C.c_uint32)), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
+            info.ctypes.data_as(dp)))
+        return [(inl[off[s]:off[s + 1]].astype(bool), RansacInfo.from_row(info[s])) for s in range(S)]
+
 
 def _model(name):
     return EQUIDISTANT if name == "equidistant" else RADTAN
@@ -224,7 +292,9 @@ class ImageProcessor:
     ``angular_velocity`` (dataset.py:56-57, 101, 169-170)."""
 
     # image slots: the previous cam0 image and the current pair rotate over three
-    def __init__(self, config=None, device=0):
+    def __init__(self, config=None, device=0, ransac_fn=None):
+        """``ransac_fn`` (signature of Frontend.two_point_ransac) replaces the
+        device call of the two-point RANSAC when config.ransac_enabled."""
         if config is None:
             config = FrontendConfig()
         elif not isinstance(config, FrontendConfig):
@@ -258,6 +328,9 @@ class ImageProcessor:
         self._slot_prev, self._slot_c0, self._slot_c1 = 0, 1, 2
         self.lk_kw = dict(win=config.patch_size, max_level=config.pyramid_levels,
                           max_iter=config.max_iteration, eps=config.track_precision)
+        self.ransac_fn = ransac_fn   # None: self.fe.two_point_ransac
+        self.ransac_n_hyp = ransac_hypotheses(config.ransac_success_probability)
+        self.ransac_rng = np.random.default_rng(config.ransac_seed)   # advanced once per tracked frame
 
     # ---- callbacks (image.py:95-147) ----
     def stareo_callback(self, stereo_msg):
@@ -324,6 +397,8 @@ class ImageProcessor:
         img = self.cam0_curr_img_msg.image
         gh, gw = self.get_grid_size(img)
         cam0_R_p_c, cam1_R_p_c = self.integrate_imu_data()
+        if self.config.ransac_enabled:   # once per tracked frame, whatever the frame holds: a replay repeats
+            draws = self.ransac_rng.integers(0, 1 << 32, size=(2, self.ransac_n_hyp, 2), dtype=np.uint32)
         prev_ids, prev_lifetime, prev_cam0_points, prev_cam1_points = [], [], [], []
         for f in chain.from_iterable(self.prev_features):
             prev_ids.append(f.id)
@@ -353,8 +428,16 @@ class ImageProcessor:
         curr_matched_cam0_points = _select(curr_tracked_cam0_points, match_inliers)
         curr_matched_cam1_points = _select(curr_cam1_points, match_inliers)
         self.num_features["after_matching"] = len(curr_matched_cam0_points)
+        ransac_inliers = None
+        if self.config.ransac_enabled:
+            ransac_inliers = self.two_point_ransac(
+                _select(_select(prev_cam0_points, track_inliers), match_inliers), curr_matched_cam0_points,
+                _select(_select(prev_cam1_points, track_inliers), match_inliers), curr_matched_cam1_points,
+                cam0_R_p_c, cam1_R_p_c, draws)
         after_ransac = 0
         for i in range(len(curr_matched_cam0_points)):   # RANSAC stub: all inliers (image.py:292-293)
+            if ransac_inliers is not None and not ransac_inliers[i]:
+                continue
             f = FeatureMetaData()
             f.id = prev_matched_ids[i]
             f.lifetime = prev_matched_lifetime[i] + 1
@@ -363,6 +446,18 @@ class ImageProcessor:
             self.curr_features[self._grid_code(curr_matched_cam0_points[i], gh, gw)].append(f)
             after_ransac += 1
         self.num_features["after_ransac"] = after_ransac
+
+    def two_point_ransac(self, prev_cam0, curr_cam0, prev_cam1, curr_cam1, cam0_R_p_c, cam1_R_p_c, draws):
+        """The step the reference stubs (image.py:292-293), as in msckf_vio:
+        the two-point RANSAC of cam0 prev -> curr and of cam1 prev -> curr, both
+        in one device call; a feature stays only if it is an inlier of both."""
+        sets = [(prev_cam0, curr_cam0, cam0_R_p_c, self.cam0_intrinsics, _model(self.cam0_distortion_model),
+                 self.cam0_distortion_coeffs),
+                (prev_cam1, curr_cam1, cam1_R_p_c, self.cam1_intrinsics, _model(self.cam1_distortion_model),
+                 self.cam1_distortion_coeffs)]
+        fn = self.ransac_fn if self.ransac_fn is not None else self.fe.two_point_ransac
+        (in0, _), (in1, _) = fn(sets, self.config.ransac_threshold, self.ransac_n_hyp, draws)
+        return np.logical_and(in0, in1)
 
     def add_new_features(self):
         """image.py:317-390."""
