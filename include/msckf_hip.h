@@ -13,8 +13,10 @@
  *   - plain pointers and sizes; host arrays are caller-owned and copied in/out;
  *     device buffers are context-owned.
  *   - return 0 on success, >0 for a benign no-op, <0 for an error (HIP failure,
- *     bad argument, non-positive-definite innovation covariance).  Nothing
- *     throws across the ABI.  msckf_last_error() gives a message.
+ *     bad argument, non-positive-definite innovation covariance; -4 from the
+ *     result readers: a track length no gating kernel is instantiated for, an
+ *     internal inconsistency of the class tables).  Nothing throws across the
+ *     ABI.  msckf_last_error() gives a message.
  *   - asynchronous calls (set_state, propagate, augment, prune, their batch
  *     forms, batch_load / batch_update / batch_triangulate, restore) enqueue
  *     work on the context's stream and return without waiting.  A kernel fault

@@ -225,15 +225,17 @@ def test_update_rejects_corrupted_covariance(corrupt):
         P[30, 30] = np.nan
     assert corrupt == "nan" or np.linalg.eigvalsh(P[21:, 21:]).min() < -1e-3 * np.abs(np.diag(P)[21:]).max()
     ctx = Context(FilterConfig(), n_filters=1, n_cam_capacity=int(d["N"]) + 2)
-    ctx.set_state(0, imu_record(d), pack_cams(d["cam_q"], d["cam_p"], d["cam_q_null"]), P)
-    sel = [f for f in range(int(d["F"])) if d["tri_ok"][f]]
-    obs = [feature_obs(d, f) for f in sel]
-    off = np.concatenate([[0], np.cumsum([len(o) for o in obs])])
-    cams = [c for o in obs for c, _ in o]
-    zs = [z for o in obs for _, z in o]
-    with pytest.raises(RuntimeError, match="rc=-3"):
-        ctx.update(0, off, cams, zs, d["tri_p"][sel], np.full(len(sel), 1e30))
-    ctx.close()
+    try:
+        ctx.set_state(0, imu_record(d), pack_cams(d["cam_q"], d["cam_p"], d["cam_q_null"]), P)
+        sel = [f for f in range(int(d["F"])) if d["tri_ok"][f]]
+        obs = [feature_obs(d, f) for f in sel]
+        off = np.concatenate([[0], np.cumsum([len(o) for o in obs])])
+        cams = [c for o in obs for c, _ in o]
+        zs = [z for o in obs for _, z in o]
+        with pytest.raises(RuntimeError, match="rc=-3"):
+            ctx.update(0, off, cams, zs, d["tri_p"][sel], np.full(len(sel), 1e30))
+    finally:
+        ctx.close()
 
 
 def test_update_empty_is_noop():
@@ -277,36 +279,38 @@ def test_stage_c_pivot_bound_every_path(ncams, chol, depth, fails, monkeypatch):
     p = 1e-3 * (1.0 + np.random.default_rng(5).random(D))
     P = np.diag(p)
     ctx = Context(FilterConfig(), n_filters=1, n_cam_capacity=ncams, dtype=np.float64)
-    imu, cams = imu_record(d), pack_cams(pr.cam_q, pr.cam_p, pr.cam_q_null)
-    ctx.set_state(0, imu, cams, P)
-    ctx.batch_load([0, pr.F], pr.obs_off, pr.obs_cam, pr.obs_z, None, np.full(pr.F, 1e30))
-    ctx.batch_update(row_cap=0, triangulate=True)
-    rows = ctx.batch_results()[4]
-    assert rows[0] > 0
-    s2 = FilterConfig().observation_noise
-    dg = np.ones(Cn)
-    dg[Cn // 2] = -depth
-    H = np.zeros((Cn, Cn + 1))
-    H[:, :Cn] = np.diag((dg - s2) / p[21:])
-    H[:, Cn] = 1e-3
-    ctx.set_state(0, imu, cams, P)   # the pre-update state again
-    _debug_call(ctx, "msckf_debug_set_workspace", 6, H.ctypes.data_as(C.POINTER(C.c_double)), H.size)
-    _debug_call(ctx, "msckf_debug_kalman")
-    if fails:
-        with pytest.raises(RuntimeError, match="innovation covariance not positive definite.*rc=-3"):
+    try:
+        imu, cams = imu_record(d), pack_cams(pr.cam_q, pr.cam_p, pr.cam_q_null)
+        ctx.set_state(0, imu, cams, P)
+        ctx.batch_load([0, pr.F], pr.obs_off, pr.obs_cam, pr.obs_z, None, np.full(pr.F, 1e30))
+        ctx.batch_update(row_cap=0, triangulate=True)
+        rows = ctx.batch_results()[4]
+        assert rows[0] > 0
+        s2 = FilterConfig().observation_noise
+        dg = np.ones(Cn)
+        dg[Cn // 2] = -depth
+        H = np.zeros((Cn, Cn + 1))
+        H[:, :Cn] = np.diag((dg - s2) / p[21:])
+        H[:, Cn] = 1e-3
+        ctx.set_state(0, imu, cams, P)   # the pre-update state again
+        _debug_call(ctx, "msckf_debug_set_workspace", 6, H.ctypes.data_as(C.POINTER(C.c_double)), H.size)
+        _debug_call(ctx, "msckf_debug_kalman")
+        if fails:
+            with pytest.raises(RuntimeError, match="innovation covariance not positive definite.*rc=-3"):
+                ctx.batch_results()
+        else:
             ctx.batch_results()
-    else:
-        ctx.batch_results()
-        _, _, P1 = ctx.get_state(0)
-        assert np.isfinite(P1).all()
-        # P+_cc = s2 Lc T^-1 Lc^T = s2 diag(p_cc / T_ii): the floored pivot (s2 in
-        # place of -1e-12) leaves its variance unchanged, the others shrink by s2
-        dd = np.diag(P1)[21:]
-        k = Cn // 2
-        assert abs(dd[k] - p[21 + k]) < 1e-9 * p[21 + k]
-        other = np.arange(Cn) != k
-        np.testing.assert_allclose(dd[other], s2 * p[21:][other], rtol=1e-9)
-    ctx.close()
+            _, _, P1 = ctx.get_state(0)
+            assert np.isfinite(P1).all()
+            # P+_cc = s2 Lc T^-1 Lc^T = s2 diag(p_cc / T_ii): the floored pivot (s2 in
+            # place of -1e-12) leaves its variance unchanged, the others shrink by s2
+            dd = np.diag(P1)[21:]
+            k = Cn // 2
+            assert abs(dd[k] - p[21 + k]) < 1e-9 * p[21 + k]
+            other = np.arange(Cn) != k
+            np.testing.assert_allclose(dd[other], s2 * p[21:][other], rtol=1e-9)
+    finally:
+        ctx.close()
 
 
 # --------------------------------------------------- full-size batched mode --
@@ -332,15 +336,16 @@ def _batched(problems, dtype, triangulate=True, row_cap=0, cap=None):
                                        (34, 60, 1, None), (50, 120, 1, None), (50, 120, 1, 50), (80, 40, 1, None),
                                        (100, 20, 1, None)])
 def test_batched_fp64_vs_oracle(N, F, B, cap):
-    """cap = cam capacity of the context (default N).  Paths exercised:
+    """cap = cam capacity of the context (default N + 2, make_ctx).  Paths exercised:
     30 -- register-tile Kalman stages, the fused information assembly
     (k_info_fused, A stored as its lower triangle), one-wave gating for every
-    size class; 30 in cap 32 and 32 -- the largest register-tile Kalman
-    window and the full 12 x 12 tile triangle (32 cams: C = 192);
+    size class; 30 in cap 32 -- the largest register-tile Kalman window (12 x 12
+    tiles) with 30 live cams; 32 (cap 34) -- the smallest global-memory Kalman
+    window (32 live cams in the register-tile window, C = 192 with no padding
+    row: test_gpu_track_sweep);
     20 x 480 -- more features per filter than the fused assembly's LDS holds
     (> 453): Gram records through k_info_mfma (lower triangle of A) into the same stage B;
-    34 (cap 36) -- the one-workgroup-per-tile-row k_info and the smallest
-    global-memory Kalman window; 50 (cap 50: four staged features per k_info
+    34 (cap 36) -- the one-workgroup-per-tile-row k_info; 50 (cap 50: four staged features per k_info
     batch, cap 52: three) -- multi-workgroup assembly, global-memory Kalman stages A / C,
     k_gate_mfma_wt on fp64 MFMA; 80 -- tracks longer than 64 observations (two
     per lane in k_feature, cam masks beyond bit 63), the MFMA assembly over six
@@ -455,11 +460,13 @@ def test_gate_fp32_gamma_vs_oracle(N, F, B, cap):
     """fp32 gating on MFMA tiles against the oracle's fp64 gamma
     (msckf.py:606-614).  N = 30 (cam capacity 30, the bench's workload);
     N = 40: every one-wave size class (1..8 16-row blocks,
-    single- and multi-pass Y staging); N = 82: also the four-wave workgroup
-    kernel for 40 < M <= 82 (up to 16 blocks, Y staged in passes); N = 100:
-    also the class beyond 82 observations (the workgroup LDS kernel k_gate_lds
-    / its global-memory variant k_gate, fed by k_feature's compact QR
-    factors), up to the longest track the chi2 table gates.  Tolerance:
+    single- and multi-pass Y staging); N = 82: also the multi-wave workgroup
+    kernel k_gate_mfma_wt for 41 < M <= 82 (9 .. 16 blocks on two, four or
+    eight waves, Y staged in passes; M = 41, 8 blocks, still one wave); N = 100:
+    also the class beyond 82 observations (the global-memory workgroup kernel
+    k_gate, fed by k_feature's compact QR factors: its LDS variant k_gate_lds
+    would need ~442 KB at M = 83 and is never launched), up to the longest
+    track the chi2 table gates.  Tolerance:
     fp32 with the saddle point's conditioning (~1e3) -- median relative error
     <= 1e-4, 99th percentile <= 1e-3; decisions: at most 1 % of the features
     differ, and only where the oracle's gamma is within 5 % of the threshold."""

@@ -1,0 +1,130 @@
+"""CPU checks of the track-length sweep (tests/track_sweep.py): the builder
+conditions the GPU sweep relies on, for the pinned seeds, and the comparator's
+self-test -- check_sweep must pass on the reference itself and raise on every
+subtly wrong result it is there to catch, so the GPU tests would fail on a
+subtly wrong kernel without one being needed to show it."""
+import numpy as np
+import pytest
+
+import track_sweep as ts
+from track_sweep import ROUTE_BOUNDS, SWEEP_SEEDS, cached_sweep, check_sweep, got_from_ref, route_of, scrambled
+
+
+@pytest.fixture(scope="module", params=sorted(SWEEP_SEEDS))
+def pair(request):
+    """The two filters of the main batch of window N: (N, [(problem, reference)] for flip 0, 1)."""
+    N = request.param
+    return N, [cached_sweep(N, SWEEP_SEEDS[N] + flip, flip) for flip in (0, 1)]
+
+
+def test_route_table_matches_block_counts():
+    """ROUTE_BOUNDS restates the device's routing: GateClasses::LIM =
+    {4, 9, 14, 20, 25, 30, 36, 40, 82}, block count ceil((3M + 4) / 16) = 8 .. 16
+    inside 41..82 with 41 alone in the first sub-list, M >= 83 last."""
+    assert len(ROUTE_BOUNDS) == 8 + 9 + 1
+    assert [hi for _, hi in ROUTE_BOUNDS[:9]] == [4, 9, 14, 20, 25, 30, 36, 40, 41]
+    assert ROUTE_BOUNDS[16] == (79, 82) and ROUTE_BOUNDS[17] == (83, 128)
+    for M in range(2, 129):
+        lo, hi = ROUTE_BOUNDS[route_of(M)]
+        assert lo <= M <= hi, M
+    for r, (lo, hi) in enumerate(ROUTE_BOUNDS[8:17]):
+        assert {-(-(3 * M + 4) // 16) for M in range(lo, hi + 1)} == {8 + r}
+
+
+def test_builder_conditions(pair):
+    N, filters = pair
+    routes = sorted({route_of(M) for M in range(2, N + 1)})
+    seen = {r: dict(acc=set(), gap=set()) for r in routes}
+    for flip, (pr, ref) in enumerate(filters):
+        M = pr.track_lengths()
+        assert sorted(M) == list(range(2, N + 1))                 # one feature for every length
+        assert list(M) != sorted(M)                               # shuffled: class lists not monotone in feature index
+        assert ref.tri_ok.all()                                   # the reference triangulates every feature
+        assert np.isfinite(ref.gamma).all() and (ref.gamma > 0).all()
+        np.testing.assert_array_equal(ref.acc, (M // 2 + flip) % 2 == 0)
+        np.testing.assert_array_equal(ref.chi2, ref.gamma * np.where(ref.acc, 2.0, 0.5))
+        assert ref.rows == int((4 * M[ref.acc] - 3).sum())
+        for f in range(pr.F):
+            c = pr.obs_cam[pr.obs_off[f]:pr.obs_off[f + 1]]
+            assert len(set(c)) == len(c) and (np.diff(c) > 0).all()   # no duplicate slots, ascending
+            assert 0 <= c.min() and c.max() < N
+            assert ref.gapped[f] == ((M[f] + flip) % 2 == 1 and M[f] != N)
+            seen[ref.route[f]]["acc"].add(bool(ref.acc[f]))
+            seen[ref.route[f]]["gap"].add(bool(ref.gapped[f]))
+        f = int(np.flatnonzero(M == N)[0])                         # M = N uses every cam slot
+        np.testing.assert_array_equal(pr.obs_cam[pr.obs_off[f]:pr.obs_off[f + 1]], np.arange(N))
+        for edge in ts.SEG_EDGES:                                  # every SegClasses edge up to N
+            assert edge > N or edge in M
+    for r in routes:   # over the two filters: accepted and rejected, contiguous and gapped in every route
+        assert seen[r]["acc"] == {True, False}, ts.route_name(r)
+        assert seen[r]["gap"] == {True, False}, ts.route_name(r)
+    assert len(routes) == (18 if N == 128 else 7)
+    # the two filters differ in state as well as in tracks
+    assert not np.array_equal(filters[0][0].P, filters[1][0].P)
+
+
+def test_scrambled_permutes_rows_together(pair):
+    N, filters = pair
+    pr = filters[1][0]
+    sc = scrambled(pr)
+    np.testing.assert_array_equal(sc.obs_off, pr.obs_off)
+    moved = 0
+    for f in range(pr.F):
+        a, b = pr.obs_off[f], pr.obs_off[f + 1]
+        key = np.argsort(sc.obs_cam[a:b], kind="stable")
+        np.testing.assert_array_equal(sc.obs_cam[a:b][key], pr.obs_cam[a:b])
+        np.testing.assert_array_equal(sc.obs_z[a:b][key], pr.obs_z[a:b])
+        if not ts.is_gapped(pr)[f]:
+            np.testing.assert_array_equal(sc.obs_cam[a:b], pr.obs_cam[a:b][::-1])
+        moved += int((sc.obs_cam[a:b] != pr.obs_cam[a:b]).any())
+    assert moved == pr.F
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_comparator_passes_on_reference(pair, dtype):
+    for pr, ref in pair[1]:
+        out = check_sweep(ref, got_from_ref(ref), dtype, "self")
+        assert out["rel_P"] == 0.0 and max(out["route_worst"].values()) == 0.0
+
+
+def _doctored(kind, ref, other):
+    got = got_from_ref(ref)
+    f = int(np.flatnonzero(ref.M == 17)[0])
+    if kind == "gamma_1e-6":
+        got["gamma"][f] *= 1 + 1e-6
+    elif kind == "route_1e-3":
+        got["gamma"][ref.route == route_of(17)] *= 1 + 1e-3
+    elif kind == "gamma_5pct":
+        got["gamma"][f] *= 1.05
+    elif kind == "accept":
+        got["accept"][f] = not got["accept"][f]
+    elif kind == "stale":          # feature f keeps what the other filter's batch left at index f
+        got["gamma"][f], got["accept"][f] = other.gamma[f], other.acc[f]
+    elif kind == "valid":
+        got["valid"][f] = False
+    elif kind == "valid_two":
+        got["valid"][[f, int(np.flatnonzero(ref.M == 18)[0])]] = False
+    elif kind == "rows":
+        got["rows"] += 4 * int(ref.M[f]) - 3
+    elif kind == "P_block":
+        blk = got["P"][21 + 6 * 3:21 + 6 * 4, 21 + 6 * 3:21 + 6 * 4]   # cam 3's block, moved by 1e-8 |P|_F
+        blk *= 1 + 1e-8 * np.linalg.norm(ref.P) / np.linalg.norm(blk)
+    return got
+
+
+@pytest.mark.parametrize("dtype,kind", [
+    (np.float64, "gamma_1e-6"), (np.float32, "route_1e-3"), (np.float32, "gamma_5pct"),
+    (np.float64, "accept"), (np.float32, "accept"), (np.float64, "stale"), (np.float32, "stale"),
+    (np.float64, "valid"), (np.float32, "valid"), (np.float32, "valid_two"),
+    (np.float64, "rows"), (np.float32, "rows"), (np.float64, "P_block")])
+def test_comparator_rejects(pair, dtype, kind):
+    """Each doctored result is one a subtly wrong kernel would produce: one
+    feature's gamma off by 1e-6 (fp64), a whole route's gamma off by 1e-3 or one
+    feature's by 5 % (fp32: inside the 2 x decision margin, so only the gamma
+    bounds can see it), a flipped decision, a feature that kept the other
+    batch's gamma and decision, a lost feature, a wrong row count, one cam
+    block of P off by 1e-8 of |P| (fp64)."""
+    (_, ref), (_, other) = pair[1]
+    check_sweep(ref, got_from_ref(ref), dtype, kind)
+    with pytest.raises(AssertionError):
+        check_sweep(ref, _doctored(kind, ref, other), dtype, kind)

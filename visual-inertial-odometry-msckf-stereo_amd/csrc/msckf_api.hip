@@ -164,6 +164,7 @@ struct msckf_ctx {
     DBuf<int> info, afail;
     // feature batch
     int nf = 0, maxM = 0, max_nf = 0, max_obs = 0;   // per filter, of the loaded batch
+    int gate_unrouted = 0;   // block count launch_gate found no kernel for in the last update chain (0: none)
     std::vector<int> h_feat_off;
     // One arena per loaded batch (load_features): the host inputs arrive in ONE
     // H2D copy, and the per-feature results [valid | p_w | include | gamma]
@@ -610,7 +611,7 @@ int run_update_chain(msckf_ctx* c, int row_cap, bool triangulate) {
     launch_feature<T>(s, st, prm, fb, c->sc);
     c->timer.end(s);
     c->timer.begin(s, "gate");
-    launch_gate<T>(s, st, prm, fb, c->gc);
+    c->gate_unrouted = launch_gate<T>(s, st, prm, fb, c->gc);   // reported by unpack_results
     c->timer.end(s);
     c->timer.begin(s, "select");
     launch_select<T>(s, st, fb, ws, row_cap);
@@ -664,6 +665,9 @@ int unpack_results(msckf_ctx* c, const DownList& d, const ResultsRead& r, uint8_
         for (int f = 0; f < nf; ++f) valid_out[f] = base[f] != 0;
     if (gamma_out && nf) to_double<T>(gamma_out, base + (c->gamma - c->valid), nf);
     if (p_w_out && nf) to_double<T>(p_w_out, base + (c->p_w - c->valid), (size_t)nf * 3);
+    if (c->gate_unrouted)   // gamma / accept of those features are the previous batch's
+        FAIL(-4, "no gating kernel for tracks of %d 16-row blocks (%d-byte scalars): the class table and the "
+                 "instantiated kernels disagree", c->gate_unrouted, c->scalar);
     const int* info = reinterpret_cast<const int*>(d.at(c, r.o_info));
     int bad = -1;
     for (int b = 0; b < c->B; ++b) {

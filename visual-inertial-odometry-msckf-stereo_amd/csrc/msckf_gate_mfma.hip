@@ -657,7 +657,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gm_wav
 // (Replaces round 5's k_gate_mfma_wg: runtime block counts, the B operands of
 // all 16 block rows formed every step, a square-root pair decode and per-
 // element index arithmetic in the assembly -- 6.0k VALU per wave at 50x400.)
-constexpr int GT_NBMAX = 16;   // block counts k_gate_mfma_wt is built for: fp32 9.., fp64 8.. (M <= 84)
+constexpr int GT_NBMAX = 16;   // block counts k_gate_mfma_wt is built for: fp32 9.., fp64 8.. (M <= 84; launch_gate sends M <= 82)
 __host__ __device__ constexpr int gt_rows(int NB, int W, int WV) { return WV < NB ? (NB - 1 - WV) / W + 1 : 0; }
 __host__ __device__ constexpr int gt_off(int W, int WV, int i) { return i * (WV + 1) + W * i * (i - 1) / 2; }
 __host__ __device__ constexpr int gt_slots(int NB, int W, int WV) { return gt_off(W, WV, gt_rows(NB, W, WV)); }
@@ -1100,11 +1100,29 @@ bool gate_mfma_wt_fits(int maxM) { return maxM >= 1 && gm_nb(maxM) <= GT_NBMAX; 
 // four for nb <= 11 -- 1.07 / 1.62 / 1.55 against 1.16 / 2.21 / 1.91 ms -- but
 // spill at nb = 12; eight waves keep nb = 16 off scratch, 2.34 ms against 7.93,
 // and lose to four below it)
+// The block counts the switches below are instantiated for, per scalar size;
+// they must cover exactly what launch_gate (msckf_kernels.hip) sends here from
+// the class table and the block-count sub-lists of load_features.
+constexpr int wt_nb_lo(int ts) { return ts == 4 ? 9 : 8; }
+constexpr int nb_hi_one_wave(int ts) { return ts == 4 ? 8 : 7; }
+static_assert(gm_nb(GateClasses::LIM[GateClasses::NC - 3] + 1) == GateClasses::BIG_NB0,
+              "the first block-count sub-list starts right after the last one-wave class");
+static_assert(gm_nb(GateClasses::LIM[GateClasses::NC - 2]) == GateClasses::BIG_NB1,
+              "the block-count sub-lists end at the class limit");
+static_assert(GateClasses::BIG_NB1 == GT_NBMAX, "k_gate_mfma_wt is instantiated up to GT_NBMAX blocks");
+static_assert(GateClasses::LIM[GateClasses::NC - 2] <= GM_MAXM, "pair table too short for the multi-wave class");
+static_assert(GateClasses::BIG_NB0 == nb_hi_one_wave(4) && GateClasses::BIG_NB0 + 1 == wt_nb_lo(4),
+              "fp32: the 8-block sub-list runs one-wave, 9 .. 16 blocks k_gate_mfma_wt");
+static_assert(GateClasses::NC - 3 == nb_hi_one_wave(8) && GateClasses::BIG_NB0 == wt_nb_lo(8),
+              "fp64: classes of 1 .. 7 blocks run one-wave, 8 .. 16 blocks k_gate_mfma_wt");
+
 template <typename T>
-void launch_gate_mfma_wt(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
+bool launch_gate_mfma_wt(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
                          const int* list, int cnt, int nb, int maxM) {
-    if (cnt <= 0) return;
+    if (cnt <= 0) return true;
+    if (gm_nb(maxM) != nb) return false;   // the kernels assume exactly nb blocks
     if constexpr (sizeof(T) == 4) {
+        static_assert(wt_nb_lo(4) == 9 && GT_NBMAX == 16, "cases below: 9 .. 16");
         switch (nb) {
             case 9: launch_wt<T, 9, 2>(s, st, prm, fb, list, cnt, maxM); break;
             case 10: launch_wt<T, 10, 2>(s, st, prm, fb, list, cnt, maxM); break;
@@ -1114,12 +1132,13 @@ void launch_gate_mfma_wt(hipStream_t s, const DevState<T>& st, const Params<T>& 
             case 14: launch_wt<T, 14, 4>(s, st, prm, fb, list, cnt, maxM); break;
             case 15: launch_wt<T, 15, 4>(s, st, prm, fb, list, cnt, maxM); break;
             case 16: launch_wt<T, 16, 8>(s, st, prm, fb, list, cnt, maxM); break;
-            default: break;   // launch_gate sends only 9 <= nb <= GT_NBMAX here
+            default: return false;   // unrouted: launch_gate reports it, the update fails
         }
     } else {
         // fp64 (8 VGPRs per accumulator block): four waves up to 10 blocks, eight
         // beyond (50x400 fp64 gate 42.8 ms with eight waves for every count, 32.2
         // with four up to 10 blocks; profiles/r06/wt64/)
+        static_assert(wt_nb_lo(8) == 8 && GT_NBMAX == 16, "cases below: 8 .. 16");
         switch (nb) {
             case 8: launch_wt<T, 8, 4>(s, st, prm, fb, list, cnt, maxM); break;
             case 9: launch_wt<T, 9, 4>(s, st, prm, fb, list, cnt, maxM); break;
@@ -1130,19 +1149,21 @@ void launch_gate_mfma_wt(hipStream_t s, const DevState<T>& st, const Params<T>& 
             case 14: launch_wt<T, 14, 8>(s, st, prm, fb, list, cnt, maxM); break;
             case 15: launch_wt<T, 15, 8>(s, st, prm, fb, list, cnt, maxM); break;
             case 16: launch_wt<T, 16, 8>(s, st, prm, fb, list, cnt, maxM); break;
-            default: break;   // launch_gate sends only 8 <= nb <= GT_NBMAX here
+            default: return false;   // unrouted: launch_gate reports it, the update fails
         }
     }
+    return true;
 }
-template void launch_gate_mfma_wt<float>(hipStream_t, const DevState<float>&, const Params<float>&,
+template bool launch_gate_mfma_wt<float>(hipStream_t, const DevState<float>&, const Params<float>&,
                                          const FeatBatch<float>&, const int*, int, int, int);
-template void launch_gate_mfma_wt<double>(hipStream_t, const DevState<double>&, const Params<double>&,
+template bool launch_gate_mfma_wt<double>(hipStream_t, const DevState<double>&, const Params<double>&,
                                           const FeatBatch<double>&, const int*, int, int, int);
 
 template <typename T>
-void launch_gate_mfma(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
+bool launch_gate_mfma(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
                       const int* list, int cnt, int maxM) {
-    if (cnt <= 0) return;
+    if (cnt <= 0) return true;
+    static_assert(nb_hi_one_wave(4) == 8 && nb_hi_one_wave(8) == 7, "cases below: 1 .. 7, fp32 also 8");
     switch (gm_nb(maxM)) {
         case 1: launch_nb<T, 1>(s, st, prm, fb, list, cnt, maxM); break;
         case 2: launch_nb<T, 2>(s, st, prm, fb, list, cnt, maxM); break;
@@ -1151,10 +1172,15 @@ void launch_gate_mfma(hipStream_t s, const DevState<T>& st, const Params<T>& prm
         case 5: launch_nb<T, 5>(s, st, prm, fb, list, cnt, maxM); break;
         case 6: launch_nb<T, 6>(s, st, prm, fb, list, cnt, maxM); break;
         case 7: launch_nb<T, 7>(s, st, prm, fb, list, cnt, maxM); break;
-        default:
-            if constexpr (sizeof(T) == 4) launch_nb<T, 8>(s, st, prm, fb, list, cnt, maxM);
-            break;
+        case 8:
+            if constexpr (sizeof(T) == 4) {
+                launch_nb<T, 8>(s, st, prm, fb, list, cnt, maxM);
+                break;
+            }
+            return false;
+        default: return false;   // unrouted: launch_gate reports it, the update fails
     }
+    return true;
 }
 #ifdef MSCKF_GATE_PROBE
 extern "C" int msckf_gate_probe_read(unsigned long long* out) {   // [2][9][8], then reset
@@ -1164,9 +1190,9 @@ extern "C" int msckf_gate_probe_read(unsigned long long* out) {   // [2][9][8], 
 }
 #endif
 
-template void launch_gate_mfma<float>(hipStream_t, const DevState<float>&, const Params<float>&,
+template bool launch_gate_mfma<float>(hipStream_t, const DevState<float>&, const Params<float>&,
                                       const FeatBatch<float>&, const int*, int, int);
-template void launch_gate_mfma<double>(hipStream_t, const DevState<double>&, const Params<double>&,
+template bool launch_gate_mfma<double>(hipStream_t, const DevState<double>&, const Params<double>&,
                                        const FeatBatch<double>&, const int*, int, int);
 
 }  // namespace msckf

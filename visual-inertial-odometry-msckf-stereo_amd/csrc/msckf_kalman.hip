@@ -177,7 +177,7 @@ __global__ void __launch_bounds__(64 * NW) k_kal_c2(DevState<T> st, UpdWs<T> ws)
     constexpr int NT = 64 * NW;
     const int b = blockIdx.x;
     if (ws.info[4 * b] == 0 || ws.info[4 * b + 3] < 0) return;
-    const int C = 6 * st.ncams[b], nT = (C + 15) / 16, E = 22 + C, nE = (E + 15) / 16;
+    const int C = 6 * st.ncams[b], nT = (C + 15) / 16, E = 22 + C, nE = (E + 15) / 16;   // nE <= NW * CT (launch_kalman_chol)
     const int tid = threadIdx.x, lane = tid & 63, lc = lane & 15, lr = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ldt = ws.Cmax + 1, Cpw = ws.Cp, ldw = st.Dmax + 1;
@@ -1442,8 +1442,14 @@ void launch_kalman_chol(hipStream_t s, const DevState<T>& st, const Params<T>& p
             else if (c.nt == 256) launch_c1<T, 256, 6>(s, st, ws, lds);
             else launch_c1<T, 512, 4>(s, st, ws, lds);
         }
-        if (Cq <= 16 * 8) launch_c2<T, 7, 2, 8>(s, st, ws);
-        else launch_c2<T, 13, 1, 12>(s, st, ws);
+        // C2 solves the E = C + 22 extra rows ([Vc_i ; Lc ; c]) in 16-row tiles, one
+        // per (wave, CT slot): NW x CT tiles must cover them.  32 cams (C = 192,
+        // E = 214) need 14 tiles -- with 13 the last one (Lc rows 187 .. 191 and
+        // c, i.e. y and so all of dx) was never written and stage E read stale W.
+        const int nE = (Cmax + 22 + 15) / 16;
+        if (Cq <= 16 * 8) launch_c2<T, 7, 2, 8>(s, st, ws);          // C <= 128: nE <= 10
+        else if (nE <= 13) launch_c2<T, 13, 1, 12>(s, st, ws);       // C <= 186
+        else launch_c2<T, 14, 1, 12>(s, st, ws);                     // C = 192
     } else {
         launch_gchol<1, T>(s, st, ws);
     }

@@ -11,8 +11,8 @@
 //                                            jit_utils.py:137-167   -> k_augment
 //   Feature.initialize_position feature.py:167-295                  -> k_triangulate
 //   measurement_jacobian + feature_jacobian msckf.py:429-541        -> k_feature
-//   gating_test msckf.py:606-614                                    -> k_gate_wave /
-//                       k_gate_big / k_gate_lds / k_gate (fp32: msckf_gate_mfma.hip)
+//   gating_test msckf.py:606-614                                    -> msckf_gate_mfma.hip
+//                       (M <= 82), k_gate (M >= 83; k_gate_lds: not launched today)
 //   stacking + row cap msckf.py:661-682, 776-798                    -> k_select
 //   measurement_update QR msckf.py:549-556 (_fastQR)                -> k_info
 //   measurement_update S, K, dx, P msckf.py:559-604 (_fastSolve)    -> msckf_kalman.hip,
@@ -2969,18 +2969,19 @@ size_t gate_lds_bytes(int maxM) {
 }
 
 // Features are launched in size classes (by M, listed on the host at load
-// time): the register-tile wave kernel sized for the class, or for the
-// largest features the workgroup LDS kernel (global-memory kernel if even
-// that does not fit).
+// time): the MFMA kernel sized for the class (one wave, or a 2- to 8-wave
+// workgroup for 8 / 9 .. 16 blocks), or for the largest features (M >= 83)
+// the global-memory workgroup kernel k_gate.
 
 // The workgroup gating kernels (M > 82) read the compact factors (V, W,
 // Q^T r, tau, Hx, r) that k_feature otherwise skips.
 bool feature_needs_compact(int maxM) { return maxM > GateClasses::LIM[GateClasses::NC - 2]; }
 
 template <typename T>
-void launch_gate(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
-                 const GateClasses& gc) {
-    if (fb.nf == 0) return;
+int launch_gate(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
+                const GateClasses& gc) {
+    if (fb.nf == 0) return 0;
+    int unrouted = 0;   // block count of a list no MFMA kernel took (launch_gate_mfma / _wt returned false)
     lds_limit((const void*)k_gate_lds<T>, 160 * 1024);
     for (int c = 0; c < GateClasses::NC; ++c) {
         const int cnt = gc.off[c + 1] - gc.off[c];
@@ -2998,8 +2999,10 @@ void launch_gate(hipStream_t s, const DevState<T>& st, const Params<T>& prm, con
                 for (int j = 0; j + GateClasses::BIG_NB0 <= GateClasses::BIG_NB1; ++j) {
                     const int n = gc.big_off[j + 1] - gc.big_off[j], nb = j + GateClasses::BIG_NB0;
                     if (n == 0) continue;
-                    if (nb < wt_lo) launch_gate_mfma<T>(s, st, prm, fb, gc.list + gc.big_off[j], n, gc.big_maxM[j]);
-                    else launch_gate_mfma_wt<T>(s, st, prm, fb, gc.list + gc.big_off[j], n, nb, gc.big_maxM[j]);
+                    const bool ok = nb < wt_lo
+                        ? launch_gate_mfma<T>(s, st, prm, fb, gc.list + gc.big_off[j], n, gc.big_maxM[j])
+                        : launch_gate_mfma_wt<T>(s, st, prm, fb, gc.list + gc.big_off[j], n, nb, gc.big_maxM[j]);
+                    if (!ok) unrouted = nb;
                 }
                 continue;
             }
@@ -3007,21 +3010,25 @@ void launch_gate(hipStream_t s, const DevState<T>& st, const Params<T>& prm, con
         if constexpr (sizeof(T) == 8) {
             // fp64: 8 blocks and more (37 <= M <= 82) on k_gate_mfma_wt (round 6)
             if (c == GateClasses::NC - 3) {
-                launch_gate_mfma_wt<T>(s, st, prm, fb, list, cnt, c + 1, maxM);
+                if (!launch_gate_mfma_wt<T>(s, st, prm, fb, list, cnt, c + 1, maxM)) unrouted = c + 1;
                 continue;
             }
             if (c == GateClasses::NC - 2 && gate_mfma_wt_fits(maxM)) {
                 for (int j = 0; j + GateClasses::BIG_NB0 <= GateClasses::BIG_NB1; ++j) {
                     const int n = gc.big_off[j + 1] - gc.big_off[j], nb = j + GateClasses::BIG_NB0;
-                    if (n > 0) launch_gate_mfma_wt<T>(s, st, prm, fb, gc.list + gc.big_off[j], n, nb, gc.big_maxM[j]);
+                    if (n > 0 && !launch_gate_mfma_wt<T>(s, st, prm, fb, gc.list + gc.big_off[j], n, nb, gc.big_maxM[j]))
+                        unrouted = nb;
                 }
                 continue;
             }
         }
         if (c < GateClasses::NC - 2 && gate_mfma_fits(maxM, (int)sizeof(T))) {   // MFMA tiles (msckf_gate_mfma.hip)
-            launch_gate_mfma<T>(s, st, prm, fb, list, cnt, maxM);
+            if (!launch_gate_mfma<T>(s, st, prm, fb, list, cnt, maxM)) unrouted = c + 1;
             continue;
         }
+        // What is left is the last class (M >= 83), and gate_lds_bytes(83) is ~442 KB
+        // (fp32): it always takes k_gate.  The k_gate_lds branch is kept for a class
+        // table that would leave smaller tracks to it; no current route reaches it.
         const size_t lds = gate_lds_bytes<T>(maxM);
         const int threads = maxM <= 12 ? 64 : (maxM <= 20 ? 128 : 256);
         if (lds <= 160 * 1024)
@@ -3029,6 +3036,7 @@ void launch_gate(hipStream_t s, const DevState<T>& st, const Params<T>& prm, con
         else
             hipLaunchKernelGGL(k_gate<T>, dim3(cnt), dim3(256), 0, s, st, prm, fb, list);
     }
+    return unrouted;
 }
 
 template <typename T>
@@ -3119,7 +3127,7 @@ void launch_kalman(hipStream_t s, const DevState<T>& st, const Params<T>& prm, c
     template void launch_triangulate<T>(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&,  \
                                         const SegClasses&);                                                 \
     template void launch_feature<T>(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const SegClasses&); \
-    template void launch_gate<T>(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const GateClasses&); \
+    template int launch_gate<T>(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const GateClasses&); \
     template void launch_select<T>(hipStream_t, const DevState<T>&, const FeatBatch<T>&, const UpdWs<T>&, int); \
     template void launch_compress<T>(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const UpdWs<T>&, int, int); \
     template void launch_kalman<T>(hipStream_t, const DevState<T>&, const Params<T>&, const UpdWs<T>&, KernelTimer*);

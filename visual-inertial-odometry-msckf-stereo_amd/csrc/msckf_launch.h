@@ -117,7 +117,8 @@ void launch_feature(hipStream_t, const DevState<T>&, const Params<T>&, const Fea
 // one-wave MFMA kernel k_gate_mfma (fp64: up to 7 blocks; its 8-block class runs
 // k_gate_mfma_wt); class NC-2 (40 < M <= 82) the multi-wave MFMA kernel
 // k_gate_mfma_wt by block count (fp32: its 8-block sub-list, M = 41, one-wave);
-// the last class the workgroup LDS kernel (or its global-memory variant).
+// the last class (M >= 83) the global-memory workgroup kernel k_gate (the LDS
+// variant k_gate_lds would need ~442 KB already at M = 83, gate_lds_bytes).
 struct GateClasses {
     // block boundaries: ceil((3M + 4) / 16) = 1..8 for M <= 4, 9, 14, 20, 25, 30, 36, 40
     static constexpr int NC = 10;
@@ -132,19 +133,27 @@ struct GateClasses {
     int big_off[BIG_NB1 - BIG_NB0 + 2] = {};
     int big_maxM[BIG_NB1 - BIG_NB0 + 1] = {};
 };
+// Returns 0, or the 16-row block count of a non-empty feature list that no
+// gating kernel is instantiated for (those features then keep the previous
+// batch's gamma / accept: the caller must fail the update).
 template <typename T>
-void launch_gate(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const GateClasses&);
-// Gating on MFMA tiles (msckf_gate_mfma.hip), one wavefront per feature, M <= 40
+int launch_gate(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const GateClasses&);
+// Gating on MFMA tiles (msckf_gate_mfma.hip), one wavefront per feature:
+// fp32 up to 8 blocks (M <= 41), fp64 up to 7 (M <= 36)
 // (fp32: v_mfma_f32_16x16x4_f32, fp64: v_mfma_f64_16x16x4_f64).
+// false: no kernel for this block count, nothing launched.
 bool gate_mfma_fits(int maxM, int scalar_bytes);
 template <typename T>
-void launch_gate_mfma(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const int* list, int cnt,
+bool launch_gate_mfma(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const int* list, int cnt,
                       int maxM);
-// fp32 gating of the tracks of exactly nb 16-row blocks (9 <= nb <= 16, 41 < M <= 84)
-// on a 2- / 4- / 8-wave workgroup per feature (k_gate_mfma_wt)
+// Gating of the tracks of exactly nb 16-row blocks on a 2- / 4- / 8-wave
+// workgroup per feature (k_gate_mfma_wt): fp32 9 <= nb <= 16 (42 <= M <= 82),
+// fp64 8 <= nb <= 16 (37 <= M <= 82; the kernels themselves hold up to M = 84,
+// the class limit GateClasses::LIM sends M >= 83 to k_gate).
+// false: no kernel for this block count, nothing launched.
 bool gate_mfma_wt_fits(int maxM);
 template <typename T>
-void launch_gate_mfma_wt(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const int* list,
+bool launch_gate_mfma_wt(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const int* list,
                          int cnt, int nb, int maxM);
 template <typename T>
 void launch_select(hipStream_t, const DevState<T>&, const FeatBatch<T>&, const UpdWs<T>&, int row_cap);
