@@ -463,9 +463,9 @@ def test_gate_fp32_gamma_vs_oracle(N, F, B, cap):
     single- and multi-pass Y staging); N = 82: also the multi-wave workgroup
     kernel k_gate_mfma_wt for 41 < M <= 82 (9 .. 16 blocks on two, four or
     eight waves, Y staged in passes; M = 41, 8 blocks, still one wave); N = 100:
-    also the class beyond 82 observations (the global-memory workgroup kernel
-    k_gate, fed by k_feature's compact QR factors: its LDS variant k_gate_lds
-    would need ~442 KB at M = 83 and is never launched), up to the longest
+    also the list beyond 82 observations (the global-memory workgroup kernel
+    k_gate, fed by k_feature's compact QR factors and the (4M)^2 scratch that
+    only such a batch allocates), up to the longest
     track the chi2 table gates.  Tolerance:
     fp32 with the saddle point's conditioning (~1e3) -- median relative error
     <= 1e-4, 99th percentile <= 1e-3; decisions: at most 1 % of the features

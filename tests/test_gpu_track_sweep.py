@@ -4,13 +4,14 @@ window sizes N = 128 (the ABI's maximum: D = 789, cam masks up to bit 127, the
 global-memory Kalman stages, k_info_big, every gate route) and N = 32 (the
 largest register-tile Kalman window), fp64 and fp32, against the CPU oracle.
 
-Gate routes (GateClasses::LIM, the block-count sub-lists of load_features,
-launch_gate; nb = ceil((3M + 4) / 16) 16-row blocks) and the kernel of each:
+Gate routes (csrc/msckf_gate_routes.h: one feature list per block count nb =
+ceil((3M + 4) / 16) up to M = 82, one beyond) and the kernel of each; the
+results are grouped with 41 apart, in the device's list of 37..40:
 
     M            nb      fp32                       fp64
     2..4 .. 31..36  1..7   k_gate_mfma<nb> (one wave) k_gate_mfma<nb> (one wave, fp64 MFMA)
     37..40       8       k_gate_mfma<8>             k_gate_mfma_wt<8, 4>
-    41           8       k_gate_mfma<8> (sub-list)  k_gate_mfma_wt<8, 4> (sub-list)
+    41           8       k_gate_mfma<8> (same list) k_gate_mfma_wt<8, 4> (same list)
     42..46       9       k_gate_mfma_wt<9, 2>       k_gate_mfma_wt<9, 4>
     47..52       10      k_gate_mfma_wt<10, 2>      k_gate_mfma_wt<10, 4>
     53..57       11      k_gate_mfma_wt<11, 2>      k_gate_mfma_wt<11, 8>

@@ -3,11 +3,19 @@ conditions the GPU sweep relies on, for the pinned seeds, and the comparator's
 self-test -- check_sweep must pass on the reference itself and raise on every
 subtly wrong result it is there to catch, so the GPU tests would fail on a
 subtly wrong kernel without one being needed to show it."""
+import os
+import shutil
+import subprocess
+
 import numpy as np
 import pytest
 
 import track_sweep as ts
 from track_sweep import ROUTE_BOUNDS, SWEEP_SEEDS, cached_sweep, check_sweep, got_from_ref, route_of, scrambled
+
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                    "visual-inertial-odometry-msckf-stereo_amd", "csrc")
 
 
 @pytest.fixture(scope="module", params=sorted(SWEEP_SEEDS))
@@ -18,9 +26,9 @@ def pair(request):
 
 
 def test_route_table_matches_block_counts():
-    """ROUTE_BOUNDS restates the device's routing: GateClasses::LIM =
-    {4, 9, 14, 20, 25, 30, 36, 40, 82}, block count ceil((3M + 4) / 16) = 8 .. 16
-    inside 41..82 with 41 alone in the first sub-list, M >= 83 last."""
+    """ROUTE_BOUNDS groups the tracks by block count ceil((3M + 4) / 16) = 1 .. 16
+    up to M = 82, with 41 kept apart from the other 8-block tracks 37..40 (the
+    device lists them together, csrc/msckf_gate_routes.h), M >= 83 last."""
     assert len(ROUTE_BOUNDS) == 8 + 9 + 1
     assert [hi for _, hi in ROUTE_BOUNDS[:9]] == [4, 9, 14, 20, 25, 30, 36, 40, 41]
     assert ROUTE_BOUNDS[16] == (79, 82) and ROUTE_BOUNDS[17] == (83, 128)
@@ -29,6 +37,71 @@ def test_route_table_matches_block_counts():
         assert lo <= M <= hi, M
     for r, (lo, hi) in enumerate(ROUTE_BOUNDS[8:17]):
         assert {-(-(3 * M + 4) // 16) for M in range(lo, hi + 1)} == {8 + r}
+
+
+_PRINT_ROUTES = r"""
+#include <cstdio>
+#include "msckf_gate_routes.h"
+using namespace msckf;
+static const char* name(GateKind k) {
+    return k == GateKind::OneWave ? "one_wave" : (k == GateKind::Workgroup ? "workgroup" : "global");
+}
+int main() {
+    static_assert(GATE_NLIST == 17, "lists");
+    for (int M = 1; M <= 128; ++M) {
+        const int l = gate_list_of(M);
+        const GateRoute r4 = gate_route(l, 4), r8 = gate_route(l, 8);
+        std::printf("%d %d %d %s %d %s %d\n", M, l, gate_nb(M), name(r4.kind), r4.waves, name(r8.kind), r8.waves);
+    }
+    return 0;
+}
+"""
+
+
+def _host_compiler():
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    for cxx in ("c++", "g++", os.path.join(rocm, "llvm", "bin", "clang++"), os.path.join(rocm, "bin", "amdclang++")):
+        path = shutil.which(cxx)
+        if path:
+            return path
+    return None
+
+
+def test_route_table_matches_device_header(tmp_path):
+    """The device's own table (csrc/msckf_gate_routes.h, built here with the host
+    compiler alone) against route_of / ROUTE_BOUNDS and the routes the project
+    measured: fp32 one wave up to 8 blocks, 2 waves for 9..11, 4 for 12..15, 8 for
+    16; fp64 one wave up to 7 blocks, 4 waves for 8..10, 8 for 11..16; M >= 83 on
+    the global-memory kernel.  ROUTE_BOUNDS is finer than the device's lists in
+    one place only: 37..40 and 41 share the 8-block list."""
+    cxx = _host_compiler()
+    assert cxx is not None, "no host C++ compiler (c++, g++ or the ROCm clang++) to build the route table with"
+    src, exe = tmp_path / "print_routes.cpp", tmp_path / "print_routes"
+    src.write_text(_PRINT_ROUTES)
+    subprocess.run([cxx, "-std=c++17", "-I", CSRC, str(src), "-o", str(exe)], check=True)
+    rows = [ln.split() for ln in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines()]
+    assert [int(r[0]) for r in rows] == list(range(1, 129))
+    dev = {int(r[0]): (int(r[1]), (r[3], int(r[4])), (r[5], int(r[6]))) for r in rows}
+    for r in rows:   # lists by block count up to 82, one list beyond
+        M, lst, nb = int(r[0]), int(r[1]), int(r[2])
+        assert nb == -(-(3 * M + 4) // 16) and lst == (nb - 1 if M <= 82 else 16), r
+    groups = {}
+    for M in range(2, 129):
+        groups.setdefault(dev[M][0], set()).add(route_of(M))
+    # route_of is constant on every device list, but for the 8-block list (41 apart) ...
+    assert {lst: sorted(g) for lst, g in groups.items() if len(g) > 1} == {7: [7, 8]}
+    # ... and a list never ends inside a group of ROUTE_BOUNDS
+    for lo, hi in ROUTE_BOUNDS:
+        assert len({dev[M][0] for M in range(lo, hi + 1)}) == 1, (lo, hi)
+    assert sorted(groups) == list(range(17))
+    fp32 = {nb: ("one_wave", 1) if nb <= 8 else ("workgroup", 2 if nb <= 11 else 4 if nb <= 15 else 8) for nb in range(1, 17)}
+    fp64 = {nb: ("one_wave", 1) if nb <= 7 else ("workgroup", 4 if nb <= 10 else 8) for nb in range(1, 17)}
+    for M in range(1, 129):
+        lst, r4, r8 = dev[M]
+        if lst == 16:
+            assert r4[0] == "global" and r8[0] == "global", M
+        else:
+            assert r4 == fp32[lst + 1] and r8 == fp64[lst + 1], (M, r4, r8)
 
 
 def test_builder_conditions(pair):

@@ -4,10 +4,11 @@ device run against it.  Pure numpy + the oracle (no GPU import): the builder
 and the comparator are themselves tested on the CPU (test_track_sweep_ref.py)
 and used by the GPU parity sweep (test_gpu_track_sweep.py).
 
-The per-feature kernels are chosen by M in several places of csrc/ (SegClasses,
-GateClasses::LIM, the block-count sub-lists of load_features, the switches of
-launch_gate_mfma / launch_gate_mfma_wt, launch_gate).  ``route_of`` restates the
-gate routing so results can be grouped by the kernel that produced them.
+The per-feature kernels are chosen by M: SegClasses for triangulation and the
+Jacobians, and for the gate the one table of csrc/msckf_gate_routes.h (a feature
+list per block count, M >= 83 last).  ``route_of`` groups results by the gate
+kernel that produced them; it is finer than the device's lists in one place (41
+apart from 37..40), and test_track_sweep_ref.py compares it with the header.
 """
 import copy
 import functools
@@ -22,10 +23,11 @@ from msckf_amd.geometry import to_rotation
 
 # Gate routes, by index into ROUTE_BOUNDS.  A track of M <= 82 observations
 # fills nb = ceil((3M + 4) / 16) 16-row blocks:
-#   0 .. 7   the one-wave classes of 1 .. 8 blocks: M <= 4, 5..9, 10..14, 15..20,
+#   0 .. 7   the lists of 1 .. 8 blocks up to M = 40: M <= 4, 5..9, 10..14, 15..20,
 #            21..25, 26..30, 31..36, 37..40
-#   8 .. 16  the block-count sub-lists of 41..82 (8 .. 16 blocks): 41 | 42..46 |
-#            47..52 | 53..57 | 58..62 | 63..68 | 69..73 | 74..78 | 79..82
+#   8        M = 41, the last track of 8 blocks (on the device in the list of 37..40)
+#   9 .. 16  the lists of 9 .. 16 blocks: 42..46 | 47..52 | 53..57 | 58..62 |
+#            63..68 | 69..73 | 74..78 | 79..82
 #   17       M >= 83
 ROUTE_BOUNDS = [(2, 4), (5, 9), (10, 14), (15, 20), (21, 25), (26, 30), (31, 36), (37, 40),
                 (41, 41), (42, 46), (47, 52), (53, 57), (58, 62), (63, 68), (69, 73), (74, 78), (79, 82),

@@ -442,44 +442,23 @@ int load_features(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filt
     HIPC(c->obs_ht.ensure((nobs * OBS_HTS + OBS_HTS) * ts));
     HIPC(c->fqr.ensure((nf + 1) * FQR_STRIDE * sizeof(double)));
     HIPC(c->tau.ensure((nf * 4 + 4) * ts));
-    {   // the (4M)^2 global gating scratch is only needed by features too large
-        // for the LDS gating path (M > ~50 in fp32, > ~35 in fp64)
-        const size_t n4 = 4 * (size_t)maxM;
-        const size_t lds = ((n4 * (n4 + 1) + 1) & ~(size_t)1) * ts + (12 * n4 + 4) * ts + (maxM + 4) * sizeof(int);
-        if (lds > 160 * 1024) HIPC(c->ysq.ensure((size_t)(ysq[nf] + 16) * ts));
-    }
-    // gating size classes, largest first inside the list (long blocks start early)
+    // the (4M)^2 global gating scratch is k_gate's alone (M > GATE_TILE_MAXM)
+    if (feature_needs_compact(maxM)) HIPC(c->ysq.ensure((size_t)(ysq[nf] + 16) * ts));
+    // the gating lists (msckf_gate_routes.h), ascending feature index inside a list
     std::vector<int> gflat;
     GateClasses gc;
     {
-        std::vector<std::vector<int>> cls(GateClasses::NC);
+        std::vector<int> lists[GATE_NLIST];
         for (int f = 0; f < nf; ++f) {
-            const int M = obs_off[f + 1] - obs_off[f];
-            int k = 0;
-            while (M > GateClasses::LIM[k]) ++k;
-            cls[k].push_back(f);
-            gc.maxM[k] = std::max(gc.maxM[k], M);
+            const int M = obs_off[f + 1] - obs_off[f], l = gate_list_of(M);
+            lists[l].push_back(f);
+            gc.maxM[l] = std::max(gc.maxM[l], M);
         }
-        for (int k = 0; k < GateClasses::NC; ++k) {
-            gc.off[k] = (int)gflat.size();
-            if (k == GateClasses::NC - 2) {   // large tracks by block count (the fp32 launches split them)
-                constexpr int NS = GateClasses::BIG_NB1 - GateClasses::BIG_NB0 + 1;
-                std::vector<int> sub[NS];
-                for (int f : cls[k]) {
-                    const int M = obs_off[f + 1] - obs_off[f], nb = (3 * M + 4 + 15) / 16 - GateClasses::BIG_NB0;
-                    sub[nb].push_back(f);
-                    gc.big_maxM[nb] = std::max(gc.big_maxM[nb], M);
-                }
-                for (int j = 0; j < NS; ++j) {
-                    gc.big_off[j] = (int)gflat.size();
-                    gflat.insert(gflat.end(), sub[j].begin(), sub[j].end());
-                }
-                gc.big_off[NS] = (int)gflat.size();
-                continue;
-            }
-            gflat.insert(gflat.end(), cls[k].begin(), cls[k].end());
+        for (int l = 0; l < GATE_NLIST; ++l) {
+            gc.off[l] = (int)gflat.size();
+            gflat.insert(gflat.end(), lists[l].begin(), lists[l].end());
         }
-        gc.off[GateClasses::NC] = (int)gflat.size();
+        gc.off[GATE_NLIST] = (int)gflat.size();
     }
     // segment classes of the per-feature kernels (M <= S)
     std::vector<int> sflat;
@@ -666,7 +645,7 @@ int unpack_results(msckf_ctx* c, const DownList& d, const ResultsRead& r, uint8_
     if (gamma_out && nf) to_double<T>(gamma_out, base + (c->gamma - c->valid), nf);
     if (p_w_out && nf) to_double<T>(p_w_out, base + (c->p_w - c->valid), (size_t)nf * 3);
     if (c->gate_unrouted)   // gamma / accept of those features are the previous batch's
-        FAIL(-4, "no gating kernel for tracks of %d 16-row blocks (%d-byte scalars): the class table and the "
+        FAIL(-4, "no gating kernel for tracks of %d 16-row blocks (%d-byte scalars): the route table and the "
                  "instantiated kernels disagree", c->gate_unrouted, c->scalar);
     const int* info = reinterpret_cast<const int*>(d.at(c, r.o_info));
     int bad = -1;

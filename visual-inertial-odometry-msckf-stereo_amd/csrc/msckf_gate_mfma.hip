@@ -56,7 +56,7 @@ using D2 = double __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float gfma(float a, float b, float c) { return fmaf(a, b, c); }
 __device__ __forceinline__ double gfma(double a, double b, double c) { return fma(a, b, c); }
 
-__host__ __device__ constexpr int gm_nb(int M) { return (3 * M + 4 + 15) / 16; }
+// (the 16-row block count gate_nb(M): msckf_gate_routes.h)
 __host__ __device__ constexpr int gm_head(int Mmax) { return (22 * Mmax + 3) & ~3; }   // Ht rows + [r~ | r_n]
 // The Y pairs are staged as a dense lower-triangular matrix, row q holding
 // columns 0..q plus two padding slots (a diagonal pair block writes its upper
@@ -71,18 +71,19 @@ __host__ __device__ constexpr int gm_dense(int alo, int ahi) {
 // Y staging / panel + the junk panel (written up to 128 NB + 12 RS + 23 by the
 // lanes that own no pivot column)
 __host__ __device__ constexpr int gm_area(int Mmax, int capf, int RS = 1) {
-    return capf > 128 * gm_nb(Mmax) + 16 * RS + 16 ? ((capf + 15) & ~3) : 128 * gm_nb(Mmax) + 16 * RS + 16;
+    return capf > 128 * gate_nb(Mmax) + 16 * RS + 16 ? ((capf + 15) & ~3) : 128 * gate_nb(Mmax) + 16 * RS + 16;
 }
 // the B rows [H_f~^T ; r~^T] (4 x 16 NB, zero beyond 3M) and a zero row (16 NB)
 // the padding rows of the assembly read
-__host__ __device__ constexpr int gm_brows(int Mmax) { return 80 * gm_nb(Mmax); }
+__host__ __device__ constexpr int gm_brows(int Mmax) { return 80 * gate_nb(Mmax); }
 // elements of T per wave (the two int offset tables take T-sized slots)
 __host__ __device__ constexpr int gm_wave_floats(int Mmax, int capf, int RS = 1) {
     return gm_head(Mmax) + gm_area(Mmax, capf, RS) + gm_brows(Mmax) + 2 * ((Mmax + 3) & ~3);
 }
 // Pair k = a (a + 1) / 2 + b (b <= a) of the Y phase: a | b << 8 | (stage offset
 // of element (3a, 3b)) << 16, one table load instead of a square-root decode.
-constexpr int GM_MAXM = 84;   // gm_nb(84) = 16: the fp32 large-track class (k_gate_mfma_wt)
+constexpr int GM_MAXM = 84;   // every M of 16 blocks (gate_nb(84) = 16); the route table stops at 82
+static_assert(GATE_TILE_MAXM <= GM_MAXM, "pair table too short for the longest track on the tile kernels");
 struct GmPairTab {
     unsigned v[GM_MAXM * (GM_MAXM + 1) / 2];
     constexpr GmPairTab() : v() {
@@ -94,17 +95,6 @@ struct GmPairTab {
 static_assert(gm_rowoff(3 * GM_MAXM) < 65536, "pair table offsets are 16-bit");
 __device__ constexpr GmPairTab g_gm_pairs{};
 __host__ __device__ constexpr int bidx(int rb, int cb) { return rb * (rb + 1) / 2 + cb; }
-// The one-wave size classes (GateClasses::LIM) are exactly the 16-row block
-// counts: every feature of class c fills nb = c + 1 blocks, so the kernel of a
-// class runs with a compile-time block count.
-constexpr bool gm_class_exact() {
-    for (int c = 0; c < GateClasses::NC - 2; ++c) {
-        const int lo = c == 0 ? 1 : GateClasses::LIM[c - 1] + 1;
-        if (gm_nb(lo) != c + 1 || gm_nb(GateClasses::LIM[c]) != c + 1) return false;
-    }
-    return true;
-}
-static_assert(gm_class_exact(), "gating size classes must match the MFMA block counts");
 
 // Blocked LDL^T of the assembled lower block triangle, 4 pivots per step (see
 // the file header).  acc holds blocks (RB, CB), CB <= RB < NB, in the C layout
@@ -375,7 +365,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gm_wav
     const int b = __builtin_amdgcn_readfirstlane(fb.feat_filter[f]);
     const int o0 = __builtin_amdgcn_readfirstlane(fb.obs_off[f]);
     const int M = __builtin_amdgcn_readfirstlane(fb.obs_off[f + 1]) - o0, M3 = 3 * M;
-    constexpr int nb = NB;                 // the size class: gm_nb(M) == NB (gm_class_exact)
+    constexpr int nb = NB;                 // the feature list: gate_nb(M) == NB (gate_list_of)
     T* ht = reinterpret_cast<T*>(smem_raw) + (size_t)wv * gm_wave_floats(Mmax, capf, RS);
     T* rt = ht + 18 * Mmax;                // [Mmax][4]: r~ (3), r_n
     T* area = ht + gm_head(Mmax);
@@ -392,7 +382,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gm_wav
     // rt [M][4].
     int* coff = slot + ((Mmax + 3) & ~3);
     {
-        constexpr int MCAP = (16 * NB - 4) / 3;   // the class's largest M (gm_class_exact)
+        constexpr int MCAP = (16 * NB - 4) / 3;   // the list's largest M (gate_list_of)
         constexpr int NCH = (12 * MCAP + 63) / 64;
         static_assert(OBS_HT == 0 && OBS_RT == 18 && OBS_HTS == 24, "record layout");
         const V2* src = reinterpret_cast<const V2*>(fb.obs_ht + (size_t)o0 * OBS_HTS);
@@ -642,7 +632,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gm_wav
 // ---------------------------------------------------------------------------
 // Large tracks, round 6: k_gate_mfma_wt<NB, W> -- the one-wave kernel's
 // elimination spread over a W-wave workgroup per feature of exactly NB blocks
-// (the host lists the 40 < M <= 82 class by block count, GateClasses::big_off).
+// (the host lists the tracks by block count, gate_list_of).
 // Wave WV owns block rows RB = WV + W i: every wave runs its own compile-time
 // specialised body (gt_body<NB, W, WV>), so its accumulator slots, block
 // indices and trailing-update ranges are constants -- no per-block branches,
@@ -657,7 +647,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gm_wav
 // (Replaces round 5's k_gate_mfma_wg: runtime block counts, the B operands of
 // all 16 block rows formed every step, a square-root pair decode and per-
 // element index arithmetic in the assembly -- 6.0k VALU per wave at 50x400.)
-constexpr int GT_NBMAX = 16;   // block counts k_gate_mfma_wt is built for: fp32 9.., fp64 8.. (M <= 84; launch_gate sends M <= 82)
 __host__ __device__ constexpr int gt_rows(int NB, int W, int WV) { return WV < NB ? (NB - 1 - WV) / W + 1 : 0; }
 __host__ __device__ constexpr int gt_off(int W, int WV, int i) { return i * (WV + 1) + W * i * (i - 1) / 2; }
 __host__ __device__ constexpr int gt_slots(int NB, int W, int WV) { return gt_off(W, WV, gt_rows(NB, W, WV)); }
@@ -1061,7 +1050,7 @@ void launch_nb(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const
     constexpr int RS = GM<T>::RS;
     const int full = gm_dense(0, Mmax - 1);
     int cmin = 0;   // one block row per pass at least
-    for (int R = 0; R < gm_nb(Mmax); ++R) {
+    for (int R = 0; R < gate_nb(Mmax); ++R) {
         const int alo = 16 * R / 3, ahi = (16 * R + 15) / 3 < Mmax - 1 ? (16 * R + 15) / 3 : Mmax - 1;
         cmin = gm_dense(alo, ahi) > cmin ? gm_dense(alo, ahi) : cmin;
     }
@@ -1081,107 +1070,44 @@ void launch_nb(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const
     else launch_cfg<T, NB, false>(s, st, prm, fb, list, cnt, Mmax, capf, wpb, wpb * pw);
 }
 
+// The kernel of the list of NB-block tracks, as the route table says (one-wave
+// or W waves per feature; the wave counts are written there and nowhere else).
+// (round 5: fp64 31 <= M <= 36 off k_gate_wave onto the one-wave kernel at one
+// wave per SIMD, the accumulators in AGPRs, 50x400 fp64 gate 60.4 -> 56.0 ms,
+// profiles/r05/ab_gate_fp64_nb7/.  Round 5 also ran the same elimination on
+// fp64 MFMA for 41 <= M <= 62, three block rows per wave: 256 VGPRs + 192 AGPRs,
+// one workgroup per CU, parity green but the 50x400 fp64 gate 55.9 -> 61.5 ms
+// against k_gate_big's register tiles at two workgroups per CU --
+// profiles/r05/exp_gate_mfma_wg64/)
+template <typename T, int NB>
+void launch_route(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb, const int* list,
+                  int cnt, int Mmax) {
+    constexpr GateRoute r = gate_route(NB - 1, (int)sizeof(T));
+    if constexpr (r.kind == GateKind::OneWave) launch_nb<T, NB>(s, st, prm, fb, list, cnt, Mmax);
+    else launch_wt<T, NB, r.waves>(s, st, prm, fb, list, cnt, Mmax);
+}
 
 }  // namespace
 
-// fp64 up to NB = 7 (M <= 36) at one wave per SIMD, the accumulators in AGPRs
-// (round 5: 31 <= M <= 36 off k_gate_wave, 50x400 fp64 gate 60.4 -> 56.0 ms,
-// profiles/r05/ab_gate_fp64_nb7/); NB = 8 would spill
-bool gate_mfma_fits(int maxM, int ts) { return maxM >= 1 && gm_nb(maxM) <= (ts == 8 ? 7 : 8); }
-bool gate_mfma_wt_fits(int maxM) { return maxM >= 1 && gm_nb(maxM) <= GT_NBMAX; }
-
-// (round 5 ran the same elimination on fp64 MFMA for 41 <= M <= 62, three
-// block rows per wave: 256 VGPRs + 192 AGPRs, one workgroup per CU, parity
-// green but the 50x400 fp64 gate 55.9 -> 61.5 ms against k_gate_big's register
-// tiles at two workgroups per CU -- profiles/r05/exp_gate_mfma_wg64/)
-
-// tracks of exactly nb blocks (fp32 9 <= nb <= 16, fp64 8 <= nb <= 16): waves per
-// feature by block count (round 6, profiles/r06/wt/: at 80x1000 two waves beat
-// four for nb <= 11 -- 1.07 / 1.62 / 1.55 against 1.16 / 2.21 / 1.91 ms -- but
-// spill at nb = 12; eight waves keep nb = 16 off scratch, 2.34 ms against 7.93,
-// and lose to four below it)
-// The block counts the switches below are instantiated for, per scalar size;
-// they must cover exactly what launch_gate (msckf_kernels.hip) sends here from
-// the class table and the block-count sub-lists of load_features.
-constexpr int wt_nb_lo(int ts) { return ts == 4 ? 9 : 8; }
-constexpr int nb_hi_one_wave(int ts) { return ts == 4 ? 8 : 7; }
-static_assert(gm_nb(GateClasses::LIM[GateClasses::NC - 3] + 1) == GateClasses::BIG_NB0,
-              "the first block-count sub-list starts right after the last one-wave class");
-static_assert(gm_nb(GateClasses::LIM[GateClasses::NC - 2]) == GateClasses::BIG_NB1,
-              "the block-count sub-lists end at the class limit");
-static_assert(GateClasses::BIG_NB1 == GT_NBMAX, "k_gate_mfma_wt is instantiated up to GT_NBMAX blocks");
-static_assert(GateClasses::LIM[GateClasses::NC - 2] <= GM_MAXM, "pair table too short for the multi-wave class");
-static_assert(GateClasses::BIG_NB0 == nb_hi_one_wave(4) && GateClasses::BIG_NB0 + 1 == wt_nb_lo(4),
-              "fp32: the 8-block sub-list runs one-wave, 9 .. 16 blocks k_gate_mfma_wt");
-static_assert(GateClasses::NC - 3 == nb_hi_one_wave(8) && GateClasses::BIG_NB0 == wt_nb_lo(8),
-              "fp64: classes of 1 .. 7 blocks run one-wave, 8 .. 16 blocks k_gate_mfma_wt");
-
 template <typename T>
-bool launch_gate_mfma_wt(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
-                         const int* list, int cnt, int nb, int maxM) {
+bool launch_gate_tiles(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
+                       const int* list, int cnt, int nb, int maxM) {
     if (cnt <= 0) return true;
-    if (gm_nb(maxM) != nb) return false;   // the kernels assume exactly nb blocks
-    if constexpr (sizeof(T) == 4) {
-        static_assert(wt_nb_lo(4) == 9 && GT_NBMAX == 16, "cases below: 9 .. 16");
-        switch (nb) {
-            case 9: launch_wt<T, 9, 2>(s, st, prm, fb, list, cnt, maxM); break;
-            case 10: launch_wt<T, 10, 2>(s, st, prm, fb, list, cnt, maxM); break;
-            case 11: launch_wt<T, 11, 2>(s, st, prm, fb, list, cnt, maxM); break;
-            case 12: launch_wt<T, 12, 4>(s, st, prm, fb, list, cnt, maxM); break;
-            case 13: launch_wt<T, 13, 4>(s, st, prm, fb, list, cnt, maxM); break;
-            case 14: launch_wt<T, 14, 4>(s, st, prm, fb, list, cnt, maxM); break;
-            case 15: launch_wt<T, 15, 4>(s, st, prm, fb, list, cnt, maxM); break;
-            case 16: launch_wt<T, 16, 8>(s, st, prm, fb, list, cnt, maxM); break;
-            default: return false;   // unrouted: launch_gate reports it, the update fails
-        }
-    } else {
-        // fp64 (8 VGPRs per accumulator block): four waves up to 10 blocks, eight
-        // beyond (50x400 fp64 gate 42.8 ms with eight waves for every count, 32.2
-        // with four up to 10 blocks; profiles/r06/wt64/)
-        static_assert(wt_nb_lo(8) == 8 && GT_NBMAX == 16, "cases below: 8 .. 16");
-        switch (nb) {
-            case 8: launch_wt<T, 8, 4>(s, st, prm, fb, list, cnt, maxM); break;
-            case 9: launch_wt<T, 9, 4>(s, st, prm, fb, list, cnt, maxM); break;
-            case 10: launch_wt<T, 10, 4>(s, st, prm, fb, list, cnt, maxM); break;
-            case 11: launch_wt<T, 11, 8>(s, st, prm, fb, list, cnt, maxM); break;
-            case 12: launch_wt<T, 12, 8>(s, st, prm, fb, list, cnt, maxM); break;
-            case 13: launch_wt<T, 13, 8>(s, st, prm, fb, list, cnt, maxM); break;
-            case 14: launch_wt<T, 14, 8>(s, st, prm, fb, list, cnt, maxM); break;
-            case 15: launch_wt<T, 15, 8>(s, st, prm, fb, list, cnt, maxM); break;
-            case 16: launch_wt<T, 16, 8>(s, st, prm, fb, list, cnt, maxM); break;
-            default: return false;   // unrouted: launch_gate reports it, the update fails
-        }
-    }
-    return true;
-}
-template bool launch_gate_mfma_wt<float>(hipStream_t, const DevState<float>&, const Params<float>&,
-                                         const FeatBatch<float>&, const int*, int, int, int);
-template bool launch_gate_mfma_wt<double>(hipStream_t, const DevState<double>&, const Params<double>&,
-                                          const FeatBatch<double>&, const int*, int, int, int);
-
-template <typename T>
-bool launch_gate_mfma(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
-                      const int* list, int cnt, int maxM) {
-    if (cnt <= 0) return true;
-    static_assert(nb_hi_one_wave(4) == 8 && nb_hi_one_wave(8) == 7, "cases below: 1 .. 7, fp32 also 8");
-    switch (gm_nb(maxM)) {
-        case 1: launch_nb<T, 1>(s, st, prm, fb, list, cnt, maxM); break;
-        case 2: launch_nb<T, 2>(s, st, prm, fb, list, cnt, maxM); break;
-        case 3: launch_nb<T, 3>(s, st, prm, fb, list, cnt, maxM); break;
-        case 4: launch_nb<T, 4>(s, st, prm, fb, list, cnt, maxM); break;
-        case 5: launch_nb<T, 5>(s, st, prm, fb, list, cnt, maxM); break;
-        case 6: launch_nb<T, 6>(s, st, prm, fb, list, cnt, maxM); break;
-        case 7: launch_nb<T, 7>(s, st, prm, fb, list, cnt, maxM); break;
-        case 8:
-            if constexpr (sizeof(T) == 4) {
-                launch_nb<T, 8>(s, st, prm, fb, list, cnt, maxM);
-                break;
-            }
-            return false;
+    if (gate_nb(maxM) != nb) return false;   // the kernels assume exactly nb blocks
+    switch (nb) {
+#define GATE_CASE(NB) case NB: launch_route<T, NB>(s, st, prm, fb, list, cnt, maxM); return true;
+        GATE_CASE(1) GATE_CASE(2) GATE_CASE(3) GATE_CASE(4) GATE_CASE(5) GATE_CASE(6) GATE_CASE(7) GATE_CASE(8)
+        GATE_CASE(9) GATE_CASE(10) GATE_CASE(11) GATE_CASE(12) GATE_CASE(13) GATE_CASE(14) GATE_CASE(15) GATE_CASE(16)
+#undef GATE_CASE
         default: return false;   // unrouted: launch_gate reports it, the update fails
     }
-    return true;
 }
+static_assert(GATE_NB_MAX == 16, "cases above: 1 .. 16");
+template bool launch_gate_tiles<float>(hipStream_t, const DevState<float>&, const Params<float>&,
+                                       const FeatBatch<float>&, const int*, int, int, int);
+template bool launch_gate_tiles<double>(hipStream_t, const DevState<double>&, const Params<double>&,
+                                        const FeatBatch<double>&, const int*, int, int, int);
+
 #ifdef MSCKF_GATE_PROBE
 extern "C" int msckf_gate_probe_read(unsigned long long* out) {   // [2][9][8], then reset
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gate_probe), sizeof(g_gate_probe)) != hipSuccess) return -1;
@@ -1189,10 +1115,4 @@ extern "C" int msckf_gate_probe_read(unsigned long long* out) {   // [2][9][8], 
     return hipMemcpyToSymbol(HIP_SYMBOL(g_gate_probe), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
 }
 #endif
-
-template bool launch_gate_mfma<float>(hipStream_t, const DevState<float>&, const Params<float>&,
-                                      const FeatBatch<float>&, const int*, int, int);
-template bool launch_gate_mfma<double>(hipStream_t, const DevState<double>&, const Params<double>&,
-                                       const FeatBatch<double>&, const int*, int, int);
-
 }  // namespace msckf

@@ -12,7 +12,7 @@
 //   Feature.initialize_position feature.py:167-295                  -> k_triangulate
 //   measurement_jacobian + feature_jacobian msckf.py:429-541        -> k_feature
 //   gating_test msckf.py:606-614                                    -> msckf_gate_mfma.hip
-//                       (M <= 82), k_gate (M >= 83; k_gate_lds: not launched today)
+//                       (M <= 82), k_gate (M >= 83); routes: msckf_gate_routes.h
 //   stacking + row cap msckf.py:661-682, 776-798                    -> k_select
 //   measurement_update QR msckf.py:549-556 (_fastQR)                -> k_info
 //   measurement_update S, K, dx, P msckf.py:559-604 (_fastSolve)    -> msckf_kalman.hip,
@@ -1476,127 +1476,6 @@ __global__ void __launch_bounds__(256) k_gate(DevState<T> st, Params<T> prm, Fea
     }
 }
 
-// Fast path of k_gate with Y / S resident in LDS (ld = 4M+1, odd: conflict-free
-// row and column sweeps) and gamma from an LDL^T elimination with the residual
-// carried along as an extra column: gamma = sum_j r~_j^2 / d_j.  One barrier
-// per pivot; the column being eliminated is read-only during its step.
-template <typename T>
-__global__ void __launch_bounds__(256) k_gate_lds(DevState<T> st, Params<T> prm, FeatBatch<T> fb,
-                                                  const int* __restrict__ flist) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int f = flist[blockIdx.x];
-    const int tid = threadIdx.x;
-    if (!fb.valid[f]) {
-        if (tid == 0) { fb.gamma[f] = T(NAN); fb.accept[f] = 0; }
-        return;
-    }
-    const int b = fb.feat_filter[f];
-    const int o0 = fb.obs_off[f], M = fb.obs_off[f + 1] - o0;
-    const int n4 = 4 * M, ld = n4 + 1;
-    const T* P = st.P + (size_t)b * st.Dmax * st.Dmax;
-    const int ldp = st.Dmax;
-    const T* ws = fb.obs_ws + (size_t)o0 * OBS_WS;
-    T* Y = reinterpret_cast<T*>(smem_raw);                       // [n4][n4+1]
-    T* s_hx = Y + (((size_t)n4 * ld + 1) & ~(size_t)1);           // [n4][6]
-    T* s_v = s_hx + 6 * n4;                                       // [3][n4]
-    T* s_r = s_v + 3 * n4;                                        // [n4]
-    T* s_p = s_r + n4;                                            // [n4]
-    T* s_w = s_p + n4;                                            // [n4]
-    T* s_sc = s_w + n4;                                           // [4]
-    int* s_slot = reinterpret_cast<int*>(s_sc + 4);               // [M]
-    for (int e = tid; e < n4 * 6; e += blockDim.x) s_hx[e] = ws[(size_t)(e / 24) * OBS_WS + OBS_HX + e % 24];
-    for (int row = tid; row < n4; row += blockDim.x) {
-        const T* w = ws + (size_t)(row >> 2) * OBS_WS;
-        for (int j = 0; j < 3; ++j) s_v[j * n4 + row] = w[OBS_V + 3 * (row & 3) + j];
-        s_r[row] = w[OBS_QR + (row & 3)];
-    }
-    for (int i = tid; i < M; i += blockDim.x) s_slot[i] = fb.obs_cam[o0 + i];
-    __syncthreads();
-    // 1. Y = Hx P Hx^T, 4x4 blocks
-    const int npairs = M * (M + 1) / 2;
-    for (int pidx = tid; pidx < npairs; pidx += blockDim.x) {
-        int i = 0, rem = pidx;
-        while (rem >= M - i) { rem -= M - i; ++i; }
-        const int l = i + rem;
-        const T* Hi = s_hx + 24 * i;
-        const T* Hl = s_hx + 24 * l;
-        const T* Pb = P + (size_t)(21 + 6 * s_slot[i]) * ldp + 21 + 6 * s_slot[l];
-        T Pl[36];
-        for (int k = 0; k < 6; ++k)
-            for (int c = 0; c < 6; ++c) Pl[6 * k + c] = Pb[(size_t)k * ldp + c];
-        T T1[24];
-        for (int a = 0; a < 4; ++a)
-            for (int c = 0; c < 6; ++c) {
-                T sacc = 0;
-                for (int k = 0; k < 6; ++k) sacc += Hi[6 * a + k] * Pl[6 * k + c];
-                T1[6 * a + c] = sacc;
-            }
-        for (int a = 0; a < 4; ++a)
-            for (int c = 0; c < 4; ++c) {
-                T sacc = 0;
-                for (int k = 0; k < 6; ++k) sacc += T1[6 * a + k] * Hl[6 * c + k];
-                Y[(4 * i + a) * ld + 4 * l + c] = sacc;
-                Y[(4 * l + c) * ld + 4 * i + a] = sacc;
-            }
-    }
-    __syncthreads();
-    // 2. Y <- H_j Y H_j for the three reflectors
-    for (int j = 0; j < 3; ++j) {
-        const T tj = fb.tau[4 * f + j];
-        if (tj == T(0)) continue;
-        const T* v = s_v + j * n4;
-        for (int a = tid; a < n4; a += blockDim.x) {
-            T sacc = 0;
-            for (int c = j; c < n4; ++c) sacc += Y[a * ld + c] * v[c];
-            s_p[a] = sacc;
-        }
-        __syncthreads();
-        if (tid < 64) {
-            T sacc = 0;
-            for (int a = tid; a < n4; a += 64) sacc += v[a] * s_p[a];
-            sacc = wave_sum(sacc);
-            if (tid == 0) s_sc[0] = sacc;
-        }
-        __syncthreads();
-        const T K = tj * tj * s_sc[0] / T(2);
-        for (int a = tid; a < n4; a += blockDim.x) s_w[a] = tj * s_p[a] - K * v[a];
-        __syncthreads();
-        for (int a = (tid >> 4); a < n4; a += (int)(blockDim.x >> 4)) {
-            const T va = v[a], wa = s_w[a];
-            for (int c = (tid & 15); c < n4; c += 16) Y[a * ld + c] -= va * s_w[c] + wa * v[c];
-        }
-        __syncthreads();
-    }
-    // 3. S = Y[3:,3:] + s2 I ; LDL^T with the residual as an extra column
-    const int k = n4 - 3;
-    T* S = Y + 3 * ld + 3;
-    T* r = s_r + 3;
-    for (int a = tid; a < k; a += blockDim.x) S[a * ld + a] += prm.sigma2;
-    __syncthreads();
-    T gam = 0;
-    bool fail = false;
-    for (int j = 0; j < k; ++j) {
-        const T d = S[j * ld + j];
-        if (!(d > 0)) { fail = true; break; }   // uniform: every thread reads the same d
-        const T inv = T(1) / d;
-        const T rj = r[j];
-        if (tid == 0) gam += rj * rj * inv;
-        // (blockDim/16) x 16 thread grid over the trailing lower triangle (no divisions)
-        const int rstep = blockDim.x >> 4;
-        for (int i = j + 1 + (tid >> 4); i < k; i += rstep) {
-            const T ai = S[i * ld + j] * inv;
-            for (int l = j + 1 + (tid & 15); l <= i; l += 16) S[i * ld + l] -= ai * S[l * ld + j];
-            if ((tid & 15) == 0) r[i] -= ai * rj;
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        if (fail) gam = T(INFINITY);
-        fb.gamma[f] = gam;
-        fb.accept[f] = (gam < fb.chi2[f]) ? 1 : 0;
-    }
-}
-
 // Gating mathematics (M <= 82).  With Y = Hx P Hx^T + s2 I (4M x 4M, PD) and N an orthonormal basis
 // of the left nullspace of H_f, the reference's S = N^T Y N (msckf.py:607-609
 // on H0 = N^T Hx) satisfies the oblique-projection identity
@@ -2913,128 +2792,65 @@ void launch_cov_diag(hipStream_t s, const DevState<T>& st, int nfilt, const int*
     hipLaunchKernelGGL(k_cov_diag<T>, dim3((nfilt * n + 255) / 256), dim3(256), 0, s, st, filters, nfilt, i0, n,
                        out);
 }
+// The non-empty classes of the S-lanes-per-feature kernels, in turn, as
+// launch(<lanes per feature>, <observations per lane>, grid, list, cnt) with the
+// first two compile-time (S = 128: a whole wavefront, 2 observations per lane).
+template <int... C, typename F>
+void for_seg_classes(std::integer_sequence<int, C...>, const SegClasses& sc, F&& launch) {
+    ([&] {
+        constexpr int S = SegClasses::S[C], lanes = S < 64 ? S : 64;
+        const int cnt = sc.off[C + 1] - sc.off[C];
+        if (cnt == 0) return;
+        const int waves = (cnt * lanes + 63) / 64, blocks = (waves + 3) / 4;
+        launch(std::integral_constant<int, lanes>{}, std::integral_constant<int, S / lanes>{}, dim3(blocks),
+               sc.list + sc.off[C], cnt);
+    }(), ...);
+}
+template <typename F>
+void for_seg_classes(const SegClasses& sc, F&& launch) {
+    for_seg_classes(std::make_integer_sequence<int, SegClasses::NC>{}, sc, launch);
+}
 template <typename T>
 void launch_triangulate(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
                         const SegClasses& sc) {
     if (fb.nf == 0) return;
-    for (int c = 0; c < SegClasses::NC; ++c) {   // the k_feature classes: S lanes, 2 views per lane
-        const int cnt = sc.off[c + 1] - sc.off[c];
-        if (cnt == 0) continue;
-        const int* list = sc.list + sc.off[c];
-        const int lanes = SegClasses::S[c] < 64 ? SegClasses::S[c] : 64;
-        const int waves = (cnt * lanes + 63) / 64, blocks = (waves + 3) / 4;
-        switch (SegClasses::S[c]) {
-            case 8: hipLaunchKernelGGL((k_triangulate<T, 8, 2>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-            case 16: hipLaunchKernelGGL((k_triangulate<T, 16, 2>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-            case 32: hipLaunchKernelGGL((k_triangulate<T, 32, 2>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-            case 64: hipLaunchKernelGGL((k_triangulate<T, 64, 2>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-            default: hipLaunchKernelGGL((k_triangulate<T, 64, 4>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-        }
-    }
+    for_seg_classes(sc, [&](auto lanes, auto per, dim3 blocks, const int* list, int cnt) {   // 2 views per observation
+        hipLaunchKernelGGL((k_triangulate<T, decltype(lanes)::value, 2 * decltype(per)::value>), blocks, dim3(256), 0, s,
+                           st, prm, fb, list, cnt);
+    });
 }
 template <typename T>
 void launch_feature(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
                     const SegClasses& sc) {
     if (fb.nf == 0) return;
-    for (int c = 0; c < SegClasses::NC; ++c) {
-        const int cnt = sc.off[c + 1] - sc.off[c];
-        if (cnt == 0) continue;
-        const int* list = sc.list + sc.off[c];
-        const int lanes = SegClasses::S[c] < 64 ? SegClasses::S[c] : 64;   // S = 128: 2 observations per lane
-        const int waves = (cnt * lanes + 63) / 64, blocks = (waves + 3) / 4;
-        if (fb.gram) {
-            switch (SegClasses::S[c]) {
-                case 8: hipLaunchKernelGGL((k_feature<T, 8, 1, true>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-                case 16: hipLaunchKernelGGL((k_feature<T, 16, 1, true>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-                case 32: hipLaunchKernelGGL((k_feature<T, 32, 1, true>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-                case 64: hipLaunchKernelGGL((k_feature<T, 64, 1, true>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-                default: hipLaunchKernelGGL((k_feature<T, 64, 2, true>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-            }
-        } else {
-            switch (SegClasses::S[c]) {
-                case 8: hipLaunchKernelGGL((k_feature<T, 8, 1, false>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-                case 16: hipLaunchKernelGGL((k_feature<T, 16, 1, false>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-                case 32: hipLaunchKernelGGL((k_feature<T, 32, 1, false>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-                case 64: hipLaunchKernelGGL((k_feature<T, 64, 1, false>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-                default: hipLaunchKernelGGL((k_feature<T, 64, 2, false>), dim3(blocks), dim3(256), 0, s, st, prm, fb, list, cnt); break;
-            }
-        }
-    }
-}
-template <typename T>
-size_t gate_lds_bytes(int maxM) {
-    const size_t n4 = 4 * maxM;
-    return ((n4 * (n4 + 1) + 1) & ~(size_t)1) * sizeof(T) + (6 * n4 + 3 * n4 + 3 * n4 + 4) * sizeof(T) +
-           (maxM + 4) * sizeof(int);
+    auto go = [&](auto gram) {
+        for_seg_classes(sc, [&](auto lanes, auto per, dim3 blocks, const int* list, int cnt) {
+            hipLaunchKernelGGL((k_feature<T, decltype(lanes)::value, decltype(per)::value, decltype(gram)::value>),
+                               blocks, dim3(256), 0, s, st, prm, fb, list, cnt);
+        });
+    };
+    if (fb.gram) go(std::true_type{});
+    else go(std::false_type{});
 }
 
-// Features are launched in size classes (by M, listed on the host at load
-// time): the MFMA kernel sized for the class (one wave, or a 2- to 8-wave
-// workgroup for 8 / 9 .. 16 blocks), or for the largest features (M >= 83)
-// the global-memory workgroup kernel k_gate.
-
-// The workgroup gating kernels (M > 82) read the compact factors (V, W,
-// Q^T r, tau, Hx, r) that k_feature otherwise skips.
-bool feature_needs_compact(int maxM) { return maxM > GateClasses::LIM[GateClasses::NC - 2]; }
-
+// Features are launched by the lists of msckf_gate_routes.h (filled on the host
+// at load time): the MFMA tile kernel of the list's block count (one wave, or a
+// 2- to 8-wave workgroup per feature), or for the largest features (M >= 83) the
+// global-memory workgroup kernel k_gate, which reads the compact factors (V, W,
+// Q^T r, tau, Hx, r) that k_feature otherwise skips (feature_needs_compact).
 template <typename T>
 int launch_gate(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
                 const GateClasses& gc) {
     if (fb.nf == 0) return 0;
-    int unrouted = 0;   // block count of a list no MFMA kernel took (launch_gate_mfma / _wt returned false)
-    lds_limit((const void*)k_gate_lds<T>, 160 * 1024);
-    for (int c = 0; c < GateClasses::NC; ++c) {
-        const int cnt = gc.off[c + 1] - gc.off[c];
+    int unrouted = 0;   // block count of a list no tile kernel took (launch_gate_tiles returned false)
+    for (int l = 0; l < GATE_NLIST; ++l) {
+        const int cnt = gc.off[l + 1] - gc.off[l];
         if (cnt == 0) continue;
-        const int maxM = gc.maxM[c];
-        const int* list = gc.list + gc.off[c];
-        if constexpr (sizeof(T) == 4) {
-            // fp32 large tracks (40 < M <= 82): by their block-count sub-lists, 8
-            // blocks (M = 41) on the one-wave kernel, 9 .. 16 on k_gate_mfma_wt, a 2- to
-            // 8-wave workgroup per feature (round 6; the one-wave classes of 7 and 8
-            // blocks on k_gate_mfma_wt<7 / 8, 2> measured slower: 50x400 gate 12.05 ->
-            // 12.39 ms, profiles/r06/wt2/)
-            constexpr int wt_lo = 9;
-            if (c == GateClasses::NC - 2 && gate_mfma_wt_fits(maxM)) {
-                for (int j = 0; j + GateClasses::BIG_NB0 <= GateClasses::BIG_NB1; ++j) {
-                    const int n = gc.big_off[j + 1] - gc.big_off[j], nb = j + GateClasses::BIG_NB0;
-                    if (n == 0) continue;
-                    const bool ok = nb < wt_lo
-                        ? launch_gate_mfma<T>(s, st, prm, fb, gc.list + gc.big_off[j], n, gc.big_maxM[j])
-                        : launch_gate_mfma_wt<T>(s, st, prm, fb, gc.list + gc.big_off[j], n, nb, gc.big_maxM[j]);
-                    if (!ok) unrouted = nb;
-                }
-                continue;
-            }
-        }
-        if constexpr (sizeof(T) == 8) {
-            // fp64: 8 blocks and more (37 <= M <= 82) on k_gate_mfma_wt (round 6)
-            if (c == GateClasses::NC - 3) {
-                if (!launch_gate_mfma_wt<T>(s, st, prm, fb, list, cnt, c + 1, maxM)) unrouted = c + 1;
-                continue;
-            }
-            if (c == GateClasses::NC - 2 && gate_mfma_wt_fits(maxM)) {
-                for (int j = 0; j + GateClasses::BIG_NB0 <= GateClasses::BIG_NB1; ++j) {
-                    const int n = gc.big_off[j + 1] - gc.big_off[j], nb = j + GateClasses::BIG_NB0;
-                    if (n > 0 && !launch_gate_mfma_wt<T>(s, st, prm, fb, gc.list + gc.big_off[j], n, nb, gc.big_maxM[j]))
-                        unrouted = nb;
-                }
-                continue;
-            }
-        }
-        if (c < GateClasses::NC - 2 && gate_mfma_fits(maxM, (int)sizeof(T))) {   // MFMA tiles (msckf_gate_mfma.hip)
-            if (!launch_gate_mfma<T>(s, st, prm, fb, list, cnt, maxM)) unrouted = c + 1;
-            continue;
-        }
-        // What is left is the last class (M >= 83), and gate_lds_bytes(83) is ~442 KB
-        // (fp32): it always takes k_gate.  The k_gate_lds branch is kept for a class
-        // table that would leave smaller tracks to it; no current route reaches it.
-        const size_t lds = gate_lds_bytes<T>(maxM);
-        const int threads = maxM <= 12 ? 64 : (maxM <= 20 ? 128 : 256);
-        if (lds <= 160 * 1024)
-            hipLaunchKernelGGL(k_gate_lds<T>, dim3(cnt), dim3(threads), lds, s, st, prm, fb, list);
-        else
+        const int* list = gc.list + gc.off[l];
+        if (l == GATE_LIST_GLOBAL)
             hipLaunchKernelGGL(k_gate<T>, dim3(cnt), dim3(256), 0, s, st, prm, fb, list);
+        else if (!launch_gate_tiles<T>(s, st, prm, fb, list, cnt, l + 1, gc.maxM[l]))
+            unrouted = l + 1;
     }
     return unrouted;
 }

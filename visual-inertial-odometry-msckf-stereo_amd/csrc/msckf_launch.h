@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "msckf_common.h"
+#include "msckf_gate_routes.h"
 
 namespace msckf {
 
@@ -111,50 +112,28 @@ template <typename T>
 void launch_triangulate(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const SegClasses&);
 template <typename T>
 void launch_feature(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const SegClasses&);
-// Feature index lists per gating size class (device pointer + host offsets).
-// Gating size classes by observation count M.  Class c < NC-2 holds the
-// tracks of exactly c + 1 16-row blocks (ceil((3M + 4) / 16)) and runs the
-// one-wave MFMA kernel k_gate_mfma (fp64: up to 7 blocks; its 8-block class runs
-// k_gate_mfma_wt); class NC-2 (40 < M <= 82) the multi-wave MFMA kernel
-// k_gate_mfma_wt by block count (fp32: its 8-block sub-list, M = 41, one-wave);
-// the last class (M >= 83) the global-memory workgroup kernel k_gate (the LDS
-// variant k_gate_lds would need ~442 KB already at M = 83, gate_lds_bytes).
+// Feature index lists per gating route (device pointer + host offsets), one
+// level: list l = gate_list_of(M) of msckf_gate_routes.h holds the tracks of
+// exactly l + 1 16-row blocks (M <= 82), the last list M >= 83; gate_route
+// names the kernel of each list.  Features keep ascending index inside a list.
 struct GateClasses {
-    // block boundaries: ceil((3M + 4) / 16) = 1..8 for M <= 4, 9, 14, 20, 25, 30, 36, 40
-    static constexpr int NC = 10;
-    static constexpr int LIM[NC] = {4, 9, 14, 20, 25, 30, 36, 40, 82, 1 << 30};
     const int* list = nullptr;
-    int off[NC + 1] = {};
-    int maxM[NC] = {};
-    // class NC - 2 (40 < M <= 82) ordered by the 16-row block count nb =
-    // ceil((3M + 4) / 16) = BIG_NB0 .. BIG_NB1: features of block count nb at
-    // list[big_off[nb - BIG_NB0] .. big_off[nb - BIG_NB0 + 1])
-    static constexpr int BIG_NB0 = 8, BIG_NB1 = 16;
-    int big_off[BIG_NB1 - BIG_NB0 + 2] = {};
-    int big_maxM[BIG_NB1 - BIG_NB0 + 1] = {};
+    int off[GATE_NLIST + 1] = {};
+    int maxM[GATE_NLIST] = {};
 };
 // Returns 0, or the 16-row block count of a non-empty feature list that no
 // gating kernel is instantiated for (those features then keep the previous
 // batch's gamma / accept: the caller must fail the update).
 template <typename T>
 int launch_gate(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const GateClasses&);
-// Gating on MFMA tiles (msckf_gate_mfma.hip), one wavefront per feature:
-// fp32 up to 8 blocks (M <= 41), fp64 up to 7 (M <= 36)
-// (fp32: v_mfma_f32_16x16x4_f32, fp64: v_mfma_f64_16x16x4_f64).
+// Gating on MFMA tiles (msckf_gate_mfma.hip; fp32: v_mfma_f32_16x16x4_f32, fp64:
+// v_mfma_f64_16x16x4_f64) of one tile list, the tracks of exactly nb blocks:
+// k_gate_mfma<nb>, one wavefront per feature, or k_gate_mfma_wt<nb, W>, a W-wave
+// workgroup per feature, as gate_route(nb - 1, sizeof(T)) says.
 // false: no kernel for this block count, nothing launched.
-bool gate_mfma_fits(int maxM, int scalar_bytes);
 template <typename T>
-bool launch_gate_mfma(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const int* list, int cnt,
-                      int maxM);
-// Gating of the tracks of exactly nb 16-row blocks on a 2- / 4- / 8-wave
-// workgroup per feature (k_gate_mfma_wt): fp32 9 <= nb <= 16 (42 <= M <= 82),
-// fp64 8 <= nb <= 16 (37 <= M <= 82; the kernels themselves hold up to M = 84,
-// the class limit GateClasses::LIM sends M >= 83 to k_gate).
-// false: no kernel for this block count, nothing launched.
-bool gate_mfma_wt_fits(int maxM);
-template <typename T>
-bool launch_gate_mfma_wt(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const int* list,
-                         int cnt, int nb, int maxM);
+bool launch_gate_tiles(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const int* list,
+                       int cnt, int nb, int maxM);
 template <typename T>
 void launch_select(hipStream_t, const DevState<T>&, const FeatBatch<T>&, const UpdWs<T>&, int row_cap);
 template <typename T>
@@ -163,8 +142,9 @@ void launch_compress(hipStream_t, const DevState<T>&, const Params<T>&, const Fe
 // The fused information assembly (no per-observation Gram records) runs when
 // the window has <= 32 cams and its per-filter tables fit the LDS.
 bool info_fused_fits(int Nmax, int maxnf);
-// The workgroup gating kernels (M > 82) need k_feature's compact QR factors
-bool feature_needs_compact(int maxM);
+// The global-memory gating kernel k_gate (M > GATE_TILE_MAXM) needs k_feature's
+// compact QR factors and the (4M)^2 scratch FeatBatch::ysq
+inline bool feature_needs_compact(int maxM) { return maxM > GATE_TILE_MAXM; }
 bool kalman_chol_supported(int Cmax);
 size_t kalman_global_ws_doubles(int Cmax);
 // Stage A of the register-tile windows (kalman_chol_supported) reads only P and
