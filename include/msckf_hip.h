@@ -189,12 +189,17 @@ int msckf_snapshot(msckf_ctx_t* ctx);
 int msckf_restore(msckf_ctx_t* ctx);
 int msckf_sync(msckf_ctx_t* ctx);
 
-/* Per-kernel device time (HIP events on the context stream), accumulated
- * while profiling is on.  names: NUL-separated list written to names_out. */
+/* Per-kernel device time (HIP events on the launch stream), accumulated
+ * while profiling is on.  names: NUL-separated list written to names_out.
+ * A batch of 1024 filters or more runs msckf_restore and the update chain as
+ * two half-batches ("lanes") on streams of their own; while every stage is
+ * profiled it runs as one, so a stage's time is its uncontended time. */
 int msckf_set_profiling(msckf_ctx_t* ctx, int on);
 /* Profiling of ONE timer stage (e.g. "gate"): every other stage records no
  * events, so the timed stream carries two event packets per step instead of
- * two per stage.  stage == NULL turns profiling off. */
+ * two per stage.  stage == NULL turns profiling off.  The lanes stay: each
+ * records its own interval and msckf_kernel_times returns their sum, an upper
+ * bound on the stage's exclusive device time (the lanes overlap). */
 int msckf_set_profiling_stage(msckf_ctx_t* ctx, const char* stage);
 int msckf_kernel_times(msckf_ctx_t* ctx, int max_k, double* ms_total, int32_t* launches,
                        char* names_out, int names_cap);

@@ -14,6 +14,7 @@
 #include "../../include/msckf_hip.h"
 #include "msckf_common.h"
 #include "msckf_launch.h"
+#include "msckf_subbatch.h"
 
 using namespace msckf;
 
@@ -148,11 +149,29 @@ struct PinnedBuf {
 
 struct msckf_ctx {
     int device = 0, scalar = 8, B = 1, Nmax = 0, Dmax = 0, Cmax = 0;
+    // Streams.  A context of two or more filters can run its update chain as two
+    // lanes (msckf_subbatch.h): lane 0 = filters [0, B / 2) on `stream`, lane 1 =
+    // the rest on `stream1`, so that one lane's kernels run in the CUs the other
+    // lane's stage is draining.  Three streams in all, created once with the
+    // context (a process has four hardware queues).  Everything but msckf_restore
+    // and the update chain runs on `stream` alone.
     hipStream_t stream = nullptr;
-    // Kalman stage A reads only P: it runs on `side` under triangulation, the
-    // Jacobians and gating (fork / join events on the main stream)
+    // Kalman stage A reads only P: as one lane it runs on `side` under
+    // triangulation, the Jacobians and gating (fork / join events on the main
+    // stream).  Under a split the other lane is the co-running work and stage A
+    // stays inline on each lane's own stream (measured faster than a side stream
+    // per lane), so lane 1 has no side stream.
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipStream_t stream1 = nullptr;   // lane 1 (B >= 2 only)
+    int last_lanes = 1;              // lanes of the last msckf_restore / update chain (msckf_debug_lanes)
+    // Ordering between `stream` and lane 1: ev_head is recorded on `stream` and
+    // waited on by stream1 before lane 1's first use after a single-stream call;
+    // ev_tail is recorded on stream1 after lane 1's last enqueued work and waited
+    // on by `stream` before the next single-stream call (join_lanes).
+    // lane1_busy: stream1 holds work `stream` has not been ordered after.
+    hipEvent_t ev_head = nullptr, ev_tail = nullptr;
+    bool lane1_busy = false;
     msckf_config_t cfg{};
     std::vector<int> h_ncams;
     // state
@@ -179,12 +198,13 @@ struct msckf_ctx {
     DBuf<int> row_off;
     GateClasses gc;
     SegClasses sc;
+    int gc_cut[GATE_NLIST] = {}, sc_cut[SegClasses::NC] = {};   // where lane 1 begins in each list (subbatch_cut_lists)
     DBuf<unsigned char> obs_ws, obs_ht, obs_g, fqr, tau, ysq;
     bool gram = true;   // k_feature writes the Gram records (record-reading assembly)
     // misc scratch
     DBuf<unsigned char> scratch;
     DBuf<int> iscratch;
-    KernelTimer timer;
+    KernelTimer timer, timer1;   // per lane; msckf_kernel_times adds them
     const char* last_async = "none";   // last asynchronous entry point (HIPSYNC's message)
     bool has_snapshot = false;
     PinnedRing up;      // upload staging
@@ -212,36 +232,41 @@ Params<T> make_params(const msckf_ctx* c) {
     return p;
 }
 
+// The state arrays of the filters [b0, b0 + nb) (nb < 0: all from b0): every
+// per-filter array is indexed b * stride, so a lane's view is the base pointers
+// moved by b0 strides and B = the lane's count.
 template <typename T>
-DevState<T> dev_state(msckf_ctx* c) {
+DevState<T> dev_state(msckf_ctx* c, int b0 = 0, int nb = -1) {
     DevState<T> s;
-    s.P = reinterpret_cast<T*>(c->P.p);
-    s.imu = reinterpret_cast<T*>(c->imu.p);
-    s.cams = reinterpret_cast<T*>(c->cams.p);
-    s.ncams = c->ncams.p;
-    s.B = c->B;
+    s.P = reinterpret_cast<T*>(c->P.p) + (size_t)b0 * c->Dmax * c->Dmax;
+    s.imu = reinterpret_cast<T*>(c->imu.p) + (size_t)b0 * IMU_STRIDE;
+    s.cams = reinterpret_cast<T*>(c->cams.p) + (size_t)b0 * c->Nmax * CAM_STRIDE;
+    s.ncams = c->ncams.p + b0;
+    s.B = nb < 0 ? c->B - b0 : nb;
     s.Nmax = c->Nmax;
     s.Dmax = c->Dmax;
     return s;
 }
 
+// The update workspace of the filters from b0 on (strides as in do_create).
 template <typename T>
-UpdWs<T> upd_ws(msckf_ctx* c) {
+UpdWs<T> upd_ws(msckf_ctx* c, int b0 = 0) {
     UpdWs<T> w;
-    w.Hthin = reinterpret_cast<KT*>(c->Hthin.p);
-    w.dx = reinterpret_cast<KT*>(c->dx.p);
-    w.info = c->info.p;
+    const size_t b = (size_t)b0, C = (size_t)c->Cmax;
     w.Cmax = c->Cmax;
     w.Cp = (c->Cmax + 15) & ~15;   // leading dim of Lc / Vi / W (MFMA path pads C to 16)
-    w.Lc = reinterpret_cast<KT*>(c->Lc.p);
-    w.afail = c->afail.p;
-    w.Vi = reinterpret_cast<KT*>(c->Vi.p);
-    w.Sii = reinterpret_cast<KT*>(c->Sii.p);
-    w.G = reinterpret_cast<KT*>(c->G.p);
-    w.Tm = reinterpret_cast<KT*>(c->Tm.p);
-    w.W = reinterpret_cast<KT*>(c->W.p);
-    w.Wk = reinterpret_cast<KT*>(c->Wk.p);
     w.wk_stride = kalman_global_ws_doubles(c->Cmax);
+    w.Hthin = reinterpret_cast<KT*>(c->Hthin.p) + b * C * (C + 1);
+    w.dx = reinterpret_cast<KT*>(c->dx.p) + b * (c->Dmax + C);
+    w.info = c->info.p + 4 * b;
+    w.Lc = reinterpret_cast<KT*>(c->Lc.p) + b * w.Cp * w.Cp;
+    w.afail = c->afail.p + b;
+    w.Vi = reinterpret_cast<KT*>(c->Vi.p) + b * 24 * w.Cp;
+    w.Sii = reinterpret_cast<KT*>(c->Sii.p) + b * 24 * 24;
+    w.G = reinterpret_cast<KT*>(c->G.p) + b * C * (C + 1);
+    w.Tm = reinterpret_cast<KT*>(c->Tm.p) + b * C * (C + 1);
+    w.W = reinterpret_cast<KT*>(c->W.p) + b * (c->Dmax + 1) * w.Cp;
+    w.Wk = c->Wk.p ? reinterpret_cast<KT*>(c->Wk.p) + b * w.wk_stride : nullptr;
     w.s2 = (double)(T)c->cfg.observation_noise;
     return w;
 }
@@ -371,7 +396,12 @@ struct DownList {
                 }
         }
         e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) c->timer.collect();
+        if (e == hipSuccess) {
+            c->timer.collect();
+            // lane 1's events are complete only once c->stream was ordered after it (join_lanes);
+            // msckf_sync and msckf_kernel_times collect whatever this skips
+            if (!c->lane1_busy) c->timer1.collect();
+        }
         return e;
     }
     const unsigned char* at(const msckf_ctx* c, size_t off) const { return c->down.p + off; }
@@ -471,6 +501,13 @@ int load_features(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filt
         }
     }
     sc.off[SegClasses::NC] = (int)sflat.size();
+    for (int l = 0; l < GATE_NLIST; ++l) gc.beg[l] = gc.off[l], gc.end[l] = gc.off[l + 1];
+    for (int k = 0; k < SegClasses::NC; ++k) sc.beg[k] = sc.off[k], sc.end[k] = sc.off[k + 1];
+    if (c->stream1) {   // where each list passes from lane 0's features to lane 1's (msckf_subbatch.h)
+        const int f_cut = h_off[subbatch_first_filter(c->B, 1, 2)];
+        subbatch_cut_lists(gflat.data(), gc.off, GATE_NLIST, f_cut, c->gc_cut);
+        subbatch_cut_lists(sflat.data(), sc.off, SegClasses::NC, f_cut, c->sc_cut);
+    }
     // the batch arena: inputs, then the result span [valid | p_w | include | gamma | accept]
     size_t total = 0;
     auto seg = [&](size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; };
@@ -555,19 +592,87 @@ int load_features(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filt
     return 0;
 }
 
+// ---- lanes (msckf_subbatch.h) ----
+// How many lanes the next msckf_restore / update chain runs as.  A context of
+// one filter has no second lane and decides nothing per call.  Profiling of
+// every stage (msckf_set_profiling) runs one lane, so that a stage's time stays
+// its uncontended time; one-stage profiling keeps the split.  MSCKF_SUBBATCH=1|2
+// (environment, read per call like MSCKF_KALMAN_CHOL) forces either mode.
+int active_lanes(const msckf_ctx* c) {
+    if (!c->stream1) return 1;
+    if (c->timer.on && c->timer.only.empty()) return 1;
+    const char* e = getenv("MSCKF_SUBBATCH");
+    return subbatch_lanes(c->B, e && (e[0] == '1' || e[0] == '2') ? e[0] - '0' : 0);
+}
+// Before a call that uses c->stream alone: order it after lane 1's work.
+int join_lanes(msckf_ctx* c) {
+    if (!c->lane1_busy) return 0;
+    HIPC(hipStreamWaitEvent(c->stream, c->ev_tail, 0));
+    c->lane1_busy = false;
+    return 0;
+}
+// Before lane 1's first use after a single-stream call: order stream1 after it.
+// (Back-to-back laned calls need no join: a lane's calls queue on its own stream
+// and the lanes share no data.)
+int fork_lanes(msckf_ctx* c) {
+    if (c->lane1_busy) return 0;
+    HIPC(hipEventRecord(c->ev_head, c->stream));
+    HIPC(hipStreamWaitEvent(c->stream1, c->ev_head, 0));
+    c->lane1_busy = true;
+    return 0;
+}
+// Marks the end of lane 1's work of a laned call on every exit path (join_lanes
+// waits on it).
+struct LaneTail {
+    msckf_ctx* c;
+    ~LaneTail() { (void)hipEventRecord(c->ev_tail, c->stream1); }
+};
+#define JOIN_LANES(c)                          \
+    do {                                       \
+        if (int _r = join_lanes(c)) return _r; \
+    } while (0)
+
+// One lane of a call: its stream and timer, and its filters [b0, b0 + nb).
+struct LaneRef {
+    hipStream_t s;
+    KernelTimer* kt;
+    int b0, nb;
+};
+LaneRef lane_ref(msckf_ctx* c, int lane, int nlanes) {
+    const int b0 = subbatch_first_filter(c->B, lane, nlanes), b1 = subbatch_first_filter(c->B, lane + 1, nlanes);
+    if (lane == 0) return {c->stream, &c->timer, b0, b1 - b0};
+    return {c->stream1, &c->timer1, b0, b1 - b0};
+}
+
+// The update chain of one lane, enqueued on the lane's streams.  Per-filter
+// kernels get the lane's views of the state, the workspace and feat_off;
+// per-feature kernels keep the absolute views (they index by feat_filter[f]) and
+// get the lane's part of each class list.  Whatever picks a kernel or sizes its
+// LDS -- the batch size behind the Cholesky path, max_nf, max_obs, the lists'
+// maxM, gram -- is the whole batch's: a lane runs the kernels the batch would.
+// One lane forks stage A onto c->side; under a split it stays inline on the
+// lane's stream (the other lane is the co-running work).
 template <typename T>
-int run_update_chain(msckf_ctx* c, int row_cap, bool triangulate) {
-    hipStream_t s = c->stream;
-    DevState<T> st = dev_state<T>(c);
-    Params<T> prm = make_params<T>(c);
-    FeatBatch<T> fb = feat_batch<T>(c);
-    UpdWs<T> ws = upd_ws<T>(c);
+int enqueue_chain(msckf_ctx* c, const LaneRef& L, int nlanes, int lane, int row_cap, bool triangulate) {
+    hipStream_t s = L.s;
+    const bool inline_a = nlanes > 1;
+    KernelTimer& kt = *L.kt;
+    const DevState<T> st_all = dev_state<T>(c), st = dev_state<T>(c, L.b0, L.nb);
+    const Params<T> prm = make_params<T>(c);
+    const FeatBatch<T> fb_all = feat_batch<T>(c);
+    FeatBatch<T> fb = fb_all;
+    fb.feat_off += L.b0;
+    const UpdWs<T> ws = upd_ws<T>(c, L.b0);
+    GateClasses gc = c->gc;
+    SegClasses sc = c->sc;
+    subbatch_lane_lists(c->gc.off, c->gc_cut, GATE_NLIST, lane, nlanes, gc.beg, gc.end);
+    subbatch_lane_lists(c->sc.off, c->sc_cut, SegClasses::NC, lane, nlanes, sc.beg, sc.end);
     // stage A (register-tile windows) under the Jacobians and gating
     const bool early_a = kalman_chol_supported(c->Cmax);
     if (triangulate) {
-        c->timer.begin(s, "triangulate");
-        launch_triangulate<T>(s, st, prm, fb, c->sc);
-        c->timer.end(s);
+        kt.begin(s, "triangulate");
+        launch_triangulate<T>(s, st_all, prm, fb_all, sc);
+        kt.end(s);
     }
     // Once stage A is on the side stream, every exit path joins it: an early
     // return must not leave k_kal_a reading P while a later call (restore,
@@ -579,31 +684,50 @@ int run_update_chain(msckf_ctx* c, int row_cap, bool triangulate) {
             if (armed) (void)hipStreamSynchronize(c->side);
         }
     } join{c};
-    if (early_a) {
+    if (early_a && inline_a) {
+        launch_kalman_a_reg<T>(s, st, ws, &kt, c->B);
+    } else if (early_a) {
         HIPC(hipEventRecord(c->ev_fork, s));
         HIPC(hipStreamWaitEvent(c->side, c->ev_fork, 0));
         join.armed = true;
-        launch_kalman_a_reg<T>(c->side, st, ws, &c->timer);
+        launch_kalman_a_reg<T>(c->side, st, ws, &kt, c->B);
         HIPC(hipEventRecord(c->ev_join, c->side));
     }
-    c->timer.begin(s, "feature_jacobian");
-    launch_feature<T>(s, st, prm, fb, c->sc);
-    c->timer.end(s);
-    c->timer.begin(s, "gate");
-    c->gate_unrouted = launch_gate<T>(s, st, prm, fb, c->gc);   // reported by unpack_results
-    c->timer.end(s);
-    c->timer.begin(s, "select");
+    kt.begin(s, "feature_jacobian");
+    launch_feature<T>(s, st_all, prm, fb_all, sc);
+    kt.end(s);
+    kt.begin(s, "gate");
+    if (const int u = launch_gate<T>(s, st_all, prm, fb_all, gc)) c->gate_unrouted = u;   // reported by unpack_results
+    kt.end(s);
+    kt.begin(s, "select");
     launch_select<T>(s, st, fb, ws, row_cap);
-    c->timer.end(s);
-    c->timer.begin(s, "compress");
+    kt.end(s);
+    kt.begin(s, "compress");
     launch_compress<T>(s, st, prm, fb, ws, c->max_nf, c->max_obs);
-    c->timer.end(s);
-    if (early_a) {
+    kt.end(s);
+    if (join.armed) {
         HIPC(hipStreamWaitEvent(s, c->ev_join, 0));
         join.armed = false;   // the main stream now orders everything after stage A
     }
-    launch_kalman<T>(s, st, prm, ws, &c->timer);
+    launch_kalman<T>(s, st, prm, ws, &kt, c->B);
     HIPC(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+int run_update_chain(msckf_ctx* c, int row_cap, bool triangulate) {
+    const int nl = active_lanes(c);
+    c->gate_unrouted = 0;
+    c->last_lanes = nl;
+    if (nl == 1) {
+        JOIN_LANES(c);
+        return enqueue_chain<T>(c, lane_ref(c, 0, 1), 1, 0, row_cap, triangulate);
+    }
+    // Two lanes, their chains enqueued back to back.
+    if (int r = fork_lanes(c)) return r;
+    LaneTail tail{c};
+    for (int lane = 0; lane < nl; ++lane)
+        if (int r = enqueue_chain<T>(c, lane_ref(c, lane, nl), nl, lane, row_cap, triangulate)) return r;
     return 0;
 }
 
@@ -613,8 +737,8 @@ int run_kalman_only(msckf_ctx* c) {
     DevState<T> st = dev_state<T>(c);
     Params<T> prm = make_params<T>(c);
     UpdWs<T> ws = upd_ws<T>(c);
-    if (kalman_chol_supported(c->Cmax)) launch_kalman_a_reg<T>(s, st, ws, &c->timer);
-    launch_kalman<T>(s, st, prm, ws, &c->timer);
+    if (kalman_chol_supported(c->Cmax)) launch_kalman_a_reg<T>(s, st, ws, &c->timer, c->B);
+    launch_kalman<T>(s, st, prm, ws, &c->timer, c->B);
     HIPC(hipGetLastError());
     return 0;
 }
@@ -664,6 +788,7 @@ int unpack_results(msckf_ctx* c, const DownList& d, const ResultsRead& r, uint8_
 template <typename T>
 int read_results(msckf_ctx* c, uint8_t* accepted_out, double* gamma_out, double* p_w_out, uint8_t* valid_out,
                  int32_t* rows_out) {
+    JOIN_LANES(c);   // (do_update reads straight after enqueuing the chain: lane 1 may still be running)
     DownList d;   // every requested array in one pinned D2H batch, one synchronisation
     const ResultsRead r = add_results<T>(c, d);
     HIPSYNC(c, d.run(c));
@@ -1076,10 +1201,16 @@ int msckf_create(const msckf_config_t* cfg, int hip_device, int scalar_bytes, in
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming);
+    if (n_filters >= 2) {   // lane 1 (msckf_subbatch.h): a single filter cannot split and creates none of this
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream1, hipStreamNonBlocking);
+        for (hipEvent_t* ev : {&c->ev_head, &c->ev_tail})
+            if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+    }
     if (e != hipSuccess) {
-        if (c->stream) (void)hipStreamDestroy(c->stream);
-        if (c->side) (void)hipStreamDestroy(c->side);
-        if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+        for (hipStream_t s : {c->stream, c->side, c->stream1})
+            if (s) (void)hipStreamDestroy(s);
+        for (hipEvent_t ev : {c->ev_fork, c->ev_join, c->ev_head, c->ev_tail})
+            if (ev) (void)hipEventDestroy(ev);
         delete c;
         FAIL(-2, "hipStreamCreate: %s", hipGetErrorString(e));
     }
@@ -1095,8 +1226,8 @@ int msckf_create(const msckf_config_t* cfg, int hip_device, int scalar_bytes, in
 int msckf_destroy(msckf_ctx_t* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->side) (void)hipStreamSynchronize(c->side);
+    for (hipStream_t s : {c->stream, c->side, c->stream1})
+        if (s) (void)hipStreamSynchronize(s);
     for (auto* b : {&c->P, &c->imu, &c->cams, &c->P_snap, &c->imu_snap, &c->cams_snap, &c->Hthin, &c->Lc, &c->Vi, &c->Sii, &c->G, &c->Tm, &c->W, &c->Wk,
                     &c->dx, &c->batch, &c->obs_ws, &c->obs_ht, &c->obs_g, &c->fqr, &c->tau, &c->ysq, &c->scratch})
         b->release();
@@ -1104,10 +1235,10 @@ int msckf_destroy(msckf_ctx_t* c) {
         b->release();
     c->up.release();
     c->down.release();
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+    for (hipStream_t s : {c->stream, c->side, c->stream1})
+        if (s) (void)hipStreamDestroy(s);
+    for (hipEvent_t ev : {c->ev_fork, c->ev_join, c->ev_head, c->ev_tail})
+        if (ev) (void)hipEventDestroy(ev);
     delete c;
     return 0;
 }
@@ -1127,16 +1258,19 @@ int msckf_device_info(const msckf_ctx_t* c, int* device_out, char* pci_bus_id, i
 int msckf_set_state(msckf_ctx_t* c, int filter, const double* imu, int n_cams, const double* cams, const double* P) {
     if (c) c->last_async = "msckf_set_state";
     if (int r = check_ctx(c, filter)) return r;
+    JOIN_LANES(c);
     return DISPATCH(c, do_set_state, c, filter, imu, n_cams, cams, P);
 }
 
 int msckf_get_state(msckf_ctx_t* c, int filter, double* imu, double* cams, double* P, int* n_cams) {
     if (int r = check_ctx(c, filter)) return r;
+    JOIN_LANES(c);
     return DISPATCH(c, do_get_state, c, filter, imu, cams, P, n_cams);
 }
 
 int msckf_get_cov_diag(msckf_ctx_t* c, int filter, int i0, int n, double* out) {
     if (int r = check_ctx(c, filter)) return r;
+    JOIN_LANES(c);
     if (n > 0 && !out) FAIL(-1, "null output");
     return DISPATCH(c, do_cov_diag_batch, c, 1, &filter, i0, n, out);
 }
@@ -1144,6 +1278,7 @@ int msckf_get_cov_diag(msckf_ctx_t* c, int filter, int i0, int n, double* out) {
 int msckf_propagate(msckf_ctx_t* c, int filter, int n, const double* dt, const double* gyro, const double* acc) {
     if (c) c->last_async = "msckf_propagate";
     if (int r = check_ctx(c, filter)) return r;
+    JOIN_LANES(c);
     if (n > 0 && (!dt || !gyro || !acc)) FAIL(-1, "null sample array");
     const int32_t off[2] = {0, n > 0 ? n : 0};
     return DISPATCH(c, do_propagate_batch, c, 1, &filter, off, dt, gyro, acc);
@@ -1153,6 +1288,7 @@ int msckf_propagate_batch(msckf_ctx_t* c, int nfilt, const int32_t* filters, con
                           const double* dt, const double* gyro, const double* acc) {
     if (c) c->last_async = "msckf_propagate_batch";
     if (!c) FAIL(-1, "null context");
+    JOIN_LANES(c);
     if (int r = check_list(c, nfilt, filters)) return r;
     if (nfilt > 0 && !sample_off) FAIL(-1, "null sample offsets");
     if (nfilt > 0 && sample_off[nfilt] > 0 && (!dt || !gyro || !acc)) FAIL(-1, "null sample array");
@@ -1162,12 +1298,14 @@ int msckf_propagate_batch(msckf_ctx_t* c, int nfilt, const int32_t* filters, con
 int msckf_augment(msckf_ctx_t* c, int filter) {
     if (c) c->last_async = "msckf_augment";
     if (int r = check_ctx(c, filter)) return r;
+    JOIN_LANES(c);
     return DISPATCH(c, do_augment_batch, c, 1, &filter);
 }
 
 int msckf_augment_batch(msckf_ctx_t* c, int nfilt, const int32_t* filters) {
     if (c) c->last_async = "msckf_augment_batch";
     if (!c) FAIL(-1, "null context");
+    JOIN_LANES(c);
     if (int r = check_list(c, nfilt, filters)) return r;
     return DISPATCH(c, do_augment_batch, c, nfilt, filters);
 }
@@ -1175,6 +1313,7 @@ int msckf_augment_batch(msckf_ctx_t* c, int nfilt, const int32_t* filters) {
 int msckf_triangulate(msckf_ctx_t* c, int filter, int nf, const int32_t* obs_off, const int32_t* obs_cam,
                       const double* obs_z, double* p_w_out, uint8_t* valid_out) {
     if (int r = check_ctx(c, filter)) return r;
+    JOIN_LANES(c);
     if (nf > 0 && (!obs_off || !obs_cam || !obs_z || !p_w_out || !valid_out)) FAIL(-1, "null argument");
     return DISPATCH(c, do_triangulate, c, filter, nf, obs_off, obs_cam, obs_z, p_w_out, valid_out);
 }
@@ -1184,6 +1323,7 @@ int msckf_update(msckf_ctx_t* c, int filter, int nf, const int32_t* obs_off, con
                  double* gamma_out, int32_t* rows_out) {
     if (c) c->last_async = "msckf_update";
     if (int r = check_ctx(c, filter)) return r;
+    JOIN_LANES(c);
     if (nf > 0 && (!obs_off || !obs_cam || !obs_z || !p_w || !chi2)) FAIL(-1, "null argument");
     return DISPATCH(c, do_update, c, filter, nf, obs_off, obs_cam, obs_z, p_w, chi2, row_cap, accepted_out,
                     gamma_out, rows_out);
@@ -1192,6 +1332,7 @@ int msckf_update(msckf_ctx_t* c, int filter, int nf, const int32_t* obs_off, con
 int msckf_prune(msckf_ctx_t* c, int filter, int n, const int32_t* cam_slots) {
     if (c) c->last_async = "msckf_prune";
     if (int r = check_ctx(c, filter)) return r;
+    JOIN_LANES(c);
     if (n <= 0) return 1;
     if (!cam_slots) FAIL(-1, "null slot list");
     const int32_t off[2] = {0, n};
@@ -1202,6 +1343,7 @@ int msckf_prune_batch(msckf_ctx_t* c, int nfilt, const int32_t* filters, const i
                       const int32_t* cam_slots) {
     if (c) c->last_async = "msckf_prune_batch";
     if (!c) FAIL(-1, "null context");
+    JOIN_LANES(c);
     if (int r = check_list(c, nfilt, filters)) return r;
     if (nfilt > 0 && !slot_off) FAIL(-1, "null slot offsets");
     if (nfilt > 0 && slot_off[nfilt] > 0 && !cam_slots) FAIL(-1, "null slot list");
@@ -1211,12 +1353,14 @@ int msckf_prune_batch(msckf_ctx_t* c, int nfilt, const int32_t* filters, const i
 int msckf_get_states_batch(msckf_ctx_t* c, int nfilt, const int32_t* filters, double* imu_out, double* cams_out,
                            int32_t* ncams_out) {
     if (!c) FAIL(-1, "null context");
+    JOIN_LANES(c);
     if (int r = check_list(c, nfilt, filters)) return r;
     return DISPATCH(c, do_get_states_batch, c, nfilt, filters, imu_out, cams_out, ncams_out);
 }
 
 int msckf_get_cov_diag_batch(msckf_ctx_t* c, int nfilt, const int32_t* filters, int i0, int n, double* out) {
     if (!c) FAIL(-1, "null context");
+    JOIN_LANES(c);
     if (int r = check_list(c, nfilt, filters)) return r;
     if (nfilt > 0 && n > 0 && !out) FAIL(-1, "null output");
     return DISPATCH(c, do_cov_diag_batch, c, nfilt, filters, i0, n, out);
@@ -1226,6 +1370,7 @@ int msckf_readback(msckf_ctx_t* c, int nfilt, const int32_t* filters, double* im
                    int32_t* ncams_out, int i0, int n, double* cov_out, uint8_t* accepted_out, double* gamma_out,
                    double* p_w_out, uint8_t* valid_out, int32_t* rows_out) {
     if (!c) FAIL(-1, "null context");
+    JOIN_LANES(c);
     if (int r = check_list(c, nfilt, filters)) return r;
     return DISPATCH(c, do_readback, c, nfilt, filters, imu_out, cams_out, ncams_out, i0, n, cov_out, accepted_out,
                     gamma_out, p_w_out, valid_out, rows_out);
@@ -1234,6 +1379,7 @@ int msckf_readback(msckf_ctx_t* c, int nfilt, const int32_t* filters, double* im
 int msckf_batch_triangulate(msckf_ctx_t* c) {
     if (c) c->last_async = "msckf_batch_triangulate";
     if (!c) FAIL(-1, "null context");
+    JOIN_LANES(c);
     return DISPATCH(c, run_triangulate_only, c);
 }
 
@@ -1241,6 +1387,7 @@ int msckf_batch_load(msckf_ctx_t* c, const int32_t* feat_off, const int32_t* obs
                      const double* obs_z, const double* p_w, const double* chi2) {
     if (c) c->last_async = "msckf_batch_load";
     if (!c || !feat_off || !obs_off || !obs_cam || !obs_z) FAIL(-1, "null argument");
+    JOIN_LANES(c);
     return DISPATCH(c, load_features, c, 0, feat_off, 0, obs_off, obs_cam, obs_z, p_w, chi2);
 }
 
@@ -1253,11 +1400,13 @@ int msckf_batch_update(msckf_ctx_t* c, int row_cap, int flags) {
 int msckf_batch_results(msckf_ctx_t* c, uint8_t* accepted_out, double* gamma_out, double* p_w_out,
                         uint8_t* valid_out, int32_t* rows_out) {
     if (!c) FAIL(-1, "null context");
+    JOIN_LANES(c);
     return DISPATCH(c, read_results, c, accepted_out, gamma_out, p_w_out, valid_out, rows_out);
 }
 
 int msckf_snapshot(msckf_ctx_t* c) {
     if (!c) FAIL(-1, "null context");
+    JOIN_LANES(c);
     HIPC(c->P_snap.ensure(c->P.cap));
     HIPC(c->imu_snap.ensure(c->imu.cap));
     HIPC(c->cams_snap.ensure(c->cams.cap));
@@ -1275,6 +1424,33 @@ int msckf_restore(msckf_ctx_t* c) {
     if (c) c->last_async = "msckf_restore";
     if (!c) FAIL(-1, "null context");
     if (!c->has_snapshot) FAIL(-1, "no snapshot");
+    // Laned (active_lanes): each lane copies its own filters' slice of P, imu, cams
+    // and ncams on its own stream, so restore / update / restore ... needs no join
+    // between the lanes and one lane's copy runs under the other's Kalman tail.
+    const int nl = active_lanes(c);
+    c->last_lanes = nl;
+    if (nl > 1) {
+        if (int r = fork_lanes(c)) return r;
+        LaneTail tail{c};
+        const size_t ts = (size_t)c->scalar;
+        const size_t sP = (size_t)c->Dmax * c->Dmax * ts, sI = IMU_STRIDE * ts, sC = (size_t)c->Nmax * CAM_STRIDE * ts;
+        for (int lane = 0; lane < nl; ++lane) {
+            const LaneRef L = lane_ref(c, lane, nl);
+            const size_t b0 = (size_t)L.b0, nb = (size_t)L.nb;
+            L.kt->begin(L.s, "restore");
+            hipError_t e = hipMemcpyAsync(c->P.p + b0 * sP, c->P_snap.p + b0 * sP, nb * sP, hipMemcpyDeviceToDevice, L.s);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(c->imu.p + b0 * sI, c->imu_snap.p + b0 * sI, nb * sI, hipMemcpyDeviceToDevice, L.s);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(c->cams.p + b0 * sC, c->cams_snap.p + b0 * sC, nb * sC, hipMemcpyDeviceToDevice, L.s);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(c->ncams.p + b0, c->ncams_snap.p + b0, nb * sizeof(int), hipMemcpyDeviceToDevice, L.s);
+            L.kt->end(L.s);   // (before the check: a failed copy must not leave the interval without its end event)
+            HIPC(e);
+        }
+        return 0;
+    }
+    JOIN_LANES(c);
     c->timer.begin(c->stream, "restore");
     HIPC(hipMemcpyAsync(c->P.p, c->P_snap.p, c->P.cap, hipMemcpyDeviceToDevice, c->stream));
     HIPC(hipMemcpyAsync(c->imu.p, c->imu_snap.p, c->imu.cap, hipMemcpyDeviceToDevice, c->stream));
@@ -1284,42 +1460,56 @@ int msckf_restore(msckf_ctx_t* c) {
     return 0;
 }
 
+// All lanes idle, both timers collected.
+static int sync_lanes(msckf_ctx_t* c) {
+    JOIN_LANES(c);
+    HIPSYNC(c, hipStreamSynchronize(c->stream));
+    if (c->stream1) HIPSYNC(c, hipStreamSynchronize(c->stream1));
+    c->timer.collect();
+    c->timer1.collect();
+    return 0;
+}
+
 int msckf_sync(msckf_ctx_t* c) {
     if (!c) FAIL(-1, "null context");
-    HIPSYNC(c, hipStreamSynchronize(c->stream));
-    c->timer.collect();
-    return 0;
+    return sync_lanes(c);
 }
 
 int msckf_set_profiling(msckf_ctx_t* c, int on) {
     if (!c) FAIL(-1, "null context");
-    HIPSYNC(c, hipStreamSynchronize(c->stream));
-    c->timer.collect();
-    c->timer.on = on != 0;
-    c->timer.only.clear();
-    c->timer.reset();
+    if (int r = sync_lanes(c)) return r;
+    for (KernelTimer* t : {&c->timer, &c->timer1}) {
+        t->on = on != 0;
+        t->only.clear();
+        t->reset();
+    }
     return 0;
 }
 
 int msckf_set_profiling_stage(msckf_ctx_t* c, const char* stage) {
     if (!c) FAIL(-1, "null context");
-    HIPSYNC(c, hipStreamSynchronize(c->stream));
-    c->timer.collect();
-    c->timer.on = stage != nullptr;
-    c->timer.only = stage ? stage : "";
-    c->timer.reset();
+    if (int r = sync_lanes(c)) return r;
+    for (KernelTimer* t : {&c->timer, &c->timer1}) {
+        t->on = stage != nullptr;
+        t->only = stage ? stage : "";
+        t->reset();
+    }
     return 0;
 }
 
 int msckf_kernel_times(msckf_ctx_t* c, int max_k, double* ms_total, int32_t* launches, char* names_out,
                        int names_cap) {
     if (!c) FAIL(-1, "null context");
-    HIPSYNC(c, hipStreamSynchronize(c->stream));
-    c->timer.collect();
+    if (int r = sync_lanes(c)) return r;
+    // Lane 0 runs every stage of every call, so its names and launch counts are
+    // the calls'; a stage's time is the sum of the lanes' intervals -- with two
+    // lanes an upper bound on its exclusive device time (the lanes overlap).
     int k = std::min<int>(max_k, (int)c->timer.names.size());
     std::string all;
     for (int i = 0; i < k; ++i) {
         ms_total[i] = c->timer.total_ms[i];
+        for (size_t j = 0; j < c->timer1.names.size(); ++j)
+            if (c->timer1.names[j] == c->timer.names[i]) ms_total[i] += c->timer1.total_ms[j];
         launches[i] = c->timer.launches[i];
         all += c->timer.names[i];
         all.push_back('\0');
@@ -1336,6 +1526,7 @@ int msckf_kernel_times(msckf_ctx_t* c, int max_k, double* ms_total, int32_t* lau
 // Kalman workspace buffer (0 Lc, 1 Vi, 2 Sii, 3 G, 4 Tm, 5 W, 6 H_thin [A | b], 7 afail (ints)) to the host.
 int msckf_debug_workspace(msckf_ctx_t* c, int which, double* out, size_t count) {
     if (!c || !out) FAIL(-1, "null argument");
+    JOIN_LANES(c);
     const void* src = which == 0 ? c->Lc.p : which == 1 ? c->Vi.p : which == 2 ? c->Sii.p
                     : which == 3 ? c->G.p : which == 4 ? c->Tm.p : which == 5 ? c->W.p
                     : which == 6 ? (const void*)c->Hthin.p : which == 7 ? (const void*)c->afail.p : nullptr;
@@ -1349,6 +1540,7 @@ int msckf_debug_workspace(msckf_ctx_t* c, int which, double* out, size_t count) 
 // Kalman workspace buffer (6: H_thin [A | b], [B][Cmax][Cmax + 1]) from the host.
 int msckf_debug_set_workspace(msckf_ctx_t* c, int which, const double* in, size_t count) {
     if (!c || !in) FAIL(-1, "null argument");
+    JOIN_LANES(c);
     void* dst = which == 6 ? (void*)c->Hthin.p : nullptr;
     if (!dst) FAIL(-1, "unknown workspace %d", which);
     if (count * sizeof(double) > c->Hthin.cap) FAIL(-1, "%zu doubles exceed H_thin", count);
@@ -1357,12 +1549,21 @@ int msckf_debug_set_workspace(msckf_ctx_t* c, int which, const double* in, size_
     return 0;
 }
 
+// Debug (not in include/msckf_hip.h): how many lanes the last msckf_restore or
+// update chain of the context ran as (msckf_subbatch.h), so that a test can tell
+// a split that was taken from one that was not.
+int msckf_debug_lanes(msckf_ctx_t* c) {
+    if (!c) FAIL(-1, "null context");
+    return c->last_lanes;
+}
+
 // Debug: the Kalman stages alone -- stage A (on the main stream), B, C, E and the
 // state correction -- on the batch's current H_thin and stacking info, so that a
 // test can drive the innovation factorisation with a chosen information matrix.
 int msckf_debug_kalman(msckf_ctx_t* c) {
     if (c) c->last_async = "msckf_debug_kalman";
     if (!c) FAIL(-1, "null context");
+    JOIN_LANES(c);
     return DISPATCH(c, run_kalman_only, c);
 }
 

@@ -1379,18 +1379,21 @@ static void launch_mk(hipStream_t s, const DevState<T>& st, const UpdWs<T>& ws, 
 constexpr int MK_MIN_B = 64;
 // MSCKF_KALMAN_CHOL=mfma / tiles (environment, read per launch) forces one
 // path -- the parity tests run both on the same inputs.
-template <typename T> static bool use_mk(const DevState<T>& st) {
+// batch_B is the whole batch's filter count: a lane of it (msckf_subbatch.h)
+// runs the path the whole batch would.
+static bool use_mk(int batch_B) {
     if (const char* e = getenv("MSCKF_KALMAN_CHOL")) {
         if (e[0] == 'm') return true;
         if (e[0] == 't') return false;
     }
-    return st.B >= MK_MIN_B;
+    return batch_B >= MK_MIN_B;
 }
 
 template <typename T>
-void launch_kalman_a_reg(hipStream_t s, const DevState<T>& st, const UpdWs<T>& ws, KernelTimer* kt) {
+void launch_kalman_a_reg(hipStream_t s, const DevState<T>& st, const UpdWs<T>& ws, KernelTimer* kt, int batch_B) {
+    if (st.B <= 0) return;
     const int Cp = (ws.Cmax + 3) & ~3;
-    if (use_mk(st)) {
+    if (use_mk(batch_B)) {
         kt->begin(s, "kalman_a");
         launch_mk<T, 0>(s, st, ws, (Cp + KW + 15) / 16);
         kt->end(s);
@@ -1409,7 +1412,7 @@ void launch_kalman_a_reg(hipStream_t s, const DevState<T>& st, const UpdWs<T>& w
 
 template <typename T>
 void launch_kalman_chol(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const UpdWs<T>& ws,
-                        KernelTimer* kt) {
+                        KernelTimer* kt, int batch_B) {
     const int Cmax = ws.Cmax;
     const bool reg = kalman_chol_supported(Cmax);   // else large window: global-memory stages A and C
     const int Cq = (Cmax + 15) & ~15;
@@ -1431,7 +1434,7 @@ void launch_kalman_chol(hipStream_t s, const DevState<T>& st, const Params<T>& p
     kt->end(s);
     kt->begin(s, "kalman_c");
     if (reg) {   // C1: Cholesky of T (register tiles); C2: MFMA forward substitution of the extra rows
-        if (use_mk(st)) {
+        if (use_mk(batch_B)) {
             launch_mk<T, 1>(s, st, ws, (Cmax + 15) / 16);
         } else {
             const int nTc = ((Cmax + 3) & ~3) / 4;
@@ -1468,11 +1471,11 @@ void launch_kalman_chol(hipStream_t s, const DevState<T>& st, const Params<T>& p
     kt->end(s);
 }
 
-template void launch_kalman_a_reg<float>(hipStream_t, const DevState<float>&, const UpdWs<float>&, KernelTimer*);
-template void launch_kalman_a_reg<double>(hipStream_t, const DevState<double>&, const UpdWs<double>&, KernelTimer*);
+template void launch_kalman_a_reg<float>(hipStream_t, const DevState<float>&, const UpdWs<float>&, KernelTimer*, int);
+template void launch_kalman_a_reg<double>(hipStream_t, const DevState<double>&, const UpdWs<double>&, KernelTimer*, int);
 template void launch_kalman_chol<float>(hipStream_t, const DevState<float>&, const Params<float>&,
-                                        const UpdWs<float>&, KernelTimer*);
+                                        const UpdWs<float>&, KernelTimer*, int);
 template void launch_kalman_chol<double>(hipStream_t, const DevState<double>&, const Params<double>&,
-                                         const UpdWs<double>&, KernelTimer*);
+                                         const UpdWs<double>&, KernelTimer*, int);
 
 }  // namespace msckf

@@ -2799,11 +2799,11 @@ template <int... C, typename F>
 void for_seg_classes(std::integer_sequence<int, C...>, const SegClasses& sc, F&& launch) {
     ([&] {
         constexpr int S = SegClasses::S[C], lanes = S < 64 ? S : 64;
-        const int cnt = sc.off[C + 1] - sc.off[C];
-        if (cnt == 0) return;
+        const int cnt = sc.end[C] - sc.beg[C];
+        if (cnt <= 0) return;
         const int waves = (cnt * lanes + 63) / 64, blocks = (waves + 3) / 4;
         launch(std::integral_constant<int, lanes>{}, std::integral_constant<int, S / lanes>{}, dim3(blocks),
-               sc.list + sc.off[C], cnt);
+               sc.list + sc.beg[C], cnt);
     }(), ...);
 }
 template <typename F>
@@ -2844,9 +2844,9 @@ int launch_gate(hipStream_t s, const DevState<T>& st, const Params<T>& prm, cons
     if (fb.nf == 0) return 0;
     int unrouted = 0;   // block count of a list no tile kernel took (launch_gate_tiles returned false)
     for (int l = 0; l < GATE_NLIST; ++l) {
-        const int cnt = gc.off[l + 1] - gc.off[l];
-        if (cnt == 0) continue;
-        const int* list = gc.list + gc.off[l];
+        const int cnt = gc.end[l] - gc.beg[l];
+        if (cnt <= 0) continue;
+        const int* list = gc.list + gc.beg[l];
         if (l == GATE_LIST_GLOBAL)
             hipLaunchKernelGGL(k_gate<T>, dim3(cnt), dim3(256), 0, s, st, prm, fb, list);
         else if (!launch_gate_tiles<T>(s, st, prm, fb, list, cnt, l + 1, gc.maxM[l]))
@@ -2858,6 +2858,7 @@ int launch_gate(hipStream_t s, const DevState<T>& st, const Params<T>& prm, cons
 template <typename T>
 void launch_select(hipStream_t s, const DevState<T>& st, const FeatBatch<T>& fb, const UpdWs<T>& ws,
                    int row_cap) {
+    if (st.B <= 0) return;   // an empty lane (msckf_subbatch.h): a zero-sized grid is an error
     hipLaunchKernelGGL(k_select<T>, dim3((st.B + 3) / 4), dim3(256), 0, s, st, fb, ws, row_cap);
 }
 
@@ -2886,6 +2887,7 @@ bool info_fused_fits(int Nmax, int maxnf) { return Nmax <= 32 && maxnf > 0 && in
 template <typename T>
 void launch_compress(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
                      const UpdWs<T>& ws, int maxnf, int maxobs) {
+    if (st.B <= 0) return;
     // windows up to 32 cams, no Gram records: the fused assembly (k_info_fused)
     if (!fb.gram) {
         const size_t lds = info_fused_lds(maxnf);
@@ -2926,8 +2928,9 @@ void launch_compress(hipStream_t s, const DevState<T>& st, const Params<T>& prm,
 
 template <typename T>
 void launch_kalman(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const UpdWs<T>& ws,
-                   KernelTimer* kt) {
-    launch_kalman_chol<T>(s, st, prm, ws, kt);
+                   KernelTimer* kt, int batch_B) {
+    if (st.B <= 0) return;
+    launch_kalman_chol<T>(s, st, prm, ws, kt, batch_B);
     kt->begin(s, "kalman_correct");
     hipLaunchKernelGGL(k_correct<T>, dim3(st.B), dim3(64), 0, s, st, ws);
     kt->end(s);
@@ -2946,7 +2949,7 @@ void launch_kalman(hipStream_t s, const DevState<T>& st, const Params<T>& prm, c
     template int launch_gate<T>(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const GateClasses&); \
     template void launch_select<T>(hipStream_t, const DevState<T>&, const FeatBatch<T>&, const UpdWs<T>&, int); \
     template void launch_compress<T>(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const UpdWs<T>&, int, int); \
-    template void launch_kalman<T>(hipStream_t, const DevState<T>&, const Params<T>&, const UpdWs<T>&, KernelTimer*);
+    template void launch_kalman<T>(hipStream_t, const DevState<T>&, const Params<T>&, const UpdWs<T>&, KernelTimer*, int);
 INSTANTIATE(float)
 INSTANTIATE(double)
 

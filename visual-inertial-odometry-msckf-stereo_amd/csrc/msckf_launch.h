@@ -37,6 +37,8 @@ inline void lds_limit(const void* fn, size_t bytes) {
 
 // Accumulates device time per kernel name from HIP events recorded on the
 // launch stream (so the measurement sees exactly the stream the kernel runs on).
+// One timer per lane (msckf_subbatch.h): each has its own open interval, and
+// msckf_kernel_times adds the lanes' totals.
 struct KernelTimer {
     bool on = false;
     std::string only;    // non-empty: time this stage only (the others record no events)
@@ -106,7 +108,8 @@ struct SegClasses {
     static constexpr int NC = 5;
     static constexpr int S[NC] = {8, 16, 32, 64, 128};   // 128: a whole wavefront, 2 observations per lane
     const int* list = nullptr;
-    int off[NC + 1] = {};
+    int off[NC + 1] = {};             // the loaded batch's lists, back to back in `list`
+    int beg[NC] = {}, end[NC] = {};   // what a launch covers of each: all of it, or one lane's part (msckf_subbatch.h)
 };
 template <typename T>
 void launch_triangulate(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const SegClasses&);
@@ -119,7 +122,8 @@ void launch_feature(hipStream_t, const DevState<T>&, const Params<T>&, const Fea
 struct GateClasses {
     const int* list = nullptr;
     int off[GATE_NLIST + 1] = {};
-    int maxM[GATE_NLIST] = {};
+    int beg[GATE_NLIST] = {}, end[GATE_NLIST] = {};   // launched range of each list, as SegClasses
+    int maxM[GATE_NLIST] = {};                         // of the whole list: a lane runs the whole batch's kernels
 };
 // Returns 0, or the 16-row block count of a non-empty feature list that no
 // gating kernel is instantiated for (those features then keep the previous
@@ -150,11 +154,14 @@ size_t kalman_global_ws_doubles(int Cmax);
 // Stage A of the register-tile windows (kalman_chol_supported) reads only P and
 // writes only Lc / Vi / Sii / afail, so it is launched on a side stream at the
 // start of the update chain; launch_kalman_chol then skips it.
+// batch_B: the filter count of the whole batch, which picks the Cholesky path
+// (MK_MIN_B) -- DevState::B is the launched lane's count and only sizes grids.
 template <typename T>
-void launch_kalman_a_reg(hipStream_t, const DevState<T>&, const UpdWs<T>&, KernelTimer*);
+void launch_kalman_a_reg(hipStream_t, const DevState<T>&, const UpdWs<T>&, KernelTimer*, int batch_B);
 template <typename T>
-void launch_kalman_chol(hipStream_t, const DevState<T>&, const Params<T>&, const UpdWs<T>&, KernelTimer*);
+void launch_kalman_chol(hipStream_t, const DevState<T>&, const Params<T>&, const UpdWs<T>&, KernelTimer*,
+                        int batch_B);
 template <typename T>
-void launch_kalman(hipStream_t, const DevState<T>&, const Params<T>&, const UpdWs<T>&, KernelTimer*);
+void launch_kalman(hipStream_t, const DevState<T>&, const Params<T>&, const UpdWs<T>&, KernelTimer*, int batch_B);
 
 }  // namespace msckf
