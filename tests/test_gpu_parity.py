@@ -15,6 +15,7 @@ import pytest
 
 from conftest import golden, rel
 from helpers import oracle_state_from_arrays, problem_to_dict, feature_obs, oracle_update, rounded, sequence_config
+from lifecycle import propagate_batch_vs_oracle
 from oracle import msckf_oracle as O
 import msckf_amd
 from msckf_amd import synth, FilterConfig, CHI2_05, chi2_threshold
@@ -94,29 +95,7 @@ def test_propagate_batch_vs_oracle(N, dtype):
     if dtype == np.float32:
         ds = [rounded(d) for d in ds]
     ctx = make_ctx(ds, dtype=dtype, cap=N)
-    rng = np.random.default_rng(N)
-    dt = np.full(B * n, 0.005)
-    gyro = 0.3 * rng.standard_normal((B * n, 3))
-    acc = rng.standard_normal((B * n, 3)) + np.array([0.0, 0.0, 9.81])
-    if dtype == np.float32:
-        gyro, acc = gyro.astype(np.float32).astype(float), acc.astype(np.float32).astype(float)
-    ctx.propagate_batch([0, 1], [0, n, 2 * n], dt, gyro, acc)
-    tol = 1e-12 if dtype == np.float64 else 1e-5
-    for b, d in enumerate(ds):
-        st = oracle_state_from_arrays(d)
-        st.imu.nulls_alias = True
-        st.imu.timestamp = 0.0
-        t_k = 0.0
-        for k in range(b * n, (b + 1) * n):
-            t_k = st.imu.timestamp + dt[k]
-            O.process_model(st, t_k, gyro[k], acc[k])
-            st.imu.timestamp = t_k
-        imu, cams, P = ctx.get_state(b)
-        s = unpack_imu(imu)
-        assert rel(P, st.P) < tol, rel(P, st.P)
-        np.testing.assert_array_equal(P, P.T)
-        for key, ref_v in (("q", st.imu.q), ("v", st.imu.v), ("p", st.imu.p)):
-            assert np.abs(s[key] - ref_v).max() <= tol * max(1.0, np.abs(ref_v).max()), key
+    propagate_batch_vs_oracle(ctx, ds, [n] * B, dtype, seed=N)
 
 
 def test_augment_golden():
