@@ -8,7 +8,14 @@ through the binding: packing, one launch, one synchronisation) at 2 sets x 100
 points (one frame's two cameras) and 22 sets x 100 points (the scheduler's 11
 lanes), next to the numpy reference tests/ransac_ref.py on the host.
 
-    python tools/bench_frontend.py [--frames 60]
+--device-pipeline runs the same stream a second time with
+FrontendConfig.device_pipeline on (stereo_match and the detection + sieve of
+add_new_features as single device calls, include/msckf_pipeline.h), checks that
+it publishes the same messages, and adds to the JSON line its frames/s next to
+the default path's and the wall time of one ImageProcessor.stereo_match at 200
+points as the one call and as the composed six.
+
+    python tools/bench_frontend.py [--frames 60] [--device-pipeline]
 """
 import argparse
 import json
@@ -50,9 +57,43 @@ def ransac_leg(fe, n_sets, n=100, n_hyp=7, reps=50):
     return {"device_ms": round(float(np.median(dev)), 4), "numpy_reference_ms": round(float(np.median(host)), 3)}
 
 
+def run_stream(cfg, frames):
+    """(ImageProcessor, frames/s from frame 2 on, features per frame, messages)."""
+    ip = fe_mod.ImageProcessor(cfg)
+    nfeat, msgs = [], []
+    t0 = None
+    for k, (c0, c1) in enumerate(frames):
+        t = 0.05 * k
+        for j in range(10):
+            ip.imu_callback(ImuMsg(t - 0.05 + 0.005 * j, np.zeros(3), np.array([0.0, 0.0, 9.81])))
+        if k == 2:
+            t0 = time.perf_counter()
+        msg = ip.stareo_callback(StereoMsg(t, c0, c1, ImgMsg(t, c0), ImgMsg(t, c1)))
+        nfeat.append(len(msg.vio_features))
+        msgs.append(msg)
+    el = time.perf_counter() - t0
+    return ip, (len(frames) - 2) / el, nfeat, msgs
+
+
+def stereo_leg(ip, c0, c1, pts, reps=30):
+    """Median wall time (ms) of ImageProcessor.stereo_match on the pair (c0, c1)."""
+    ip.cam0_curr_img_msg, ip.cam1_curr_img_msg = ImgMsg(0.0, c0), ImgMsg(0.0, c1)
+    ip.create_image_pyramids()
+    for _ in range(3):
+        ip.stereo_match(pts)
+    ms = []
+    for _ in range(reps):
+        t1 = time.perf_counter()
+        ip.stereo_match(pts)
+        ms.append((time.perf_counter() - t1) * 1e3)
+    return round(float(np.median(ms)), 3)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=60)
+    ap.add_argument("--device-pipeline", action="store_true",
+                    help="also run the stream with FrontendConfig.device_pipeline on")
     a = ap.parse_args()
     W, H = 752, 480
     f = fs.texture_fn(4, W=W, H=H)
@@ -65,18 +106,20 @@ def main():
     for k in range(a.frames):   # rendered up front: not part of the timing
         dx, dy = 1.5 * (k % 40), -0.5 * (k % 40)
         frames.append((fs.render(f, W, H, dx, dy), fs.render(f, W, H, dx - 12.0, dy)))
-    ip = fe_mod.ImageProcessor(cfg)
-    nfeat = []
-    t0 = None
-    for k, (c0, c1) in enumerate(frames):
-        t = 0.05 * k
-        for j in range(10):
-            ip.imu_callback(ImuMsg(t - 0.05 + 0.005 * j, np.zeros(3), np.array([0.0, 0.0, 9.81])))
-        if k == 2:
-            t0 = time.perf_counter()
-        msg = ip.stareo_callback(StereoMsg(t, c0, c1, ImgMsg(t, c0), ImgMsg(t, c1)))
-        nfeat.append(len(msg.vio_features))
-    el = time.perf_counter() - t0
+    ip, fps, nfeat, msgs = run_stream(cfg, frames)
+    extra = {}
+    if a.device_pipeline:
+        cfg_on = fe_mod.FrontendConfig(**{**vars(cfg), "device_pipeline": True})
+        ip_on, fps_on, nfeat_on, msgs_on = run_stream(cfg_on, frames)
+        if msgs_on != msgs:
+            raise SystemExit("the device pipeline published different messages")
+        fps = 0.5 * (fps + run_stream(cfg, frames)[1])          # off, on, off, on: the means of two runs each
+        fps_on = 0.5 * (fps_on + run_stream(cfg_on, frames)[1])
+        pts = ip.fe.fast(ip._slot_c0, 15)[0][:200].astype(float)
+        extra = {"frames_per_s_device_pipeline": round(fps_on, 1), "messages_identical": True,
+                 "stereo_match_200pts_ms": {"one_call": stereo_leg(ip_on, *frames[0], pts),
+                                            "composed_six_calls": stereo_leg(ip, *frames[0], pts)}}
+        ip_on.fe.close()
     fe = ip.fe
     c0 = frames[0][0]
     ops = {}
@@ -87,7 +130,7 @@ def main():
     t1 = time.perf_counter(); fe.lk(0, 1, pts, pts); ops["lk_200pts_ms"] = (time.perf_counter() - t1) * 1e3
     ransac = {"%dx100" % s: ransac_leg(fe, s) for s in (2, 22)}
     print(json.dumps({"component": "stereo front-end (image.py) on GPU", "resolution": [W, H],
-                      "frames_per_s": round((a.frames - 2) / el, 1), "features_per_frame": float(np.mean(nfeat)),
+                      "frames_per_s": round(fps, 1), **extra, "features_per_frame": float(np.mean(nfeat)),
                       "fast_keypoints_frame0": int(len(xy)), "op_wall_ms": {k: round(v, 3) for k, v in ops.items()},
                       "two_point_ransac_n_hyp7": ransac,
                       "note": "host bookkeeping in Python; synthetic stream; cv2 absent (no reference timing)"}))

@@ -107,6 +107,18 @@ FRONTEND_RANSAC_SIGS = {
 }
 FRONTEND_RANSAC_EXPORTED = tuple(FRONTEND_RANSAC_SIGS)
 
+# stereo matching and grid-selected detection as single device calls
+# (include/msckf_pipeline.h), same library and context
+GRID_MAX_K = 16
+GRID_MAX_CELLS = 1024
+FRONTEND_PIPELINE_SIGS = {
+    "mfe_stereo_match": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _D, _D, C.c_int, _D, _D, C.c_int, _D, _D, _D,
+                                   C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _F, _U8, _U8]),
+    "mfe_fast_grid": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _F, C.c_int, C.c_int, C.c_int, C.c_int, _F, _F, _I,
+                                _I]),
+}
+FRONTEND_PIPELINE_EXPORTED = tuple(FRONTEND_PIPELINE_SIGS)
+
 # multi-GPU replica transport, RCCL (include/msckf_replicas.h), same library
 REPLICA_SIGS = {
     "msckf_rccl_unique_id": (C.c_int, [_U8]),
@@ -133,7 +145,8 @@ def load_library(path: str = LIB_PATH):
                              "(or __graft_entry__.build()); there is no CPU fallback" % path)
         lib = C.CDLL(path)
         for name, (res, args) in (list(_SIGS.items()) + list(FRONTEND_SIGS.items()) +
-                                  list(FRONTEND_RANSAC_SIGS.items()) + list(REPLICA_SIGS.items())):
+                                  list(FRONTEND_RANSAC_SIGS.items()) + list(FRONTEND_PIPELINE_SIGS.items()) +
+                                  list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -21,6 +21,14 @@
 //   k_undistort / k_distort   radtan and equidistant camera models, fp64
 //   k_two_point_ransac   temporal outlier rejection (include/msckf_ransac.h): one
 //               workgroup per point set, one wave per hypothesis
+//   k_stereo_match   ImageProcessor.stereo_match in one launch
+//               (include/msckf_pipeline.h): one wavefront per point, the camera
+//               models and both LK runs from the functions k_undistort,
+//               k_distort and k_lk are made of
+//   k_mask_clear / k_row_scan / k_grid_select   masked detection with the
+//               per-cell selection (include/msckf_pipeline.h) around k_fast and
+//               k_fast_rows: device-built mask, device scan of the row counts,
+//               one workgroup per grid cell
 // Images are 8-bit, small (752 x 480 for EuRoC) and read through the cache:
 // these kernels are latency-class work, not HBM-bound.
 #include <hip/hip_runtime.h>
@@ -33,6 +41,7 @@
 #include <vector>
 
 #include "../../include/msckf_frontend.h"
+#include "../../include/msckf_pipeline.h"
 #include "../../include/msckf_ransac.h"
 
 namespace {
@@ -265,16 +274,15 @@ __device__ __forceinline__ void lk_weights(float a, float b, int& w00, int& w01,
 
 constexpr int LK_SLOTS = 4;   // window pixels per lane: win <= 16 (win^2 <= 256)
 
-__global__ void __launch_bounds__(64) k_lk(Pyr P, Pyr N, int n, const float* __restrict__ prev_pts,
-                                           float* __restrict__ next_pts, uint8_t* __restrict__ status, int win,
-                                           int max_level, int max_iter, double eps) {
+// One point on one wavefront (every lane calls it with the same arguments):
+// (nx, ny) is nextPts[ptidx], the initial guess on entry and the tracked
+// position on exit, the same in every lane; returns the status.  Shared by
+// k_lk and k_stereo_match.
+__device__ __forceinline__ bool lk_point(const Pyr& P, const Pyr& N, float ppx, float ppy, float& nx, float& ny,
+                                         int win, int max_level, int max_iter, double eps, int lane) {
 #pragma clang fp contract(off)
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= n) return;
     const float half = (float)(win - 1) * 0.5f;
     const int npix = win * win;
-    const float ppx = prev_pts[2 * i], ppy = prev_pts[2 * i + 1];
-    float nx = next_pts[2 * i], ny = next_pts[2 * i + 1];   // nextPts[ptidx]
     bool st = true;
     for (int level = max_level; level >= 0; --level) {
         const Level I = P.lv[level], J = N.lv[level];
@@ -366,6 +374,16 @@ __global__ void __launch_bounds__(64) k_lk(Pyr P, Pyr N, int n, const float* __r
             pdy = dy;
         }
     }
+    return st;
+}
+
+__global__ void __launch_bounds__(64) k_lk(Pyr P, Pyr N, int n, const float* __restrict__ prev_pts,
+                                           float* __restrict__ next_pts, uint8_t* __restrict__ status, int win,
+                                           int max_level, int max_iter, double eps) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= n) return;
+    float nx = next_pts[2 * i], ny = next_pts[2 * i + 1];
+    const bool st = lk_point(P, N, prev_pts[2 * i], prev_pts[2 * i + 1], nx, ny, win, max_level, max_iter, eps, lane);
     if (lane == 0) {
         next_pts[2 * i] = nx;
         next_pts[2 * i + 1] = ny;
@@ -425,30 +443,27 @@ __device__ __forceinline__ bool undistort_norm(const CamModel& c, double px, dou
     return true;
 }
 
-__global__ void __launch_bounds__(256) k_undistort(CamModel c, int n, const double* __restrict__ in,
-                                                   double* __restrict__ out) {
+// mfe_undistort of one point: undistort_norm, the rectification c.R and the new
+// intrinsics; a rejected fisheye solution goes out as (-1e6, -1e6), unrectified.
+// Shared by k_undistort and k_stereo_match.
+__device__ __forceinline__ void undistort_rect(const CamModel& c, double px, double py, double& xo, double& yo) {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
     double x, y;
-    if (!undistort_norm(c, in[2 * t], in[2 * t + 1], x, y)) {
-        out[2 * t] = -1000000.0;
-        out[2 * t + 1] = -1000000.0;
+    if (!undistort_norm(c, px, py, x, y)) {
+        xo = -1000000.0;
+        yo = -1000000.0;
         return;
     }
     const double X = c.R[0] * x + c.R[1] * y + c.R[2];
     const double Y = c.R[3] * x + c.R[4] * y + c.R[5];
     const double Wz = c.R[6] * x + c.R[7] * y + c.R[8];
-    out[2 * t] = c.nfx * X / Wz + c.ncx;
-    out[2 * t + 1] = c.nfy * Y / Wz + c.ncy;
+    xo = c.nfx * X / Wz + c.ncx;
+    yo = c.nfy * Y / Wz + c.ncy;
 }
 
-__global__ void __launch_bounds__(256) k_distort(CamModel c, int n, const double* __restrict__ in,
-                                                 double* __restrict__ out) {
+// mfe_distort of one normalised point.  Shared by k_distort and k_stereo_match.
+__device__ __forceinline__ void distort_pix(const CamModel& c, double x, double y, double& xo, double& yo) {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
-    const double x = in[2 * t], y = in[2 * t + 1];
     double xd, yd;
     if (c.model == MFE_EQUIDISTANT) {   // cv2.fisheye.distortPoints
         const double r = sqrt(x * x + y * y);
@@ -464,8 +479,28 @@ __global__ void __launch_bounds__(256) k_distort(CamModel c, int n, const double
         xd = x * radial + 2 * p1 * x * y + p2 * (r2 + 2 * x * x);
         yd = y * radial + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
     }
-    out[2 * t] = c.fx * xd + c.cx;
-    out[2 * t + 1] = c.fy * yd + c.cy;
+    xo = c.fx * xd + c.cx;
+    yo = c.fy * yd + c.cy;
+}
+
+__global__ void __launch_bounds__(256) k_undistort(CamModel c, int n, const double* __restrict__ in,
+                                                   double* __restrict__ out) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    double x, y;
+    undistort_rect(c, in[2 * t], in[2 * t + 1], x, y);
+    out[2 * t] = x;
+    out[2 * t + 1] = y;
+}
+
+__global__ void __launch_bounds__(256) k_distort(CamModel c, int n, const double* __restrict__ in,
+                                                 double* __restrict__ out) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    double x, y;
+    distort_pix(c, in[2 * t], in[2 * t + 1], x, y);
+    out[2 * t] = x;
+    out[2 * t + 1] = y;
 }
 
 // ------------------------------------------------------- two-point RANSAC --
@@ -683,6 +718,162 @@ __global__ void __launch_bounds__(RS_THREADS) k_two_point_ransac(RansacArgs a) {
     }
 }
 
+// ----------------------------------------------------------- stereo match --
+// include/msckf_pipeline.h states the algorithm: ImageProcessor.stereo_match
+// as one kernel, one wavefront per point.  Every lane computes the same fp64
+// camera arithmetic; the two LK runs spread their windows over the lanes.
+struct StereoArgs {
+    CamModel cam0, cam1;   // cam0.R = R_guess; both with new intrinsics [1 1 0 0]
+    double E[9];
+    double eps, epi_thr;   // epi_thr = stereo_threshold * norm_pixel_unit
+    const double* pts;
+    float* cam1_pts;
+    uint8_t *inlier, *reason;
+    int n, win, max_level, max_iter;
+};
+
+__global__ void __launch_bounds__(64) k_stereo_match(Pyr P0, Pyr P1, StereoArgs a) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= a.n) return;
+    const double px = a.pts[2 * i], py = a.pts[2 * i + 1];
+    double ux, uy, gx, gy;
+    undistort_rect(a.cam0, px, py, ux, uy);   // step 1
+    distort_pix(a.cam1, ux, uy, gx, gy);
+    const float c0x = (float)px, c0y = (float)py;
+    float c1x = (float)gx, c1y = (float)gy;
+    const bool st = lk_point(P0, P1, c0x, c0y, c1x, c1y, a.win, a.max_level, a.max_iter, a.eps, lane);   // step 2
+    float bx = c0x, by = c0y;
+    (void)lk_point(P1, P0, c1x, c1y, bx, by, a.win, a.max_level, a.max_iter, a.eps, lane);   // step 3
+    const float dx = c0x - bx, dy = c0y - by;
+    const float err = sqrtf(dx * dx + dy * dy);
+    const float xmax = (float)(P1.lv[0].w - 1), ymax = (float)(P1.lv[0].h - 1);
+    int reason = 0;
+    if (!st) {
+        reason = 1;
+    } else if (!(err < 3.f)) {
+        reason = 2;
+    } else if (!(fabs(gy - (double)c1y) < 20.0)) {
+        reason = 3;
+    } else if (c1x < 0.f || c1x > xmax || c1y < 0.f || c1y > ymax) {
+        reason = 4;
+    } else {
+        double u0x, u0y, u1x, u1y;
+        if (!undistort_norm(a.cam0, (double)c0x, (double)c0y, u0x, u0y)) u0x = u0y = -1000000.0;
+        if (!undistort_norm(a.cam1, (double)c1x, (double)c1y, u1x, u1y)) u1x = u1y = -1000000.0;
+        const double lx = a.E[0] * u0x + a.E[1] * u0y + a.E[2], ly = a.E[3] * u0x + a.E[4] * u0y + a.E[5];
+        const double error = fabs(u1x * lx) / sqrt(lx * lx + ly * ly);
+        if (error > a.epi_thr) reason = 5;
+    }
+    if (lane == 0) {
+        a.cam1_pts[2 * i] = c1x;
+        a.cam1_pts[2 * i + 1] = c1y;
+        a.inlier[i] = reason == 0 ? 1 : 0;
+        a.reason[i] = (uint8_t)reason;
+    }
+}
+
+// ---------------------------------------------------- grid-selected detection --
+// include/msckf_pipeline.h states the stages.  k_mask_clear: 7 threads per
+// occupied point, one per row of its 7 x 7 block (threads of overlapping blocks
+// store the same 0).
+__global__ void __launch_bounds__(256) k_mask_clear(const float* __restrict__ occ, int n_occ,
+                                                    uint8_t* __restrict__ mask, int w, int h) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int p = t / 7, r = t - 7 * p;
+    if (p >= n_occ) return;
+    const float px = occ[2 * p], py = occ[2 * p + 1];
+    if (!(px >= 3.f && py >= 3.f && px < (float)(w + 3) && py < (float)(h + 3))) return;   // NaN: nothing
+    const int x = (int)px, yy = (int)py - 3 + r;   // 3 <= x <= w + 2, yy >= 0
+    if (yy >= h) return;
+    const int x1 = min(x + 3, w - 1);
+    for (int xx = x - 3; xx <= x1; ++xx) mask[(size_t)yy * w + xx] = 0;
+}
+
+// exclusive scan of the row counts in one workgroup: a contiguous run of rows
+// per thread, the 256 run sums through LDS; *total = the sum
+__global__ void __launch_bounds__(256) k_row_scan(const int* __restrict__ cnt, int* __restrict__ off, int h,
+                                                  int* __restrict__ total) {
+    __shared__ int s_part[256];
+    const int tid = threadIdx.x, per = (h + 255) / 256;
+    const int r0 = min(tid * per, h), r1 = min(r0 + per, h);
+    int s = 0;
+    for (int r = r0; r < r1; ++r) s += cnt[r];
+    s_part[tid] = s;
+    __syncthreads();
+    int base = 0;
+    for (int j = 0; j < tid; ++j) base += s_part[j];
+    for (int r = r0; r < r1; ++r) {
+        off[r] = base;
+        base += cnt[r];
+    }
+    if (tid == 255) *total = base;
+}
+
+struct GridArgs {
+    const float *xy, *resp;   // the raster list
+    const int* total;
+    float *out_xy, *out_resp;   // [cell][k]
+    int* cell_count;
+    int cap, gh, gw, grid_col, k;
+};
+
+__device__ __forceinline__ long long wave_max64(long long v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const int lo = __shfl_xor((int)(v & 0xffffffffLL), m, 64);
+        const int hi = __shfl_xor((int)(v >> 32), m, 64);
+        const long long o = ((long long)hi << 32) | (unsigned int)lo;
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+// one workgroup per cell: the cell's keypoints counted, then k rounds of
+// arg-max over the raster list.  key = response << 32 | (INT_MAX - index), so
+// the larger key is the larger response and, among equals, the earlier
+// keypoint; round r takes the largest key below round r - 1's.
+__global__ void __launch_bounds__(256) k_grid_select(GridArgs a) {
+    __shared__ long long s_key[4];
+    __shared__ int s_cnt[4];
+    const int cell = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = min(*a.total, a.cap);
+    auto in_cell = [&](int i) -> bool {
+        const int x = (int)a.xy[2 * i], y = (int)a.xy[2 * i + 1];
+        return (y / a.gh) * a.grid_col + x / a.gw == cell;
+    };
+    int cnt = 0;
+    for (int i = tid; i < n; i += 256) cnt += in_cell(i) ? 1 : 0;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m, 64);
+    if (lane == 0) s_cnt[wave] = cnt;
+    __syncthreads();
+    if (tid == 0) a.cell_count[cell] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    long long prev = 0x7fffffffffffffffLL;
+    for (int r = 0; r < a.k; ++r) {
+        long long best = -1;
+        for (int i = tid; i < n; i += 256) {
+            if (!in_cell(i)) continue;
+            const long long key = ((long long)(int)a.resp[i] << 32) | (long long)(0x7fffffff - i);
+            if (key < prev && key > best) best = key;
+        }
+        best = wave_max64(best);
+        __syncthreads();   // s_key may still be read by the round before
+        if (lane == 0) s_key[wave] = best;
+        __syncthreads();
+        best = max(max(s_key[0], s_key[1]), max(s_key[2], s_key[3]));
+        if (best < 0) break;   // the same in every thread
+        if (tid == 0) {
+            const int idx = 0x7fffffff - (int)(best & 0xffffffffLL);
+            const size_t o = (size_t)cell * a.k + r;
+            a.out_xy[2 * o] = a.xy[2 * idx];
+            a.out_xy[2 * o + 1] = a.xy[2 * idx + 1];
+            a.out_resp[o] = a.resp[idx];
+        }
+        prev = best;
+    }
+}
+
 }  // namespace
 
 // ================================================================ C-ABI ====
@@ -699,8 +890,9 @@ struct mfe_ctx {
     float* pts = nullptr;  // [2][max_points][2]
     uint8_t* st = nullptr;
     double* dpts = nullptr;   // [2][max_points][2]
-    // mfe_two_point_ransac: one device block (inputs | work | outputs) and one pinned
-    // host block (inputs | outputs), grown to the largest call seen
+    // mfe_two_point_ransac, mfe_stereo_match, mfe_fast_grid: one device block (inputs |
+    // work | outputs) and one pinned host block (inputs | outputs), grown to the largest
+    // call seen
     unsigned char* rs_dev = nullptr;
     unsigned char* rs_host = nullptr;
     size_t rs_dev_cap = 0, rs_host_cap = 0;
@@ -716,6 +908,24 @@ int dev_alloc(mfe_ctx* c, void** p, size_t bytes) {
 
 int check_n(mfe_ctx* c, int n) {
     if (n < 0 || n > c->max_points) MFE_FAIL(-1, "n = %d outside [0, %d]", n, c->max_points);
+    return 0;
+}
+
+int grow_scratch(mfe_ctx* c, size_t dev_bytes, size_t host_bytes) {
+    if (dev_bytes > c->rs_dev_cap) {   // nothing is in flight: every call ends with a synchronisation
+        if (c->rs_dev) (void)hipFree(c->rs_dev);
+        c->rs_dev = nullptr;
+        c->rs_dev_cap = 0;
+        MFE_HIP(hipMalloc((void**)&c->rs_dev, dev_bytes));
+        c->rs_dev_cap = dev_bytes;
+    }
+    if (host_bytes > c->rs_host_cap) {
+        if (c->rs_host) (void)hipHostFree(c->rs_host);
+        c->rs_host = nullptr;
+        c->rs_host_cap = 0;
+        MFE_HIP(hipHostMalloc((void**)&c->rs_host, host_bytes, hipHostMallocDefault));
+        c->rs_host_cap = host_bytes;
+    }
     return 0;
 }
 
@@ -944,20 +1154,7 @@ int mfe_two_point_ransac(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const
                  o_draw = o_model + 4 * S, in_bytes = (o_draw + 8 * S * H + 7) & ~(size_t)7;
     const size_t o_work = in_bytes, o_info = o_work + 32 * T, o_inl = o_info + 8 * MFE_RANSAC_INFO_LEN * S,
                  out_bytes = 8 * MFE_RANSAC_INFO_LEN * S + T, dev_bytes = o_inl + T;
-    if (dev_bytes > c->rs_dev_cap) {   // nothing is in flight: every call ends with a synchronisation
-        if (c->rs_dev) (void)hipFree(c->rs_dev);
-        c->rs_dev = nullptr;
-        c->rs_dev_cap = 0;
-        MFE_HIP(hipMalloc((void**)&c->rs_dev, dev_bytes));
-        c->rs_dev_cap = dev_bytes;
-    }
-    if (in_bytes + out_bytes > c->rs_host_cap) {
-        if (c->rs_host) (void)hipHostFree(c->rs_host);
-        c->rs_host = nullptr;
-        c->rs_host_cap = 0;
-        MFE_HIP(hipHostMalloc((void**)&c->rs_host, in_bytes + out_bytes, hipHostMallocDefault));
-        c->rs_host_cap = in_bytes + out_bytes;
-    }
+    if (int rc = grow_scratch(c, dev_bytes, in_bytes + out_bytes)) return rc;
     unsigned char *hin = c->rs_host, *hout = c->rs_host + in_bytes, *d = c->rs_dev;
     memcpy(hin + o_prev, pts_prev, 16 * T);
     memcpy(hin + o_curr, pts_curr, 16 * T);
@@ -988,6 +1185,118 @@ int mfe_two_point_ransac(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const
     MFE_HIP(hipStreamSynchronize(st));
     memcpy(info_out, hout, 8 * MFE_RANSAC_INFO_LEN * S);
     memcpy(inlier_out, hout + 8 * MFE_RANSAC_INFO_LEN * S, T);
+    return 0;
+}
+
+int mfe_stereo_match(mfe_ctx_t* c, int slot_cam0, int slot_cam1, int n, const double* cam0_pts,
+                     const double* intrinsics0, int model0, const double* coeffs0, const double* intrinsics1,
+                     int model1, const double* coeffs1, const double* R_guess, const double* E, int win,
+                     int max_level, int max_iter, double eps, double stereo_threshold, float* cam1_pts,
+                     uint8_t* inlier, uint8_t* reason) {
+    if (!c) MFE_FAIL(-1, "null context");
+    if (check_n(c, n)) return -1;
+    if (n == 0) return 0;
+    if (!cam0_pts || !cam1_pts || !inlier || !reason) MFE_FAIL(-1, "null point array");
+    if (!intrinsics0 || !coeffs0 || !intrinsics1 || !coeffs1 || !R_guess || !E) MFE_FAIL(-1, "null camera argument");
+    if ((model0 != MFE_RADTAN && model0 != MFE_EQUIDISTANT) || (model1 != MFE_RADTAN && model1 != MFE_EQUIDISTANT))
+        MFE_FAIL(-1, "unknown distortion model %d / %d", model0, model1);
+    if (slot_cam0 < 0 || slot_cam0 >= c->nslot || slot_cam1 < 0 || slot_cam1 >= c->nslot) MFE_FAIL(-1, "bad slot");
+    if (win < 3 || win * win > 64 * LK_SLOTS) MFE_FAIL(-1, "window %d outside [3, 16]", win);
+    if (max_level < 0 || max_level > c->max_level) MFE_FAIL(-1, "max_level %d outside [0, %d]", max_level, c->max_level);
+    if (max_iter < 1) MFE_FAIL(-1, "max_iter must be positive");
+    MFE_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t N = (size_t)n, in_bytes = 16 * N, o_c1 = in_bytes, o_inl = o_c1 + 8 * N, o_rsn = o_inl + N,
+                 out_bytes = 10 * N;
+    if (int rc = grow_scratch(c, in_bytes + out_bytes, in_bytes + out_bytes)) return rc;
+    unsigned char *hin = c->rs_host, *hout = c->rs_host + in_bytes, *d = c->rs_dev;
+    memcpy(hin, cam0_pts, in_bytes);
+    MFE_HIP(hipMemcpyAsync(d, hin, in_bytes, hipMemcpyHostToDevice, s));
+    StereoArgs a;
+    a.cam0 = make_model(intrinsics0, model0, coeffs0, R_guess, nullptr);
+    a.cam1 = make_model(intrinsics1, model1, coeffs1, nullptr, nullptr);
+    for (int i = 0; i < 9; ++i) a.E[i] = E[i];
+    a.eps = eps;
+    a.epi_thr = stereo_threshold * (4.0 / (intrinsics0[0] + intrinsics0[1] + intrinsics1[0] + intrinsics1[1]));
+    a.pts = (const double*)d;
+    a.cam1_pts = (float*)(d + o_c1);
+    a.inlier = d + o_inl;
+    a.reason = d + o_rsn;
+    a.n = n; a.win = win; a.max_level = max_level; a.max_iter = max_iter;
+    hipLaunchKernelGGL(k_stereo_match, dim3(n), dim3(64), 0, s, c->slots[slot_cam0], c->slots[slot_cam1], a);
+    MFE_HIP(hipGetLastError());
+    MFE_HIP(hipMemcpyAsync(hout, d + o_c1, out_bytes, hipMemcpyDeviceToHost, s));
+    MFE_HIP(hipStreamSynchronize(s));
+    memcpy(cam1_pts, hout, 8 * N);
+    memcpy(inlier, hout + 8 * N, N);
+    memcpy(reason, hout + 9 * N, N);
+    return 0;
+}
+
+int mfe_fast_grid(mfe_ctx_t* c, int slot, int threshold, int n_occ, const float* occupied, int grid_row,
+                  int grid_col, int k, int max_kp, float* xy_out, float* response_out, int32_t* cell_count,
+                  int* n_total) {
+    if (!c || !xy_out || !response_out || !cell_count || !n_total) MFE_FAIL(-1, "null argument");
+    if (slot < 0 || slot >= c->nslot) MFE_FAIL(-1, "slot %d outside [0, %d)", slot, c->nslot);
+    if (check_n(c, n_occ)) return -1;
+    if (n_occ > 0 && !occupied) MFE_FAIL(-1, "null occupied points");
+    if (c->W < 16 || c->H < 16) MFE_FAIL(-1, "image %dx%d is smaller than 16x16", c->W, c->H);
+    if (k < 1 || k > MFE_GRID_MAX_K) MFE_FAIL(-1, "k = %d outside [1, %d]", k, MFE_GRID_MAX_K);
+    if (grid_row < 1 || grid_col < 1 || (long long)grid_row * grid_col > MFE_GRID_MAX_CELLS)
+        MFE_FAIL(-1, "grid %dx%d outside [1, %d] cells", grid_row, grid_col, MFE_GRID_MAX_CELLS);
+    if (max_kp < 1 || max_kp > c->kp_cap) MFE_FAIL(-1, "max_kp = %d outside [1, %d]", max_kp, c->kp_cap);
+    MFE_HIP(hipSetDevice(c->device));
+    threshold = threshold < 0 ? 0 : (threshold > 255 ? 255 : threshold);
+    const Level& L = c->slots[slot].lv[0];
+    hipStream_t s = c->stream;
+    const int W = L.w, H = L.h;
+    const size_t cells = (size_t)grid_row * grid_col, K = (size_t)k;
+    // device block: occupied | total, pad | cell_count | response | xy; the part after occupied comes back
+    const size_t in_bytes = (8 * (size_t)n_occ + 15) & ~(size_t)15, o_cnt = 8, o_resp = o_cnt + 4 * cells,
+                 o_xy = o_resp + 4 * cells * K, out_bytes = o_xy + 8 * cells * K;
+    if (int rc = grow_scratch(c, in_bytes + out_bytes, in_bytes + out_bytes)) return rc;
+    unsigned char *hin = c->rs_host, *hout = c->rs_host + in_bytes, *d = c->rs_dev, *dout = c->rs_dev + in_bytes;
+    MFE_HIP(hipMemsetAsync(c->mask, 1, (size_t)W * H, s));
+    if (n_occ > 0) {
+        memcpy(hin, occupied, 8 * (size_t)n_occ);
+        MFE_HIP(hipMemcpyAsync(d, hin, 8 * (size_t)n_occ, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_mask_clear, dim3((7 * n_occ + 255) / 256), dim3(256), 0, s, (const float*)d, n_occ,
+                           c->mask, W, H);
+    }
+    float* kxy = c->kp;
+    float* kresp = c->kp + 2 * (size_t)c->kp_cap;
+    hipLaunchKernelGGL(k_fast, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, s, L.img, W, H, threshold, c->score);
+    hipLaunchKernelGGL(k_fast_rows, dim3((H + 3) / 4), dim3(256), 0, s, c->score, c->mask, W, H, 0, c->rows,
+                       (const int*)nullptr, 0, (float*)nullptr, (float*)nullptr);
+    hipLaunchKernelGGL(k_row_scan, dim3(1), dim3(256), 0, s, (const int*)c->rows, c->rows + H, H, (int*)dout);
+    hipLaunchKernelGGL(k_fast_rows, dim3((H + 3) / 4), dim3(256), 0, s, c->score, c->mask, W, H, 1, c->rows,
+                       (const int*)(c->rows + H), max_kp, kxy, kresp);
+    GridArgs a;
+    a.xy = kxy; a.resp = kresp; a.total = (const int*)dout;
+    a.out_xy = (float*)(dout + o_xy); a.out_resp = (float*)(dout + o_resp); a.cell_count = (int*)(dout + o_cnt);
+    a.cap = max_kp; a.gh = (H + grid_row - 1) / grid_row; a.gw = (W + grid_col - 1) / grid_col;
+    a.grid_col = grid_col; a.k = k;
+    hipLaunchKernelGGL(k_grid_select, dim3((unsigned)cells), dim3(256), 0, s, a);
+    MFE_HIP(hipGetLastError());
+    MFE_HIP(hipMemcpyAsync(hout, dout, out_bytes, hipMemcpyDeviceToHost, s));
+    MFE_HIP(hipStreamSynchronize(s));
+    int tot;
+    memcpy(&tot, hout, sizeof(int));
+    *n_total = tot;
+    if (tot > max_kp) MFE_FAIL(-3, "%d keypoints exceed the capacity of %d", tot, max_kp);
+    const int32_t* cnt = (const int32_t*)(hout + o_cnt);
+    const float* resp = (const float*)(hout + o_resp);
+    const float* xy = (const float*)(hout + o_xy);
+    size_t w = 0;
+    for (size_t cell = 0; cell < cells; ++cell) {
+        cell_count[cell] = cnt[cell];
+        const size_t kept = std::min((size_t)cnt[cell], K);
+        for (size_t r = 0; r < kept; ++r, ++w) {
+            xy_out[2 * w] = xy[2 * (cell * K + r)];
+            xy_out[2 * w + 1] = xy[2 * (cell * K + r) + 1];
+            response_out[w] = resp[cell * K + r];
+        }
+    }
     return 0;
 }
 

@@ -14,6 +14,9 @@ published message -- and every image operator runs in the HIP kernels of
   projectPoints / fisheye (image.py:676-702)    mfe_distort
   RANSAC stub (image.py:292-293)                mfe_two_point_ransac (k_two_point_ransac,
                                                 include/msckf_ransac.h), opt-in
+  stereo_match (image.py:554-638)               mfe_stereo_match (k_stereo_match,
+                                                include/msckf_pipeline.h), opt-in
+  mask + detect + sieve (image.py:317-360)      mfe_fast_grid (include/msckf_pipeline.h), opt-in
 
 cv2 is absent here and on the GPU box: the kernels restate the published
 OpenCV 4.x algorithms (oracle/frontend_oracle.py), parity unpinned against cv2
@@ -26,7 +29,11 @@ the two-point RANSAC the stub stands for (Sun et al., msckf_vio) in its place:
 one device call per frame over the cam0 and cam1 temporal matches with the
 IMU-predicted rotations, ``ransac_threshold`` its inlier error in pixels, the
 hypothesis draws from a seeded generator (``ransac_seed``) so that a replay
-repeats.  There is no CPU fallback: without the HIP library or a GPU the
+repeats.  ``FrontendConfig.device_pipeline = True`` makes ``stereo_match`` one
+device call instead of six and the mask, detection and per-cell sieve of
+``add_new_features`` one call instead of a host mask, ``mfe_fast`` and a Python
+loop over every keypoint; the published messages are the same.  There is no
+CPU fallback: without the HIP library or a GPU the
 constructor raises.
 """
 from __future__ import annotations
@@ -107,6 +114,10 @@ class FrontendConfig:
     ransac_enabled: bool = False
     ransac_success_probability: float = 0.99
     ransac_seed: int = 0
+    # not in the reference: stereo_match and the detection + sieve of add_new_features each as
+    # one device call (include/msckf_pipeline.h) instead of Python around many small ones;
+    # the published messages are the same
+    device_pipeline: bool = False
 
     @property
     def grid_num(self):
@@ -279,6 +290,61 @@ class Frontend:
             draws.ctypes.data_as(C.POINTER(C.c_uint32)), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
             info.ctypes.data_as(dp)))
         return [(inl[off[s]:off[s + 1]].astype(bool), RansacInfo.from_row(info[s])) for s in range(S)]
+
+    def stereo_match(self, slot_cam0, slot_cam1, cam0_pts, cam0, cam1, R_guess, E, stereo_threshold,
+                     win=15, max_level=3, max_iter=30, eps=0.01):
+        """mfe_stereo_match (include/msckf_pipeline.h): ImageProcessor.stereo_match
+        in one device call.  ``cam0`` / ``cam1``: (intrinsics, model, coeffs);
+        ``R_guess``: the rotation of the initial guess; ``E``: the essential
+        matrix.  Returns (cam1_pts float32 (n, 2), inlier uint8, reason uint8);
+        the forward LK status is ``reason != 1``."""
+        p = np.ascontiguousarray(np.asarray(cam0_pts, float).reshape(-1, 2))
+        n = len(p)
+        c1 = np.zeros((n, 2), np.float32)
+        inl, rsn = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        if n == 0:
+            return c1, inl, rsn
+        if n > self.max_points:
+            raise ValueError("%d points exceed the context's %d" % (n, self.max_points))
+        f64 = lambda a, m: np.ascontiguousarray(np.asarray(a, float).ravel()[:m])
+        dp, u8 = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        K0, k0, K1, k1 = f64(cam0[0], 4), f64(cam0[2], 4), f64(cam1[0], 4), f64(cam1[2], 4)
+        R, Em = f64(R_guess, 9), f64(E, 9)
+        if min(len(K0), len(k0), len(K1), len(k1)) < 4 or len(R) < 9 or len(Em) < 9:
+            raise ValueError("camera arguments: 4 intrinsics, 4 coefficients, 3x3 R_guess and E")
+        self._check(self.lib.mfe_stereo_match(
+            self.h, int(slot_cam0), int(slot_cam1), n, p.ctypes.data_as(dp), K0.ctypes.data_as(dp), int(cam0[1]),
+            k0.ctypes.data_as(dp), K1.ctypes.data_as(dp), int(cam1[1]), k1.ctypes.data_as(dp), R.ctypes.data_as(dp),
+            Em.ctypes.data_as(dp), int(win), int(max_level), int(max_iter), float(eps), float(stereo_threshold),
+            c1.ctypes.data_as(C.POINTER(C.c_float)), inl.ctypes.data_as(u8), rsn.ctypes.data_as(u8)))
+        return c1, inl, rsn
+
+    def fast_grid(self, slot, threshold, occupied, grid_row, grid_col, k, max_kp=1 << 16):
+        """mfe_fast_grid (include/msckf_pipeline.h): masked FAST detection and the
+        per-cell selection in one device call.  ``occupied``: float32 xy of the
+        points whose 7 x 7 neighbourhoods are masked out.  Returns (xy float32
+        (m, 2), response float32 (m,), cell_count int32 (grid_row * grid_col,),
+        n_total): the kept keypoints grouped by cell, response-descending with
+        raster ties; raises if n_total exceeds ``max_kp``."""
+        occ = np.ascontiguousarray(np.asarray(occupied, np.float32).reshape(-1, 2))
+        if len(occ) > self.max_points:
+            raise ValueError("%d points exceed the context's %d" % (len(occ), self.max_points))
+        cells = int(grid_row) * int(grid_col)
+        if not (1 <= int(k) <= _lib.GRID_MAX_K and int(grid_row) >= 1 and int(grid_col) >= 1 and
+                cells <= _lib.GRID_MAX_CELLS):
+            raise ValueError("grid %dx%d, k = %d outside the limits of msckf_pipeline.h" % (grid_row, grid_col, k))
+        xy = np.zeros((cells * int(k), 2), np.float32)
+        resp = np.zeros(cells * int(k), np.float32)
+        cnt = np.zeros(cells, np.int32)
+        n = C.c_int(0)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.mfe_fast_grid(self.h, int(slot), int(threshold), len(occ),
+                                           occ.ctypes.data_as(fp) if len(occ) else None, int(grid_row),
+                                           int(grid_col), int(k), int(max_kp), xy.ctypes.data_as(fp),
+                                           resp.ctypes.data_as(fp), cnt.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           C.byref(n)))
+        m = int(np.minimum(cnt, int(k)).sum())
+        return xy[:m].copy(), resp[:m].copy(), cnt, n.value
 
 
 def _model(name):
@@ -461,6 +527,8 @@ class ImageProcessor:
 
     def add_new_features(self):
         """image.py:317-390."""
+        if self.config.device_pipeline:
+            return self._add_new_features_device()
         img = self.cam0_curr_img_msg.image
         gh, gw = self.get_grid_size(img)
         mask = np.ones(img.shape[:2], dtype=np.uint8)
@@ -539,6 +607,8 @@ class ImageProcessor:
         """image.py:554-638: project into cam1 through the extrinsics, LK
         cam0 -> cam1 and back, and the vertical-disparity, round-trip and
         epipolar tests."""
+        if self.config.device_pipeline:
+            return self._stereo_match_device(cam0_points)
         cam0_points = np.asarray(cam0_points, float).reshape(-1, 2)
         if len(cam0_points) == 0:
             return [], []
@@ -576,6 +646,35 @@ class ImageProcessor:
             if error > self.config.stereo_threshold * norm_pixel_unit:
                 inliers[i] = False
         return [tuple(p) for p in c1], list(inliers)
+
+    def _stereo_match_device(self, cam0_points):
+        """stereo_match as the one call mfe_stereo_match.  The equidistant
+        quirk of undistort_points (no rectification) is kept by passing the
+        identity as the rotation of the initial guess."""
+        cam0_points = np.asarray(cam0_points, float).reshape(-1, 2)
+        if len(cam0_points) == 0:
+            return [], []
+        R_cam0_cam1 = self.R_cam1_imu.T @ self.R_cam0_imu
+        t_cam0_cam1 = self.R_cam1_imu.T @ (self.t_cam0_imu - self.t_cam1_imu)
+        E = _skew(t_cam0_cam1) @ R_cam0_cam1
+        model0 = _model(self.cam0_distortion_model)
+        c1, inliers, _ = self.fe.stereo_match(
+            self._slot_c0, self._slot_c1, cam0_points,
+            (self.cam0_intrinsics, model0, self.cam0_distortion_coeffs),
+            (self.cam1_intrinsics, _model(self.cam1_distortion_model), self.cam1_distortion_coeffs),
+            np.identity(3) if model0 == EQUIDISTANT else R_cam0_cam1, E, self.config.stereo_threshold, **self.lk_kw)
+        return [tuple(p) for p in c1], list(inliers.astype(bool))
+
+    def _add_new_features_device(self):
+        """add_new_features with the mask, the detection and the per-cell sieve
+        as the one call mfe_fast_grid.  A cell comes back response-descending
+        with raster ties where the sieve leaves a cell of at most
+        grid_max_feature_num in raster order; _collect_new sorts every cell by
+        response with a stable sort, so the features and their ids are the same."""
+        occ = np.array([f.cam0_point for f in chain.from_iterable(self.curr_features)], np.float32).reshape(-1, 2)
+        xy, resp, _, _ = self.fe.fast_grid(self._slot_c0, self.config.fast_threshold, occ, self.config.grid_row,
+                                           self.config.grid_col, self.config.grid_max_feature_num)
+        self._collect_new([tuple(p) for p in xy], list(resp))
 
     def undistort_points(self, pts_in, intrinsics, distortion_model, distortion_coeffs,
                          rectification_matrix=np.identity(3), new_intrinsics=np.array([1, 1, 0, 0])):
