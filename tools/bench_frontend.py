@@ -15,9 +15,19 @@ it publishes the same messages, and adds to the JSON line its frames/s next to
 the default path's and the wall time of one ImageProcessor.stereo_match at 200
 points as the one call and as the composed six.
 
-    python tools/bench_frontend.py [--frames 60] [--device-pipeline]
+--lanes S runs S streams (distinct textures and motions) instead and prints its
+own JSON line: (a) S ImageProcessor(device_pipeline=True) one after another,
+frame by frame, against (b) one MultiImageProcessor (include/msckf_lanes.h:
+one device call per stage for all lanes); the messages must be identical lane
+by lane.  Lane-frames/s of both as the means of two alternated runs, the
+device calls per step of each, and a cProfile split of (b)'s host time (a
+further, untimed run).
+
+    python tools/bench_frontend.py [--frames 60] [--device-pipeline] [--lanes S]
 """
 import argparse
+import cProfile
+import pstats
 import json
 import os
 import sys
@@ -89,9 +99,119 @@ def stereo_leg(ip, c0, c1, pts, reps=30):
     return round(float(np.median(ms)), 3)
 
 
+def lane_streams(S, n, W, H):
+    """S streams of n rendered stereo pairs: texture seed, motion and disparity
+    differ per lane.  As in the single stream the motion starts over every 40
+    frames, so 40 pairs per lane are rendered."""
+    streams = []
+    for i in range(S):
+        f = fs.texture_fn(4 + i, W=W, H=H)
+        vx, vy, disp = 1.5 - 0.25 * (i % 5), -0.5 + 0.2 * (i % 4), 12.0 - 0.5 * (i % 3)
+        pairs = [(fs.render(f, W, H, vx * k, vy * k), fs.render(f, W, H, vx * k - disp, vy * k))
+                 for k in range(min(n, 40))]
+        streams.append([pairs[k % 40] for k in range(n)])
+    return streams
+
+
+def lane_messages(k, streams):
+    t = 0.05 * k
+    imu = [ImuMsg(t - 0.05 + 0.005 * j, np.zeros(3), np.array([0.0, 0.0, 9.81])) for j in range(10)]
+    return imu, [StereoMsg(t, c0, c1, ImgMsg(t, c0), ImgMsg(t, c1)) for c0, c1 in (st[k] for st in streams)]
+
+
+def run_singles(cfg, streams):
+    """(a): (lane-frames/s from step 2 on, messages per lane, device calls per step)."""
+    S, n = len(streams), len(streams[0])
+    ips = [fe_mod.ImageProcessor(fe_mod.FrontendConfig(**vars(cfg))) for _ in range(S)]
+    calls = [0]
+    for ip in ips:
+        def serve(req, inner=ip._serve):
+            calls[0] += (len(req[1]) if req[0] == "upload" else
+                         sum(1 for a in req[1] if len(a[0])) if req[0] == "undistort" else 1)
+            return inner(req)
+        ip._serve = serve
+    msgs = [[] for _ in range(S)]
+    for k in range(n):
+        imu, stereo = lane_messages(k, streams)
+        if k == 2:
+            t0, c0 = time.perf_counter(), calls[0]
+        for i, ip in enumerate(ips):
+            for m in imu:
+                ip.imu_callback(m)
+            msgs[i].append(ip.stareo_callback(stereo[i]))
+    el = time.perf_counter() - t0
+    for ip in ips:
+        ip.fe.close()
+    return S * (n - 2) / el, msgs, (calls[0] - c0) / (n - 2)
+
+
+def run_multi(cfg, streams, profile=None):
+    """(b): the same through one MultiImageProcessor."""
+    S, n = len(streams), len(streams[0])
+    mp = fe_mod.MultiImageProcessor(S, config=cfg)
+    msgs = [[] for _ in range(S)]
+    for k in range(n):
+        imu, stereo = lane_messages(k, streams)
+        if k == 2:
+            t0, c0 = time.perf_counter(), sum(mp.launches.values())
+            if profile:
+                profile.enable()
+        for i in range(S):
+            for m in imu:
+                mp.imu_callback(i, m)
+        out = mp.stereo_callbacks(dict(enumerate(stereo)))
+        for i in range(S):
+            msgs[i].append(out[i])
+    if profile:
+        profile.disable()
+    el = time.perf_counter() - t0
+    calls = (sum(mp.launches.values()) - c0) / (n - 2)
+    mp.close()
+    return S * (n - 2) / el, msgs, calls
+
+
+def profile_split(prof):
+    """Cumulative seconds of (b)'s steps by where they go: each set call of
+    Frontend (packing, the device call, unpacking), the lanes' generators
+    between requests (per-feature Python) and the rest of stereo_callbacks."""
+    st = pstats.Stats(prof).stats
+    cum = lambda name: sum(v[3] for (f, _, fn), v in st.items() if fn == name and f.endswith("frontend.py"))
+    total = cum("stereo_callbacks")
+    dev = {k: round(cum(k), 4) for k in ("upload_many", "lk_sets", "stereo_match_sets", "two_point_ransac",
+                                         "fast_grid_sets", "undistort_sets")}
+    adv = cum("_advance")
+    return {"stereo_callbacks_s": round(total, 4), "set_calls_s": dev, "set_calls_total_s": round(sum(dev.values()), 4),
+            "lane_generators_s": round(adv, 4), "scheduling_rest_s": round(total - adv - sum(dev.values()), 4)}
+
+
+def lanes_main(a, cfg, W, H):
+    cfg = fe_mod.FrontendConfig(**{**vars(cfg), "device_pipeline": True})
+    streams = lane_streams(a.lanes, a.frames, W, H)       # rendered up front: not part of the timing
+    fa, msgs_a, calls_a = run_singles(cfg, streams)
+    fb, msgs_b, calls_b = run_multi(cfg, streams)
+    for i, (ma, mb) in enumerate(zip(msgs_a, msgs_b)):
+        if ma != mb:
+            raise SystemExit("lane %d: MultiImageProcessor published different messages" % i)
+    fa = 0.5 * (fa + run_singles(cfg, streams)[0])        # a, b, a, b: the means of two runs each
+    fb = 0.5 * (fb + run_multi(cfg, streams)[0])
+    prof = cProfile.Profile()
+    run_multi(cfg, streams, profile=prof)
+    nfeat = float(np.mean([len(m.vio_features) for lane in msgs_b for m in lane]))
+    print(json.dumps({"component": "stereo front-end (image.py) on GPU, lanes", "resolution": [W, H],
+                      "lanes": a.lanes, "frames_per_lane": a.frames, "messages_identical": True,
+                      "lane_frames_per_s": {"single_processors": round(fa, 1), "multi_image_processor": round(fb, 1)},
+                      "device_calls_per_step": {"single_processors": round(calls_a, 2),
+                                                "multi_image_processor": round(calls_b, 2)},
+                      "features_per_frame": nfeat, "multi_host_profile": profile_split(prof),
+                      "note": "timed from step 2 on; the profile is a separate run under cProfile, which slows "
+                              "the host: read it as shares, not as times"}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=60)
+    ap.add_argument("--lanes", type=int, default=0,
+                    help="run this many streams through single processors and through MultiImageProcessor")
     ap.add_argument("--device-pipeline", action="store_true",
                     help="also run the stream with FrontendConfig.device_pipeline on")
     a = ap.parse_args()
@@ -102,6 +222,8 @@ def main():
     Ti1[0, 3] = -0.11
     cfg = fe_mod.FrontendConfig(T_imu_cam0=np.eye(4), T_imu_cam1=Ti1, cam0_distortion_coeffs=np.zeros(4),
                                 cam1_distortion_coeffs=np.zeros(4), cam0_intrinsics=K, cam1_intrinsics=K)
+    if a.lanes:
+        return lanes_main(a, cfg, W, H)
     frames = []
     for k in range(a.frames):   # rendered up front: not part of the timing
         dx, dy = 1.5 * (k % 40), -0.5 * (k % 40)

@@ -119,6 +119,20 @@ FRONTEND_PIPELINE_SIGS = {
 }
 FRONTEND_PIPELINE_EXPORTED = tuple(FRONTEND_PIPELINE_SIGS)
 
+# the front-end's calls over many streams' sets (include/msckf_lanes.h), same library and context
+MAX_SLOTS = 96
+MAX_SETS = 1024
+FRONTEND_LANES_SIGS = {
+    "mfe_upload_many": (C.c_int, [_P, C.c_int, _I, _U8]),
+    "mfe_lk_sets": (C.c_int, [_P, C.c_int, _I, _I, _I, _F, _F, _U8, C.c_int, C.c_int, C.c_int, C.c_double]),
+    "mfe_stereo_match_sets": (C.c_int, [_P, C.c_int, _I, _I, _I, _D, _D, _I, _D, _D, _I, _D, _D, _D, _D,
+                                        C.c_int, C.c_int, C.c_int, C.c_double, _F, _U8, _U8]),
+    "mfe_fast_grid_sets": (C.c_int, [_P, C.c_int, _I, _I, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _F,
+                                     _I, _I]),
+    "mfe_undistort_sets": (C.c_int, [_P, C.c_int, _I, _D, _D, _D, _I, _D, _D, _D]),
+}
+FRONTEND_LANES_EXPORTED = tuple(FRONTEND_LANES_SIGS)
+
 # multi-GPU replica transport, RCCL (include/msckf_replicas.h), same library
 REPLICA_SIGS = {
     "msckf_rccl_unique_id": (C.c_int, [_U8]),
@@ -146,6 +160,7 @@ def load_library(path: str = LIB_PATH):
         lib = C.CDLL(path)
         for name, (res, args) in (list(_SIGS.items()) + list(FRONTEND_SIGS.items()) +
                                   list(FRONTEND_RANSAC_SIGS.items()) + list(FRONTEND_PIPELINE_SIGS.items()) +
+                                  list(FRONTEND_LANES_SIGS.items()) +
                                   list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "../../include/msckf_frontend.h"
+#include "../../include/msckf_lanes.h"
 #include "../../include/msckf_pipeline.h"
 #include "../../include/msckf_ransac.h"
 
@@ -89,9 +90,13 @@ __device__ __forceinline__ int refl101(int i, int n) {   // BORDER_REFLECT_101
 __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 
 // ---------------------------------------------------------------- pyramid --
-__global__ void __launch_bounds__(256) k_pyrdown(const uint8_t* __restrict__ src, int sw, int sh,
-                                                 uint8_t* __restrict__ dst, int dw, int dh) {
-    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+// The kernels below come in two forms around one body each: the single-image form
+// of msckf_frontend.h / msckf_pipeline.h with its arguments in the kernel arguments,
+// and the set form of msckf_lanes.h (k_*_sets), which takes the set index from the
+// grid or from a per-point index and reads the slots' Pyr descriptors and the
+// per-set arguments from device tables.
+__device__ __forceinline__ void pyrdown_px(const uint8_t* __restrict__ src, int sw, int sh,
+                                           uint8_t* __restrict__ dst, int dw, int dh, int x, int y) {
     if (x >= dw || y >= dh) return;
     const int k[5] = {1, 4, 6, 4, 1};
     int cols[5];
@@ -109,9 +114,22 @@ __global__ void __launch_bounds__(256) k_pyrdown(const uint8_t* __restrict__ src
     dst[(size_t)y * dw + x] = (uint8_t)((s + 128) >> 8);
 }
 
-__global__ void __launch_bounds__(256) k_scharr(const uint8_t* __restrict__ img, int w, int h,
-                                                int16_t* __restrict__ ix, int16_t* __restrict__ iy) {
-    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+__global__ void __launch_bounds__(256) k_pyrdown(const uint8_t* __restrict__ src, int sw, int sh,
+                                                 uint8_t* __restrict__ dst, int dw, int dh) {
+    pyrdown_px(src, sw, sh, dst, dw, dh, blockIdx.x * 16 + (threadIdx.x & 15), blockIdx.y * 16 + (threadIdx.x >> 4));
+}
+
+// blockIdx.z = the image of the call; its slot's level - 1 -> level
+__global__ void __launch_bounds__(256) k_pyrdown_sets(const Pyr* __restrict__ tab, const int32_t* __restrict__ slots,
+                                                      int level) {
+    const Pyr& P = tab[slots[blockIdx.z]];
+    const Level U = P.lv[level - 1], L = P.lv[level];
+    pyrdown_px(U.img, U.w, U.h, L.img, L.w, L.h, blockIdx.x * 16 + (threadIdx.x & 15),
+               blockIdx.y * 16 + (threadIdx.x >> 4));
+}
+
+__device__ __forceinline__ void scharr_px(const uint8_t* __restrict__ img, int w, int h, int16_t* __restrict__ ix,
+                                          int16_t* __restrict__ iy, int x, int y) {
     if (x >= w || y >= h) return;
     const int xm = refl101(x - 1, w), xp = refl101(x + 1, w);
     const uint8_t* rm = img + (size_t)refl101(y - 1, h) * w;
@@ -121,6 +139,32 @@ __global__ void __launch_bounds__(256) k_scharr(const uint8_t* __restrict__ img,
     const int gy = 3 * (rp[xm] + rp[xp]) + 10 * rp[x] - (3 * (rm[xm] + rm[xp]) + 10 * rm[x]);
     ix[(size_t)y * w + x] = (int16_t)gx;
     iy[(size_t)y * w + x] = (int16_t)gy;
+}
+
+__global__ void __launch_bounds__(256) k_scharr(const uint8_t* __restrict__ img, int w, int h,
+                                                int16_t* __restrict__ ix, int16_t* __restrict__ iy) {
+    scharr_px(img, w, h, ix, iy, blockIdx.x * 16 + (threadIdx.x & 15), blockIdx.y * 16 + (threadIdx.x >> 4));
+}
+
+__global__ void __launch_bounds__(256) k_scharr_sets(const Pyr* __restrict__ tab, const int32_t* __restrict__ slots,
+                                                     int level) {
+    const Level L = tab[slots[blockIdx.z]].lv[level];
+    scharr_px(L.img, L.w, L.h, L.ix, L.iy, blockIdx.x * 16 + (threadIdx.x & 15), blockIdx.y * 16 + (threadIdx.x >> 4));
+}
+
+// mfe_upload_many: image blockIdx.z of the packed block -> level 0 of its slot;
+// 16 bytes per thread where the image size allows it, single bytes otherwise
+__global__ void __launch_bounds__(256) k_image_scatter_sets(const Pyr* __restrict__ tab,
+                                                            const int32_t* __restrict__ slots,
+                                                            const uint8_t* __restrict__ images, size_t bytes, int vec) {
+    const uint8_t* src = images + (size_t)blockIdx.z * bytes;
+    uint8_t* dst = tab[slots[blockIdx.z]].lv[0].img;
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (vec) {
+        if (16 * t < bytes) ((uint4*)dst)[t] = ((const uint4*)src)[t];
+    } else if (t < bytes) {
+        dst[t] = src[t];
+    }
 }
 
 // ------------------------------------------------------------------- FAST --
@@ -169,9 +213,8 @@ __device__ __forceinline__ bool run9(unsigned m) {
 
 // score map: 0x100 | score for corners, 0 elsewhere (the non-max test reads
 // non-corner neighbours as score 0, as fast.cpp's row buffers do)
-__global__ void __launch_bounds__(256) k_fast(const uint8_t* __restrict__ img, int w, int h, int threshold,
-                                              uint16_t* __restrict__ score) {
-    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+__device__ __forceinline__ void fast_px(const uint8_t* __restrict__ img, int w, int h, int threshold,
+                                        uint16_t* __restrict__ score, int x, int y) {
     if (x >= w || y >= h) return;
     uint16_t out = 0;
     if (x >= 3 && x < w - 3 && y >= 3 && y < h - 3) {
@@ -194,14 +237,25 @@ __global__ void __launch_bounds__(256) k_fast(const uint8_t* __restrict__ img, i
     score[(size_t)y * w + x] = out;
 }
 
+__global__ void __launch_bounds__(256) k_fast(const uint8_t* __restrict__ img, int w, int h, int threshold,
+                                              uint16_t* __restrict__ score) {
+    fast_px(img, w, h, threshold, score, blockIdx.x * 16 + (threadIdx.x & 15), blockIdx.y * 16 + (threadIdx.x >> 4));
+}
+
+// blockIdx.z = the set: level 0 of its slot -> the set's score map
+__global__ void __launch_bounds__(256) k_fast_sets(const Pyr* __restrict__ tab, const int32_t* __restrict__ slots,
+                                                   int threshold, uint16_t* __restrict__ score) {
+    const Level L = tab[slots[blockIdx.z]].lv[0];
+    fast_px(L.img, L.w, L.h, threshold, score + (size_t)blockIdx.z * L.w * L.h, blockIdx.x * 16 + (threadIdx.x & 15),
+            blockIdx.y * 16 + (threadIdx.x >> 4));
+}
+
 // one wave per row: corners whose score beats all 8 neighbours (and pass the
 // mask); pass 0 counts per row, pass 1 writes at row_off[y] + rank in raster order
-__global__ void __launch_bounds__(256) k_fast_rows(const uint16_t* __restrict__ score, const uint8_t* __restrict__ mask,
-                                                   int w, int h, int pass, int* __restrict__ row_count,
-                                                   const int* __restrict__ row_off, int max_kp,
-                                                   float* __restrict__ xy, float* __restrict__ resp) {
-    const int lane = threadIdx.x & 63;
-    const int y = blockIdx.x * 4 + (threadIdx.x >> 6);
+__device__ __forceinline__ void fast_rows_row(const uint16_t* __restrict__ score, const uint8_t* __restrict__ mask,
+                                              int w, int h, int pass, int* __restrict__ row_count,
+                                              const int* __restrict__ row_off, int max_kp, float* __restrict__ xy,
+                                              float* __restrict__ resp, int y, int lane) {
     if (y >= h) return;
     int count = 0;
     for (int x0 = 0; x0 < w; x0 += 64) {
@@ -232,6 +286,34 @@ __global__ void __launch_bounds__(256) k_fast_rows(const uint16_t* __restrict__ 
         count += __popcll(bal);
     }
     if (pass == 0 && lane == 0) row_count[y] = count;
+}
+
+__global__ void __launch_bounds__(256) k_fast_rows(const uint16_t* __restrict__ score, const uint8_t* __restrict__ mask,
+                                                   int w, int h, int pass, int* __restrict__ row_count,
+                                                   const int* __restrict__ row_off, int max_kp,
+                                                   float* __restrict__ xy, float* __restrict__ resp) {
+    fast_rows_row(score, mask, w, h, pass, row_count, row_off, max_kp, xy, resp, blockIdx.x * 4 + (threadIdx.x >> 6),
+                  threadIdx.x & 63);
+}
+
+// The per-set work areas of mfe_fast_grid_sets, set s at s times the single call's
+// extent: score and mask [w h], rows [2][h] (counts, offsets), kp [kp_cap][3] (xy,
+// then the responses).
+struct GridWork {
+    uint16_t* score;
+    uint8_t* mask;
+    int* rows;
+    float* kp;
+    int w, h, kp_cap;
+};
+
+// blockIdx.y = the set
+__global__ void __launch_bounds__(256) k_fast_rows_sets(GridWork g, int pass, int max_kp) {
+    const size_t s = blockIdx.y, px = (size_t)g.w * g.h;
+    int* rows = g.rows + s * 2 * g.h;
+    float* kp = g.kp + s * 3 * g.kp_cap;
+    fast_rows_row(g.score + s * px, g.mask + s * px, g.w, g.h, pass, rows, rows + g.h, max_kp, kp,
+                  kp + 2 * (size_t)g.kp_cap, blockIdx.x * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
 }
 
 // --------------------------------------------------------------------- LK --
@@ -391,6 +473,35 @@ __global__ void __launch_bounds__(64) k_lk(Pyr P, Pyr N, int n, const float* __r
     }
 }
 
+// mfe_lk_sets: the per-point set index is the same in every lane of the
+// wavefront, so the descriptors come through scalar loads
+struct LkSetsArgs {
+    const Pyr* tab;
+    const int32_t* pt_set;      // [n]
+    const int32_t* set_slots;   // [n_sets][2]: previous, next
+    const float* prev_pts;
+    float* next_pts;
+    uint8_t* status;
+    double eps;
+    int n, win, max_level, max_iter;
+};
+
+__global__ void __launch_bounds__(64) k_lk_sets(LkSetsArgs a) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= a.n) return;
+    const int s = __builtin_amdgcn_readfirstlane(a.pt_set[i]);
+    const Pyr& P = a.tab[a.set_slots[2 * s]];
+    const Pyr& N = a.tab[a.set_slots[2 * s + 1]];
+    float nx = a.next_pts[2 * i], ny = a.next_pts[2 * i + 1];
+    const bool st = lk_point(P, N, a.prev_pts[2 * i], a.prev_pts[2 * i + 1], nx, ny, a.win, a.max_level, a.max_iter,
+                             a.eps, lane);
+    if (lane == 0) {
+        a.next_pts[2 * i] = nx;
+        a.next_pts[2 * i + 1] = ny;
+        a.status[i] = st ? 1 : 0;
+    }
+}
+
 // ---------------------------------------------------------- camera models --
 struct CamModel {
     double fx, fy, cx, cy, k[4], R[9], nfx, nfy, ncx, ncy;
@@ -489,6 +600,18 @@ __global__ void __launch_bounds__(256) k_undistort(CamModel c, int n, const doub
     if (t >= n) return;
     double x, y;
     undistort_rect(c, in[2 * t], in[2 * t + 1], x, y);
+    out[2 * t] = x;
+    out[2 * t + 1] = y;
+}
+
+// mfe_undistort_sets: point t with the model of its set
+__global__ void __launch_bounds__(256) k_undistort_sets(const CamModel* __restrict__ cams,
+                                                        const int32_t* __restrict__ pt_set, int n,
+                                                        const double* __restrict__ in, double* __restrict__ out) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    double x, y;
+    undistort_rect(cams[pt_set[t]], in[2 * t], in[2 * t + 1], x, y);
     out[2 * t] = x;
     out[2 * t + 1] = y;
 }
@@ -732,19 +855,21 @@ struct StereoArgs {
     int n, win, max_level, max_iter;
 };
 
-__global__ void __launch_bounds__(64) k_stereo_match(Pyr P0, Pyr P1, StereoArgs a) {
+// One point on one wavefront: steps 1-4 of the header; (c1x, c1y) is cam1_pts[i],
+// the return value reason[i].  Shared by k_stereo_match and k_stereo_match_sets.
+__device__ __forceinline__ int stereo_point(const Pyr& P0, const Pyr& P1, const CamModel& cam0, const CamModel& cam1,
+                                            const double* E, double epi_thr, double eps, int win, int max_level,
+                                            int max_iter, double px, double py, int lane, float& c1x, float& c1y) {
 #pragma clang fp contract(off)
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= a.n) return;
-    const double px = a.pts[2 * i], py = a.pts[2 * i + 1];
     double ux, uy, gx, gy;
-    undistort_rect(a.cam0, px, py, ux, uy);   // step 1
-    distort_pix(a.cam1, ux, uy, gx, gy);
+    undistort_rect(cam0, px, py, ux, uy);   // step 1
+    distort_pix(cam1, ux, uy, gx, gy);
     const float c0x = (float)px, c0y = (float)py;
-    float c1x = (float)gx, c1y = (float)gy;
-    const bool st = lk_point(P0, P1, c0x, c0y, c1x, c1y, a.win, a.max_level, a.max_iter, a.eps, lane);   // step 2
+    c1x = (float)gx;
+    c1y = (float)gy;
+    const bool st = lk_point(P0, P1, c0x, c0y, c1x, c1y, win, max_level, max_iter, eps, lane);   // step 2
     float bx = c0x, by = c0y;
-    (void)lk_point(P1, P0, c1x, c1y, bx, by, a.win, a.max_level, a.max_iter, a.eps, lane);   // step 3
+    (void)lk_point(P1, P0, c1x, c1y, bx, by, win, max_level, max_iter, eps, lane);   // step 3
     const float dx = c0x - bx, dy = c0y - by;
     const float err = sqrtf(dx * dx + dy * dy);
     const float xmax = (float)(P1.lv[0].w - 1), ymax = (float)(P1.lv[0].h - 1);
@@ -759,12 +884,56 @@ __global__ void __launch_bounds__(64) k_stereo_match(Pyr P0, Pyr P1, StereoArgs 
         reason = 4;
     } else {
         double u0x, u0y, u1x, u1y;
-        if (!undistort_norm(a.cam0, (double)c0x, (double)c0y, u0x, u0y)) u0x = u0y = -1000000.0;
-        if (!undistort_norm(a.cam1, (double)c1x, (double)c1y, u1x, u1y)) u1x = u1y = -1000000.0;
-        const double lx = a.E[0] * u0x + a.E[1] * u0y + a.E[2], ly = a.E[3] * u0x + a.E[4] * u0y + a.E[5];
+        if (!undistort_norm(cam0, (double)c0x, (double)c0y, u0x, u0y)) u0x = u0y = -1000000.0;
+        if (!undistort_norm(cam1, (double)c1x, (double)c1y, u1x, u1y)) u1x = u1y = -1000000.0;
+        const double lx = E[0] * u0x + E[1] * u0y + E[2], ly = E[3] * u0x + E[4] * u0y + E[5];
         const double error = fabs(u1x * lx) / sqrt(lx * lx + ly * ly);
-        if (error > a.epi_thr) reason = 5;
+        if (error > epi_thr) reason = 5;
     }
+    return reason;
+}
+
+__global__ void __launch_bounds__(64) k_stereo_match(Pyr P0, Pyr P1, StereoArgs a) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= a.n) return;
+    float c1x, c1y;
+    const int reason = stereo_point(P0, P1, a.cam0, a.cam1, a.E, a.epi_thr, a.eps, a.win, a.max_level, a.max_iter,
+                                    a.pts[2 * i], a.pts[2 * i + 1], lane, c1x, c1y);
+    if (lane == 0) {
+        a.cam1_pts[2 * i] = c1x;
+        a.cam1_pts[2 * i + 1] = c1y;
+        a.inlier[i] = reason == 0 ? 1 : 0;
+        a.reason[i] = (uint8_t)reason;
+    }
+}
+
+// mfe_stereo_match_sets: one table entry per set (cam0.R = R_guess, both cameras
+// with new intrinsics [1 1 0 0], as StereoArgs), read by every lane of the point's
+// wavefront at the same address
+struct StereoSet {
+    CamModel cam0, cam1;
+    double E[9];
+    double epi_thr;
+    int slot0, slot1;
+};
+struct StereoSetsArgs {
+    const Pyr* tab;
+    const StereoSet* sets;
+    const int32_t* pt_set;
+    const double* pts;
+    float* cam1_pts;
+    uint8_t *inlier, *reason;
+    double eps;
+    int n, win, max_level, max_iter;
+};
+
+__global__ void __launch_bounds__(64) k_stereo_match_sets(StereoSetsArgs a) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    if (i >= a.n) return;
+    const StereoSet& S = a.sets[__builtin_amdgcn_readfirstlane(a.pt_set[i])];
+    float c1x, c1y;
+    const int reason = stereo_point(a.tab[S.slot0], a.tab[S.slot1], S.cam0, S.cam1, S.E, S.epi_thr, a.eps, a.win,
+                                    a.max_level, a.max_iter, a.pts[2 * i], a.pts[2 * i + 1], lane, c1x, c1y);
     if (lane == 0) {
         a.cam1_pts[2 * i] = c1x;
         a.cam1_pts[2 * i + 1] = c1y;
@@ -777,12 +946,7 @@ __global__ void __launch_bounds__(64) k_stereo_match(Pyr P0, Pyr P1, StereoArgs 
 // include/msckf_pipeline.h states the stages.  k_mask_clear: 7 threads per
 // occupied point, one per row of its 7 x 7 block (threads of overlapping blocks
 // store the same 0).
-__global__ void __launch_bounds__(256) k_mask_clear(const float* __restrict__ occ, int n_occ,
-                                                    uint8_t* __restrict__ mask, int w, int h) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    const int p = t / 7, r = t - 7 * p;
-    if (p >= n_occ) return;
-    const float px = occ[2 * p], py = occ[2 * p + 1];
+__device__ __forceinline__ void mask_clear_row(float px, float py, int r, uint8_t* __restrict__ mask, int w, int h) {
     if (!(px >= 3.f && py >= 3.f && px < (float)(w + 3) && py < (float)(h + 3))) return;   // NaN: nothing
     const int x = (int)px, yy = (int)py - 3 + r;   // 3 <= x <= w + 2, yy >= 0
     if (yy >= h) return;
@@ -790,11 +954,28 @@ __global__ void __launch_bounds__(256) k_mask_clear(const float* __restrict__ oc
     for (int xx = x - 3; xx <= x1; ++xx) mask[(size_t)yy * w + xx] = 0;
 }
 
+__global__ void __launch_bounds__(256) k_mask_clear(const float* __restrict__ occ, int n_occ,
+                                                    uint8_t* __restrict__ mask, int w, int h) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int p = t / 7, r = t - 7 * p;
+    if (p >= n_occ) return;
+    mask_clear_row(occ[2 * p], occ[2 * p + 1], r, mask, w, h);
+}
+
+// the occupied points of all sets, each in the mask of its set (occ_set[p])
+__global__ void __launch_bounds__(256) k_mask_clear_sets(const float* __restrict__ occ,
+                                                         const int32_t* __restrict__ occ_set, int n_occ,
+                                                         uint8_t* __restrict__ mask, int w, int h) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int p = t / 7, r = t - 7 * p;
+    if (p >= n_occ) return;
+    mask_clear_row(occ[2 * p], occ[2 * p + 1], r, mask + (size_t)occ_set[p] * w * h, w, h);
+}
+
 // exclusive scan of the row counts in one workgroup: a contiguous run of rows
 // per thread, the 256 run sums through LDS; *total = the sum
-__global__ void __launch_bounds__(256) k_row_scan(const int* __restrict__ cnt, int* __restrict__ off, int h,
-                                                  int* __restrict__ total) {
-    __shared__ int s_part[256];
+__device__ __forceinline__ void row_scan_block(const int* __restrict__ cnt, int* __restrict__ off, int h,
+                                               int* __restrict__ total, int* s_part) {
     const int tid = threadIdx.x, per = (h + 255) / 256;
     const int r0 = min(tid * per, h), r1 = min(r0 + per, h);
     int s = 0;
@@ -808,6 +989,19 @@ __global__ void __launch_bounds__(256) k_row_scan(const int* __restrict__ cnt, i
         base += cnt[r];
     }
     if (tid == 255) *total = base;
+}
+
+__global__ void __launch_bounds__(256) k_row_scan(const int* __restrict__ cnt, int* __restrict__ off, int h,
+                                                  int* __restrict__ total) {
+    __shared__ int s_part[256];
+    row_scan_block(cnt, off, h, total, s_part);
+}
+
+// blockIdx.x = the set
+__global__ void __launch_bounds__(256) k_row_scan_sets(GridWork g, int* __restrict__ totals) {
+    __shared__ int s_part[256];
+    int* rows = g.rows + (size_t)blockIdx.x * 2 * g.h;
+    row_scan_block(rows, rows + g.h, g.h, totals + blockIdx.x, s_part);
 }
 
 struct GridArgs {
@@ -833,10 +1027,8 @@ __device__ __forceinline__ long long wave_max64(long long v) {
 // arg-max over the raster list.  key = response << 32 | (INT_MAX - index), so
 // the larger key is the larger response and, among equals, the earlier
 // keypoint; round r takes the largest key below round r - 1's.
-__global__ void __launch_bounds__(256) k_grid_select(GridArgs a) {
-    __shared__ long long s_key[4];
-    __shared__ int s_cnt[4];
-    const int cell = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__device__ __forceinline__ void grid_select_cell(const GridArgs& a, int cell, long long* s_key, int* s_cnt) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = min(*a.total, a.cap);
     auto in_cell = [&](int i) -> bool {
         const int x = (int)a.xy[2 * i], y = (int)a.xy[2 * i + 1];
@@ -874,6 +1066,26 @@ __global__ void __launch_bounds__(256) k_grid_select(GridArgs a) {
     }
 }
 
+__global__ void __launch_bounds__(256) k_grid_select(GridArgs a) {
+    __shared__ long long s_key[4];
+    __shared__ int s_cnt[4];
+    grid_select_cell(a, blockIdx.x, s_key, s_cnt);
+}
+
+// blockIdx.y = the set; a holds set 0's pointers, the outputs [n_sets][cells k]
+__global__ void __launch_bounds__(256) k_grid_select_sets(GridArgs a, int kp_cap) {
+    __shared__ long long s_key[4];
+    __shared__ int s_cnt[4];
+    const size_t s = blockIdx.y, cells = gridDim.x;
+    a.xy += s * 3 * kp_cap;
+    a.resp += s * 3 * kp_cap;
+    a.total += s;
+    a.out_xy += s * cells * a.k * 2;
+    a.out_resp += s * cells * a.k;
+    a.cell_count += s * cells;
+    grid_select_cell(a, blockIdx.x, s_key, s_cnt);
+}
+
 }  // namespace
 
 // ================================================================ C-ABI ====
@@ -896,6 +1108,11 @@ struct mfe_ctx {
     unsigned char* rs_dev = nullptr;
     unsigned char* rs_host = nullptr;
     size_t rs_dev_cap = 0, rs_host_cap = 0;
+    // the set calls (msckf_lanes.h): the slots' Pyr descriptors on the device, written by the
+    // first set call, and the per-set work areas of mfe_fast_grid_sets for lanes_cap sets
+    Pyr* d_pyr = nullptr;
+    GridWork lanes{};
+    int lanes_cap = 0;
 };
 
 namespace {
@@ -929,6 +1146,90 @@ int grow_scratch(mfe_ctx* c, size_t dev_bytes, size_t host_bytes) {
     return 0;
 }
 
+void free_grid_work(mfe_ctx* c) {
+    if (c->lanes.score) (void)hipFree(c->lanes.score);
+    if (c->lanes.mask) (void)hipFree(c->lanes.mask);
+    if (c->lanes.rows) (void)hipFree(c->lanes.rows);
+    if (c->lanes.kp) (void)hipFree(c->lanes.kp);
+    c->lanes = GridWork{};
+    c->lanes_cap = 0;
+}
+
+// the work areas of mfe_fast_grid_sets for n_sets sets (nothing is in flight: every call
+// ends with a synchronisation)
+int grow_grid_work(mfe_ctx* c, int n_sets) {
+    if (n_sets <= c->lanes_cap) return 0;
+    free_grid_work(c);
+    const size_t S = (size_t)n_sets, px = (size_t)c->W * c->H;
+    GridWork& g = c->lanes;
+    MFE_HIP(hipMalloc((void**)&g.score, S * px * 2));
+    MFE_HIP(hipMalloc((void**)&g.mask, S * px));
+    MFE_HIP(hipMalloc((void**)&g.rows, S * 2 * c->H * sizeof(int)));
+    MFE_HIP(hipMalloc((void**)&g.kp, S * 3 * c->kp_cap * sizeof(float)));
+    g.w = c->W; g.h = c->H; g.kp_cap = c->kp_cap;
+    c->lanes_cap = n_sets;
+    return 0;
+}
+
+// the first set call of a context writes the slots' descriptors to the device
+int ensure_pyr_table(mfe_ctx* c) {
+    if (c->d_pyr) return 0;
+    void* p;
+    if (int rc = dev_alloc(c, &p, c->slots.size() * sizeof(Pyr))) return rc;
+    MFE_HIP(hipMemcpy(p, c->slots.data(), c->slots.size() * sizeof(Pyr), hipMemcpyHostToDevice));
+    c->d_pyr = (Pyr*)p;
+    return 0;
+}
+
+// set_off of a set call: [n_sets + 1], from 0, not decreasing, the total within max_points
+int check_set_off(mfe_ctx* c, int n_sets, const int32_t* set_off, const char* name) {
+    if (!set_off) MFE_FAIL(-1, "null %s", name);
+    if (set_off[0] != 0) MFE_FAIL(-1, "%s[0] = %d, must be 0", name, set_off[0]);
+    for (int s = 0; s < n_sets; ++s)
+        if (set_off[s + 1] < set_off[s]) MFE_FAIL(-1, "%s is not monotone at set %d", name, s);
+    if (set_off[n_sets] > c->max_points)
+        MFE_FAIL(-1, "%d points in all sets, above the context's %d", set_off[n_sets], c->max_points);
+    return 0;
+}
+
+int check_slots(mfe_ctx* c, int n, const int32_t* slots, const char* name) {
+    if (!slots) MFE_FAIL(-1, "null %s", name);
+    for (int s = 0; s < n; ++s)
+        if (slots[s] < 0 || slots[s] >= c->nslot)
+            MFE_FAIL(-1, "%s[%d] = %d outside [0, %d)", name, s, slots[s], c->nslot);
+    return 0;
+}
+
+int check_lk_args(mfe_ctx* c, int win, int max_level, int max_iter) {
+    if (win < 3 || win * win > 64 * LK_SLOTS) MFE_FAIL(-1, "window %d outside [3, 16]", win);
+    if (max_level < 0 || max_level > c->max_level) MFE_FAIL(-1, "max_level %d outside [0, %d]", max_level, c->max_level);
+    if (max_iter < 1) MFE_FAIL(-1, "max_iter must be positive");
+    return 0;
+}
+
+int check_models(int n_sets, const int32_t* model, const char* name) {
+    if (!model) MFE_FAIL(-1, "null %s", name);
+    for (int s = 0; s < n_sets; ++s)
+        if (model[s] != MFE_RADTAN && model[s] != MFE_EQUIDISTANT)
+            MFE_FAIL(-1, "unknown distortion model %d (%s[%d])", model[s], name, s);
+    return 0;
+}
+
+// byte offsets of a packed block's sections, each aligned to 16
+struct Block {
+    size_t size = 0;
+    size_t add(size_t bytes) {
+        const size_t o = size;
+        size = (size + bytes + 15) & ~(size_t)15;
+        return o;
+    }
+};
+
+void fill_pt_set(int32_t* pt_set, int n_sets, const int32_t* set_off) {
+    for (int s = 0; s < n_sets; ++s)
+        for (int i = set_off[s]; i < set_off[s + 1]; ++i) pt_set[i] = s;
+}
+
 CamModel make_model(const double* intr, int model, const double* coeffs, const double* R, const double* nk) {
     CamModel m{};
     m.fx = intr[0]; m.fy = intr[1]; m.cx = intr[2]; m.cy = intr[3];
@@ -949,7 +1250,7 @@ int mfe_create(int hip_device, int width, int height, int nslot, int max_level, 
     if (!out) MFE_FAIL(-1, "null out");
     *out = nullptr;
     if (width < 8 || height < 8 || width > 16384 || height > 16384) MFE_FAIL(-1, "bad image size %dx%d", width, height);
-    if (nslot < 1 || nslot > 16) MFE_FAIL(-1, "nslot %d outside [1, 16]", nslot);
+    if (nslot < 1 || nslot > MFE_MAX_SLOTS) MFE_FAIL(-1, "nslot %d outside [1, %d]", nslot, MFE_MAX_SLOTS);
     if (max_level < 0 || max_level >= MAXL) MFE_FAIL(-1, "max_level %d outside [0, %d]", max_level, MAXL - 1);
     if (max_points < 1) MFE_FAIL(-1, "max_points must be positive");
     MFE_HIP(hipSetDevice(hip_device));
@@ -1005,6 +1306,7 @@ int mfe_destroy(mfe_ctx_t* c) {
     for (void* p : c->allocs) (void)hipFree(p);
     if (c->rs_dev) (void)hipFree(c->rs_dev);
     if (c->rs_host) (void)hipHostFree(c->rs_host);
+    free_grid_work(c);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return 0;
@@ -1297,6 +1599,259 @@ int mfe_fast_grid(mfe_ctx_t* c, int slot, int threshold, int n_occ, const float*
             response_out[w] = resp[cell * K + r];
         }
     }
+    return 0;
+}
+
+// ------------------------------------------------- set calls (msckf_lanes.h) --
+int mfe_upload_many(mfe_ctx_t* c, int n, const int32_t* slots, const uint8_t* images) {
+    if (!c || !images) MFE_FAIL(-1, "null argument");
+    if (n < 1 || n > c->nslot) MFE_FAIL(-1, "n = %d outside [1, %d]", n, c->nslot);
+    if (check_slots(c, n, slots, "slots")) return -1;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j)
+            if (slots[i] == slots[j]) MFE_FAIL(-1, "slot %d is named twice (images %d and %d)", slots[i], j, i);
+    MFE_HIP(hipSetDevice(c->device));
+    if (int rc = ensure_pyr_table(c)) return rc;
+    hipStream_t s = c->stream;
+    const size_t px = (size_t)c->W * c->H;
+    Block b;
+    const size_t o_slots = b.add(4 * (size_t)n), o_img = b.add(px * n);
+    if (int rc = grow_scratch(c, b.size, b.size)) return rc;
+    unsigned char *hin = c->rs_host, *d = c->rs_dev;
+    memcpy(hin + o_slots, slots, 4 * (size_t)n);
+    memcpy(hin + o_img, images, px * n);
+    MFE_HIP(hipMemcpyAsync(d, hin, b.size, hipMemcpyHostToDevice, s));
+    const int32_t* dslots = (const int32_t*)(d + o_slots);
+    const int vec = px % 16 == 0 ? 1 : 0;
+    const size_t items = vec ? px / 16 : px;
+    hipLaunchKernelGGL(k_image_scatter_sets, dim3((unsigned)((items + 255) / 256), 1, n), dim3(256), 0, s,
+                       (const Pyr*)c->d_pyr, dslots, (const uint8_t*)(d + o_img), px, vec);
+    for (int l = 0; l <= c->max_level; ++l) {
+        const Level& L = c->slots[0].lv[l];
+        const dim3 grid((L.w + 15) / 16, (L.h + 15) / 16, n);
+        if (l > 0) hipLaunchKernelGGL(k_pyrdown_sets, grid, dim3(256), 0, s, (const Pyr*)c->d_pyr, dslots, l);
+        hipLaunchKernelGGL(k_scharr_sets, grid, dim3(256), 0, s, (const Pyr*)c->d_pyr, dslots, l);
+    }
+    MFE_HIP(hipGetLastError());
+    MFE_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int mfe_lk_sets(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const int32_t* slot_prev,
+                const int32_t* slot_next, const float* prev_pts, float* next_pts, uint8_t* status, int win,
+                int max_level, int max_iter, double eps) {
+    if (!c) MFE_FAIL(-1, "null context");
+    if (n_sets < 0 || n_sets > MFE_MAX_SETS) MFE_FAIL(-1, "n_sets = %d outside [0, %d]", n_sets, MFE_MAX_SETS);
+    if (n_sets == 0) return 0;
+    if (check_set_off(c, n_sets, set_off, "set_off") || check_slots(c, n_sets, slot_prev, "slot_prev") ||
+        check_slots(c, n_sets, slot_next, "slot_next") || check_lk_args(c, win, max_level, max_iter))
+        return -1;
+    const size_t T = (size_t)set_off[n_sets], S = (size_t)n_sets;
+    if (T == 0) return 0;
+    if (!prev_pts || !next_pts || !status) MFE_FAIL(-1, "null point array");
+    MFE_HIP(hipSetDevice(c->device));
+    if (int rc = ensure_pyr_table(c)) return rc;
+    hipStream_t s = c->stream;
+    // prev | pt_set | slots | next | status: next ends what goes in and starts what comes back
+    Block b;
+    const size_t o_prev = b.add(8 * T), o_set = b.add(4 * T), o_slots = b.add(8 * S), o_next = b.add(8 * T),
+                 in_bytes = b.size, o_st = b.add(T), out_bytes = b.size - o_next;
+    if (int rc = grow_scratch(c, b.size, b.size)) return rc;
+    unsigned char *h = c->rs_host, *d = c->rs_dev;
+    memcpy(h + o_prev, prev_pts, 8 * T);
+    fill_pt_set((int32_t*)(h + o_set), n_sets, set_off);
+    for (size_t i = 0; i < S; ++i) {
+        ((int32_t*)(h + o_slots))[2 * i] = slot_prev[i];
+        ((int32_t*)(h + o_slots))[2 * i + 1] = slot_next[i];
+    }
+    memcpy(h + o_next, next_pts, 8 * T);
+    MFE_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+    LkSetsArgs a;
+    a.tab = c->d_pyr;
+    a.pt_set = (const int32_t*)(d + o_set);
+    a.set_slots = (const int32_t*)(d + o_slots);
+    a.prev_pts = (const float*)(d + o_prev);
+    a.next_pts = (float*)(d + o_next);
+    a.status = d + o_st;
+    a.eps = eps;
+    a.n = (int)T; a.win = win; a.max_level = max_level; a.max_iter = max_iter;
+    hipLaunchKernelGGL(k_lk_sets, dim3((unsigned)T), dim3(64), 0, s, a);
+    MFE_HIP(hipGetLastError());
+    MFE_HIP(hipMemcpyAsync(h + o_next, d + o_next, out_bytes, hipMemcpyDeviceToHost, s));
+    MFE_HIP(hipStreamSynchronize(s));
+    memcpy(next_pts, h + o_next, 8 * T);
+    memcpy(status, h + o_st, T);
+    return 0;
+}
+
+int mfe_stereo_match_sets(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const int32_t* slot_cam0,
+                          const int32_t* slot_cam1, const double* cam0_pts, const double* intrinsics0,
+                          const int32_t* model0, const double* coeffs0, const double* intrinsics1,
+                          const int32_t* model1, const double* coeffs1, const double* R_guess, const double* E,
+                          const double* stereo_threshold, int win, int max_level, int max_iter, double eps,
+                          float* cam1_pts, uint8_t* inlier, uint8_t* reason) {
+    if (!c) MFE_FAIL(-1, "null context");
+    if (n_sets < 0 || n_sets > MFE_MAX_SETS) MFE_FAIL(-1, "n_sets = %d outside [0, %d]", n_sets, MFE_MAX_SETS);
+    if (n_sets == 0) return 0;
+    if (check_set_off(c, n_sets, set_off, "set_off") || check_slots(c, n_sets, slot_cam0, "slot_cam0") ||
+        check_slots(c, n_sets, slot_cam1, "slot_cam1") || check_lk_args(c, win, max_level, max_iter))
+        return -1;
+    if (!intrinsics0 || !coeffs0 || !intrinsics1 || !coeffs1 || !R_guess || !E || !stereo_threshold)
+        MFE_FAIL(-1, "null camera argument");
+    if (check_models(n_sets, model0, "model0") || check_models(n_sets, model1, "model1")) return -1;
+    const size_t T = (size_t)set_off[n_sets], S = (size_t)n_sets;
+    if (T == 0) return 0;
+    if (!cam0_pts || !cam1_pts || !inlier || !reason) MFE_FAIL(-1, "null point array");
+    MFE_HIP(hipSetDevice(c->device));
+    if (int rc = ensure_pyr_table(c)) return rc;
+    hipStream_t s = c->stream;
+    Block b;
+    const size_t o_pts = b.add(16 * T), o_tab = b.add(sizeof(StereoSet) * S), o_set = b.add(4 * T), in_bytes = b.size,
+                 o_c1 = b.add(8 * T), o_inl = b.add(T), o_rsn = b.add(T), out_bytes = b.size - o_c1;
+    if (int rc = grow_scratch(c, b.size, b.size)) return rc;
+    unsigned char *h = c->rs_host, *d = c->rs_dev;
+    memcpy(h + o_pts, cam0_pts, 16 * T);
+    StereoSet* tab = (StereoSet*)(h + o_tab);
+    for (size_t i = 0; i < S; ++i) {
+        const double *K0 = intrinsics0 + 4 * i, *K1 = intrinsics1 + 4 * i;
+        tab[i].cam0 = make_model(K0, model0[i], coeffs0 + 4 * i, R_guess + 9 * i, nullptr);
+        tab[i].cam1 = make_model(K1, model1[i], coeffs1 + 4 * i, nullptr, nullptr);
+        for (int j = 0; j < 9; ++j) tab[i].E[j] = E[9 * i + j];
+        tab[i].epi_thr = stereo_threshold[i] * (4.0 / (K0[0] + K0[1] + K1[0] + K1[1]));
+        tab[i].slot0 = slot_cam0[i];
+        tab[i].slot1 = slot_cam1[i];
+    }
+    fill_pt_set((int32_t*)(h + o_set), n_sets, set_off);
+    MFE_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+    StereoSetsArgs a;
+    a.tab = c->d_pyr;
+    a.sets = (const StereoSet*)(d + o_tab);
+    a.pt_set = (const int32_t*)(d + o_set);
+    a.pts = (const double*)(d + o_pts);
+    a.cam1_pts = (float*)(d + o_c1);
+    a.inlier = d + o_inl;
+    a.reason = d + o_rsn;
+    a.eps = eps;
+    a.n = (int)T; a.win = win; a.max_level = max_level; a.max_iter = max_iter;
+    hipLaunchKernelGGL(k_stereo_match_sets, dim3((unsigned)T), dim3(64), 0, s, a);
+    MFE_HIP(hipGetLastError());
+    MFE_HIP(hipMemcpyAsync(h + o_c1, d + o_c1, out_bytes, hipMemcpyDeviceToHost, s));
+    MFE_HIP(hipStreamSynchronize(s));
+    memcpy(cam1_pts, h + o_c1, 8 * T);
+    memcpy(inlier, h + o_inl, T);
+    memcpy(reason, h + o_rsn, T);
+    return 0;
+}
+
+int mfe_fast_grid_sets(mfe_ctx_t* c, int n_sets, const int32_t* slots, const int32_t* occ_off,
+                       const float* occupied, int threshold, int grid_row, int grid_col, int k, int max_kp,
+                       float* xy_out, float* response_out, int32_t* cell_count, int32_t* n_total) {
+    if (!c) MFE_FAIL(-1, "null context");
+    if (n_sets < 0 || n_sets > MFE_MAX_SETS) MFE_FAIL(-1, "n_sets = %d outside [0, %d]", n_sets, MFE_MAX_SETS);
+    if (n_sets == 0) return 0;
+    if (!xy_out || !response_out || !cell_count || !n_total) MFE_FAIL(-1, "null argument");
+    if (check_slots(c, n_sets, slots, "slots") || check_set_off(c, n_sets, occ_off, "occ_off")) return -1;
+    const size_t T = (size_t)occ_off[n_sets], S = (size_t)n_sets;
+    if (T > 0 && !occupied) MFE_FAIL(-1, "null occupied points");
+    if (c->W < 16 || c->H < 16) MFE_FAIL(-1, "image %dx%d is smaller than 16x16", c->W, c->H);
+    if (k < 1 || k > MFE_GRID_MAX_K) MFE_FAIL(-1, "k = %d outside [1, %d]", k, MFE_GRID_MAX_K);
+    if (grid_row < 1 || grid_col < 1 || (long long)grid_row * grid_col > MFE_GRID_MAX_CELLS)
+        MFE_FAIL(-1, "grid %dx%d outside [1, %d] cells", grid_row, grid_col, MFE_GRID_MAX_CELLS);
+    if (max_kp < 1 || max_kp > c->kp_cap) MFE_FAIL(-1, "max_kp = %d outside [1, %d]", max_kp, c->kp_cap);
+    MFE_HIP(hipSetDevice(c->device));
+    if (int rc = ensure_pyr_table(c)) return rc;
+    if (int rc = grow_grid_work(c, n_sets)) return rc;
+    threshold = threshold < 0 ? 0 : (threshold > 255 ? 255 : threshold);
+    hipStream_t s = c->stream;
+    const int W = c->W, H = c->H;
+    const size_t cells = (size_t)grid_row * grid_col, K = (size_t)k;
+    Block b;
+    const size_t o_occ = b.add(8 * T), o_oset = b.add(4 * T), o_slots = b.add(4 * S), in_bytes = b.size,
+                 o_tot = b.add(4 * S), o_cnt = b.add(4 * S * cells), o_resp = b.add(4 * S * cells * K),
+                 o_xy = b.add(8 * S * cells * K), out_bytes = b.size - o_tot;
+    if (int rc = grow_scratch(c, b.size, b.size)) return rc;
+    unsigned char *h = c->rs_host, *d = c->rs_dev;
+    if (T > 0) memcpy(h + o_occ, occupied, 8 * T);
+    fill_pt_set((int32_t*)(h + o_oset), n_sets, occ_off);
+    memcpy(h + o_slots, slots, 4 * S);
+    MFE_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+    const GridWork& g = c->lanes;
+    const int32_t* dslots = (const int32_t*)(d + o_slots);
+    MFE_HIP(hipMemsetAsync(g.mask, 1, S * W * H, s));
+    if (T > 0)
+        hipLaunchKernelGGL(k_mask_clear_sets, dim3((unsigned)((7 * T + 255) / 256)), dim3(256), 0, s,
+                           (const float*)(d + o_occ), (const int32_t*)(d + o_oset), (int)T, g.mask, W, H);
+    hipLaunchKernelGGL(k_fast_sets, dim3((W + 15) / 16, (H + 15) / 16, n_sets), dim3(256), 0, s, (const Pyr*)c->d_pyr,
+                       dslots, threshold, g.score);
+    hipLaunchKernelGGL(k_fast_rows_sets, dim3((H + 3) / 4, n_sets), dim3(256), 0, s, g, 0, 0);
+    hipLaunchKernelGGL(k_row_scan_sets, dim3(n_sets), dim3(256), 0, s, g, (int*)(d + o_tot));
+    hipLaunchKernelGGL(k_fast_rows_sets, dim3((H + 3) / 4, n_sets), dim3(256), 0, s, g, 1, max_kp);
+    GridArgs a;
+    a.xy = g.kp; a.resp = g.kp + 2 * (size_t)g.kp_cap; a.total = (const int*)(d + o_tot);
+    a.out_xy = (float*)(d + o_xy); a.out_resp = (float*)(d + o_resp); a.cell_count = (int*)(d + o_cnt);
+    a.cap = max_kp; a.gh = (H + grid_row - 1) / grid_row; a.gw = (W + grid_col - 1) / grid_col;
+    a.grid_col = grid_col; a.k = k;
+    hipLaunchKernelGGL(k_grid_select_sets, dim3((unsigned)cells, n_sets), dim3(256), 0, s, a, g.kp_cap);
+    MFE_HIP(hipGetLastError());
+    MFE_HIP(hipMemcpyAsync(h + o_tot, d + o_tot, out_bytes, hipMemcpyDeviceToHost, s));
+    MFE_HIP(hipStreamSynchronize(s));
+    const int32_t* tot = (const int32_t*)(h + o_tot);
+    int over = -1;
+    for (size_t i = 0; i < S; ++i) {
+        n_total[i] = tot[i];
+        if (tot[i] > max_kp && over < 0) over = (int)i;
+    }
+    if (over >= 0) MFE_FAIL(-3, "set %d: %d keypoints exceed the capacity of %d", over, tot[over], max_kp);
+    const int32_t* cnt = (const int32_t*)(h + o_cnt);
+    const float* resp = (const float*)(h + o_resp);
+    const float* xy = (const float*)(h + o_xy);
+    for (size_t i = 0; i < S; ++i) {
+        size_t w = i * cells * K;
+        for (size_t cell = 0; cell < cells; ++cell) {
+            const size_t q = i * cells + cell, kept = std::min((size_t)cnt[q], K);
+            cell_count[q] = cnt[q];
+            for (size_t r = 0; r < kept; ++r, ++w) {
+                xy_out[2 * w] = xy[2 * (q * K + r)];
+                xy_out[2 * w + 1] = xy[2 * (q * K + r) + 1];
+                response_out[w] = resp[q * K + r];
+            }
+        }
+    }
+    return 0;
+}
+
+int mfe_undistort_sets(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const double* pts_in, double* pts_out,
+                       const double* intrinsics, const int32_t* model, const double* coeffs, const double* R,
+                       const double* new_intrinsics) {
+    if (!c) MFE_FAIL(-1, "null context");
+    if (n_sets < 0 || n_sets > MFE_MAX_SETS) MFE_FAIL(-1, "n_sets = %d outside [0, %d]", n_sets, MFE_MAX_SETS);
+    if (n_sets == 0) return 0;
+    if (check_set_off(c, n_sets, set_off, "set_off")) return -1;
+    if (!intrinsics || !coeffs || !R || !new_intrinsics) MFE_FAIL(-1, "null camera argument");
+    if (check_models(n_sets, model, "model")) return -1;
+    const size_t T = (size_t)set_off[n_sets], S = (size_t)n_sets;
+    if (T == 0) return 0;
+    if (!pts_in || !pts_out) MFE_FAIL(-1, "null point array");
+    MFE_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    Block b;
+    const size_t o_pts = b.add(16 * T), o_tab = b.add(sizeof(CamModel) * S), o_set = b.add(4 * T), in_bytes = b.size,
+                 o_out = b.add(16 * T);
+    if (int rc = grow_scratch(c, b.size, b.size)) return rc;
+    unsigned char *h = c->rs_host, *d = c->rs_dev;
+    memcpy(h + o_pts, pts_in, 16 * T);
+    CamModel* tab = (CamModel*)(h + o_tab);
+    for (size_t i = 0; i < S; ++i)
+        tab[i] = make_model(intrinsics + 4 * i, model[i], coeffs + 4 * i, R + 9 * i, new_intrinsics + 4 * i);
+    fill_pt_set((int32_t*)(h + o_set), n_sets, set_off);
+    MFE_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_undistort_sets, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, s,
+                       (const CamModel*)(d + o_tab), (const int32_t*)(d + o_set), (int)T, (const double*)(d + o_pts),
+                       (double*)(d + o_out));
+    MFE_HIP(hipGetLastError());
+    MFE_HIP(hipMemcpyAsync(h + o_out, d + o_out, 16 * T, hipMemcpyDeviceToHost, s));
+    MFE_HIP(hipStreamSynchronize(s));
+    memcpy(pts_out, h + o_out, 16 * T);
     return 0;
 }
 

@@ -17,6 +17,11 @@ published message -- and every image operator runs in the HIP kernels of
   stereo_match (image.py:554-638)               mfe_stereo_match (k_stereo_match,
                                                 include/msckf_pipeline.h), opt-in
   mask + detect + sieve (image.py:317-360)      mfe_fast_grid (include/msckf_pipeline.h), opt-in
+  one stream per ImageProcessor                 MultiImageProcessor: S streams on one context,
+                                                each stage one call over all lanes' sets
+                                                (mfe_upload_many, mfe_lk_sets, mfe_stereo_match_sets,
+                                                mfe_fast_grid_sets, mfe_undistort_sets,
+                                                include/msckf_lanes.h)
 
 cv2 is absent here and on the GPU box: the kernels restate the published
 OpenCV 4.x algorithms (oracle/frontend_oracle.py), parity unpinned against cv2
@@ -49,6 +54,7 @@ from . import _lib
 from .config import _default_T_imu_cam0
 
 RADTAN, EQUIDISTANT = 0, 1
+_I32P = C.POINTER(C.c_int32)
 
 FeatureMeasurement = namedtuple("FeatureMeasurement", ["id", "u0", "v0", "u1", "v1"])
 FeatureMsg = namedtuple("vio_feature_msg__", ["timestamp", "vio_features"])
@@ -346,6 +352,121 @@ class Frontend:
         m = int(np.minimum(cnt, int(k)).sum())
         return xy[:m].copy(), resp[:m].copy(), cnt, n.value
 
+    # ---- the calls over many streams' sets (include/msckf_lanes.h): one device call for a
+    # list of sets, one result per set in the shape of the single method ----
+    def _set_off(self, lens):
+        off = np.zeros(len(lens) + 1, np.int32)
+        np.cumsum(lens, out=off[1:])
+        if int(off[-1]) > self.max_points:
+            raise ValueError("%d points in all sets exceed the context's %d" % (off[-1], self.max_points))
+        return off
+
+    def upload_many(self, slots, images):
+        """mfe_upload_many: ``images[i]`` into ``slots[i]`` (distinct), all
+        pyramids built by launches over the image index."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        imgs = np.ascontiguousarray(images, np.uint8)
+        if imgs.shape != (len(sl), self.H, self.W):
+            raise ValueError("images of shape %s, expected %s" % (imgs.shape, (len(sl), self.H, self.W)))
+        self._check(self.lib.mfe_upload_many(self.h, len(sl), sl.ctypes.data_as(_I32P),
+                                             imgs.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def lk_sets(self, sets, win=15, max_level=3, max_iter=30, eps=0.01):
+        """mfe_lk_sets.  ``sets``: (slot_prev, slot_next, prev_pts, next_pts) per
+        set.  Returns one (next_pts float32 (n, 2), status uint8) per set."""
+        prev = [np.asarray(s[2], np.float32).reshape(-1, 2) for s in sets]
+        nxt = [np.asarray(s[3], np.float32).reshape(-1, 2) for s in sets]
+        for p, q in zip(prev, nxt):
+            if len(p) != len(q):
+                raise ValueError("a set's point lists differ in length (%d, %d)" % (len(p), len(q)))
+        off = self._set_off([len(p) for p in prev])
+        T = int(off[-1])
+        p = np.ascontiguousarray(np.concatenate(prev)) if sets else np.zeros((0, 2), np.float32)
+        q = np.ascontiguousarray(np.concatenate(nxt)) if sets else np.zeros((0, 2), np.float32)
+        st = np.zeros(T, np.uint8)
+        s0 = np.array([int(s[0]) for s in sets], np.int32)
+        s1 = np.array([int(s[1]) for s in sets], np.int32)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.mfe_lk_sets(self.h, len(sets), off.ctypes.data_as(_I32P), s0.ctypes.data_as(_I32P),
+                                         s1.ctypes.data_as(_I32P), p.ctypes.data_as(fp), q.ctypes.data_as(fp),
+                                         st.ctypes.data_as(C.POINTER(C.c_uint8)), int(win), int(max_level),
+                                         int(max_iter), float(eps)))
+        return [(q[off[i]:off[i + 1]], st[off[i]:off[i + 1]]) for i in range(len(sets))]
+
+    def stereo_match_sets(self, sets, win=15, max_level=3, max_iter=30, eps=0.01):
+        """mfe_stereo_match_sets.  ``sets``: (slot_cam0, slot_cam1, cam0_pts,
+        cam0, cam1, R_guess, E, stereo_threshold) per set, the arguments of
+        ``stereo_match``.  Returns one (cam1_pts, inlier, reason) per set."""
+        S = len(sets)
+        pts = [np.asarray(s[2], float).reshape(-1, 2) for s in sets]
+        off = self._set_off([len(p) for p in pts])
+        T = int(off[-1])
+        p = np.ascontiguousarray(np.concatenate(pts)) if sets else np.zeros((0, 2))
+        row = lambda get, w: np.ascontiguousarray(
+            np.array([np.asarray(get(s), float).ravel()[:w] for s in sets], float).reshape(S, w))
+        K0, k0 = row(lambda s: s[3][0], 4), row(lambda s: s[3][2], 4)
+        K1, k1 = row(lambda s: s[4][0], 4), row(lambda s: s[4][2], 4)
+        R, E = row(lambda s: s[5], 9), row(lambda s: s[6], 9)
+        thr = np.array([float(s[7]) for s in sets], float)
+        i32 = lambda get: np.array([int(get(s)) for s in sets], np.int32)
+        s0, s1, m0, m1 = i32(lambda s: s[0]), i32(lambda s: s[1]), i32(lambda s: s[3][1]), i32(lambda s: s[4][1])
+        c1 = np.zeros((T, 2), np.float32)
+        inl, rsn = np.zeros(T, np.uint8), np.zeros(T, np.uint8)
+        dp, u8 = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        self._check(self.lib.mfe_stereo_match_sets(
+            self.h, S, off.ctypes.data_as(_I32P), s0.ctypes.data_as(_I32P), s1.ctypes.data_as(_I32P),
+            p.ctypes.data_as(dp), K0.ctypes.data_as(dp), m0.ctypes.data_as(_I32P), k0.ctypes.data_as(dp),
+            K1.ctypes.data_as(dp), m1.ctypes.data_as(_I32P), k1.ctypes.data_as(dp), R.ctypes.data_as(dp),
+            E.ctypes.data_as(dp), thr.ctypes.data_as(dp), int(win), int(max_level), int(max_iter), float(eps),
+            c1.ctypes.data_as(C.POINTER(C.c_float)), inl.ctypes.data_as(u8), rsn.ctypes.data_as(u8)))
+        return [(c1[off[i]:off[i + 1]], inl[off[i]:off[i + 1]], rsn[off[i]:off[i + 1]]) for i in range(S)]
+
+    def fast_grid_sets(self, sets, threshold, grid_row, grid_col, k, max_kp=1 << 16):
+        """mfe_fast_grid_sets.  ``sets``: (slot, occupied) per set.  Returns one
+        (xy, response, cell_count, n_total) per set, as ``fast_grid``; raises
+        if any set's n_total exceeds ``max_kp``."""
+        S = len(sets)
+        occ = [np.asarray(s[1], np.float32).reshape(-1, 2) for s in sets]
+        off = self._set_off([len(o) for o in occ])
+        cells, k = int(grid_row) * int(grid_col), int(k)
+        if not (1 <= k <= _lib.GRID_MAX_K and int(grid_row) >= 1 and int(grid_col) >= 1 and
+                cells <= _lib.GRID_MAX_CELLS):
+            raise ValueError("grid %dx%d, k = %d outside the limits of msckf_pipeline.h" % (grid_row, grid_col, k))
+        o = np.ascontiguousarray(np.concatenate(occ)) if sets else np.zeros((0, 2), np.float32)
+        sl = np.array([int(s[0]) for s in sets], np.int32)
+        xy = np.zeros((S, cells * k, 2), np.float32)
+        resp = np.zeros((S, cells * k), np.float32)
+        cnt = np.zeros((S, cells), np.int32)
+        tot = np.zeros(S, np.int32)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.mfe_fast_grid_sets(
+            self.h, S, sl.ctypes.data_as(_I32P), off.ctypes.data_as(_I32P), o.ctypes.data_as(fp) if len(o) else None,
+            int(threshold), int(grid_row), int(grid_col), k, int(max_kp), xy.ctypes.data_as(fp),
+            resp.ctypes.data_as(fp), cnt.ctypes.data_as(_I32P), tot.ctypes.data_as(_I32P)))
+        m = np.minimum(cnt, k).sum(axis=1)
+        return [(xy[i, :m[i]].copy(), resp[i, :m[i]].copy(), cnt[i], int(tot[i])) for i in range(S)]
+
+    def undistort_sets(self, sets):
+        """mfe_undistort_sets.  ``sets``: (pts, intrinsics, model, coeffs, R,
+        new_intrinsics) per set, the arguments of ``undistort`` (R and
+        new_intrinsics may be None).  Returns one float64 (n, 2) per set."""
+        S = len(sets)
+        pts = [np.asarray(s[0], float).reshape(-1, 2) for s in sets]
+        off = self._set_off([len(p) for p in pts])
+        p = np.ascontiguousarray(np.concatenate(pts)) if sets else np.zeros((0, 2))
+        out = np.zeros_like(p)
+        row = lambda j, w, dflt: np.ascontiguousarray(np.array(
+            [np.asarray(dflt if s[j] is None else s[j], float).ravel()[:w] for s in sets], float).reshape(S, w))
+        K, k = row(1, 4, None), row(3, 4, None)
+        R, nK = row(4, 9, np.identity(3)), row(5, 4, (1.0, 1.0, 0.0, 0.0))
+        model = np.array([int(s[2]) for s in sets], np.int32)
+        dp = C.POINTER(C.c_double)
+        self._check(self.lib.mfe_undistort_sets(self.h, S, off.ctypes.data_as(_I32P), p.ctypes.data_as(dp),
+                                                out.ctypes.data_as(dp), K.ctypes.data_as(dp),
+                                                model.ctypes.data_as(_I32P), k.ctypes.data_as(dp),
+                                                R.ctypes.data_as(dp), nK.ctypes.data_as(dp)))
+        return [out[off[i]:off[i + 1]] for i in range(S)]
+
 
 def _model(name):
     return EQUIDISTANT if name == "equidistant" else RADTAN
@@ -358,9 +479,12 @@ class ImageProcessor:
     ``angular_velocity`` (dataset.py:56-57, 101, 169-170)."""
 
     # image slots: the previous cam0 image and the current pair rotate over three
-    def __init__(self, config=None, device=0, ransac_fn=None):
+    def __init__(self, config=None, device=0, ransac_fn=None, fe=None, slot_base=0):
         """``ransac_fn`` (signature of Frontend.two_point_ransac) replaces the
-        device call of the two-point RANSAC when config.ransac_enabled."""
+        device call of the two-point RANSAC when config.ransac_enabled.
+        ``fe`` / ``slot_base``: a shared device context and the first of this
+        stream's three slots in it (MultiImageProcessor's lanes); by default
+        the processor makes its own."""
         if config is None:
             config = FrontendConfig()
         elif not isinstance(config, FrontendConfig):
@@ -390,8 +514,9 @@ class ImageProcessor:
         self.R_cam1_imu = self.T_cam1_imu[:3, :3]
         self.t_cam1_imu = self.T_cam1_imu[:3, 3]
         W, H = int(self.cam0_resolution[0]), int(self.cam0_resolution[1])
-        self.fe = Frontend(W, H, nslot=3, max_level=config.pyramid_levels, max_points=1 << 16, device=device)
-        self._slot_prev, self._slot_c0, self._slot_c1 = 0, 1, 2
+        self.fe = fe if fe is not None else Frontend(W, H, nslot=3, max_level=config.pyramid_levels,
+                                                     max_points=1 << 16, device=device)
+        self._slot_prev, self._slot_c0, self._slot_c1 = slot_base, slot_base + 1, slot_base + 2
         self.lk_kw = dict(win=config.patch_size, max_level=config.pyramid_levels,
                           max_iter=config.max_iteration, eps=config.track_precision)
         self.ransac_fn = ransac_fn   # None: self.fe.two_point_ransac
@@ -400,6 +525,8 @@ class ImageProcessor:
 
     # ---- callbacks (image.py:95-147) ----
     def stareo_callback(self, stereo_msg):
+        if self.config.device_pipeline:
+            return self._drive(self._frame_steps(stereo_msg))
         self.cam0_curr_img_msg = stereo_msg.cam0_msg
         self.cam1_curr_img_msg = stereo_msg.cam1_msg
         self.create_image_pyramids()
@@ -413,13 +540,16 @@ class ImageProcessor:
         try:
             return self.publish()
         finally:
-            self.cam0_prev_img_msg = self.cam0_curr_img_msg
-            self.prev_features = self.curr_features
-            # the current cam0 slot becomes the previous one (its pyramid stays on the device)
-            self._slot_prev, self._slot_c0 = self._slot_c0, self._slot_prev
-            self.curr_features = [[] for _ in range(self.config.grid_num)]
+            self._end_frame()
 
     stereo_callback = stareo_callback
+
+    def _end_frame(self):
+        self.cam0_prev_img_msg = self.cam0_curr_img_msg
+        self.prev_features = self.curr_features
+        # the current cam0 slot becomes the previous one (its pyramid stays on the device)
+        self._slot_prev, self._slot_c0 = self._slot_c0, self._slot_prev
+        self.curr_features = [[] for _ in range(self.config.grid_num)]
 
     def imu_callback(self, msg):
         self.imu_msg_buffer.append(msg)
@@ -427,6 +557,8 @@ class ImageProcessor:
     def create_image_pyramids(self):
         """image.py:149-164 -- here the device builds the pyramids (and the
         Scharr derivatives LK needs) once per image."""
+        if self.config.device_pipeline:
+            return self._drive(self._upload_steps())
         self.fe.upload(self._slot_c0, self.cam0_curr_img_msg.image)
         self.fe.upload(self._slot_c1, self.cam1_curr_img_msg.image)
 
@@ -435,8 +567,11 @@ class ImageProcessor:
         return int(pt[1] / gh) * self.config.grid_col + int(pt[0] / gw)
 
     def _collect_new(self, cam0_points, responses):
-        gh, gw = self.get_grid_size(self.cam0_curr_img_msg.image)
         cam1_points, inliers = self.stereo_match(cam0_points)
+        self._assign_new(cam0_points, responses, cam1_points, inliers)
+
+    def _assign_new(self, cam0_points, responses, cam1_points, inliers):
+        gh, gw = self.get_grid_size(self.cam0_curr_img_msg.image)
         grid_new = [[] for _ in range(self.config.grid_num)]
         for i, ok in enumerate(inliers):
             if not ok:
@@ -455,11 +590,15 @@ class ImageProcessor:
 
     def initialize_first_frame(self):
         """image.py:166-217."""
+        if self.config.device_pipeline:
+            return self._drive(self._first_frame_steps())
         xy, resp = self.fe.fast(self._slot_c0, self.config.fast_threshold)
         self._collect_new([tuple(p) for p in xy], list(resp))
 
     def track_features(self):
         """image.py:219-313."""
+        if self.config.device_pipeline:
+            return self._drive(self._track_steps())
         img = self.cam0_curr_img_msg.image
         gh, gw = self.get_grid_size(img)
         cam0_R_p_c, cam1_R_p_c = self.integrate_imu_data()
@@ -517,18 +656,21 @@ class ImageProcessor:
         """The step the reference stubs (image.py:292-293), as in msckf_vio:
         the two-point RANSAC of cam0 prev -> curr and of cam1 prev -> curr, both
         in one device call; a feature stays only if it is an inlier of both."""
-        sets = [(prev_cam0, curr_cam0, cam0_R_p_c, self.cam0_intrinsics, _model(self.cam0_distortion_model),
-                 self.cam0_distortion_coeffs),
-                (prev_cam1, curr_cam1, cam1_R_p_c, self.cam1_intrinsics, _model(self.cam1_distortion_model),
-                 self.cam1_distortion_coeffs)]
+        sets = self._ransac_sets(prev_cam0, curr_cam0, prev_cam1, curr_cam1, cam0_R_p_c, cam1_R_p_c)
         fn = self.ransac_fn if self.ransac_fn is not None else self.fe.two_point_ransac
         (in0, _), (in1, _) = fn(sets, self.config.ransac_threshold, self.ransac_n_hyp, draws)
         return np.logical_and(in0, in1)
 
+    def _ransac_sets(self, prev_cam0, curr_cam0, prev_cam1, curr_cam1, cam0_R_p_c, cam1_R_p_c):
+        return [(prev_cam0, curr_cam0, cam0_R_p_c, self.cam0_intrinsics, _model(self.cam0_distortion_model),
+                 self.cam0_distortion_coeffs),
+                (prev_cam1, curr_cam1, cam1_R_p_c, self.cam1_intrinsics, _model(self.cam1_distortion_model),
+                 self.cam1_distortion_coeffs)]
+
     def add_new_features(self):
         """image.py:317-390."""
         if self.config.device_pipeline:
-            return self._add_new_features_device()
+            return self._drive(self._add_new_steps())
         img = self.cam0_curr_img_msg.image
         gh, gw = self.get_grid_size(img)
         mask = np.ones(img.shape[:2], dtype=np.uint8)
@@ -556,6 +698,8 @@ class ImageProcessor:
 
     def publish(self):
         """image.py:406-438."""
+        if self.config.device_pipeline:
+            return self._drive(self._publish_steps())
         ids, c0, c1 = [], [], []
         for f in chain.from_iterable(self.curr_features):
             ids.append(f.id)
@@ -608,7 +752,7 @@ class ImageProcessor:
         cam0 -> cam1 and back, and the vertical-disparity, round-trip and
         epipolar tests."""
         if self.config.device_pipeline:
-            return self._stereo_match_device(cam0_points)
+            return self._drive(self._stereo_match_steps(cam0_points))
         cam0_points = np.asarray(cam0_points, float).reshape(-1, 2)
         if len(cam0_points) == 0:
             return [], []
@@ -647,7 +791,136 @@ class ImageProcessor:
                 inliers[i] = False
         return [tuple(p) for p in c1], list(inliers)
 
-    def _stereo_match_device(self, cam0_points):
+    # ---- the device pipeline as a generator of device requests ----
+    # With config.device_pipeline the frame logic is written once, as generators that
+    # yield a request wherever a device call is due and receive its result (as
+    # MSCKF._frame_steps does for the filter).  The public methods above drive them with
+    # the single calls (_serve); MultiImageProcessor drives many lanes' _frame_steps and
+    # serves each kind for all waiting lanes with one set call.  Requests:
+    #   ("upload", [(slot, image), ...])                                     -> None
+    #   ("fast", slot, threshold)                                            -> Frontend.fast
+    #   ("lk", slot_prev, slot_next, prev_pts, next_pts)                     -> Frontend.lk
+    #   ("stereo_match", slot0, slot1, pts, cam0, cam1, R_guess, E, thr)     -> Frontend.stereo_match
+    #   ("ransac", sets, inlier_error, n_hyp, draws)                         -> Frontend.two_point_ransac
+    #   ("fast_grid", slot, threshold, occupied, grid_row, grid_col, k)      -> Frontend.fast_grid
+    #   ("undistort", [(pts, intrinsics, model, coeffs, R, new_intrinsics)]) -> [points per set]
+    # The LK parameters (self.lk_kw) are not part of a request: they are per processor, and
+    # lanes of one MultiImageProcessor agree on them.
+    def _drive(self, gen):
+        try:
+            req = next(gen)
+            while True:
+                req = gen.send(self._serve(req))
+        except StopIteration as e:
+            return e.value
+
+    def _serve(self, req):
+        kind = req[0]
+        if kind == "upload":
+            for slot, image in req[1]:
+                self.fe.upload(slot, image)
+            return None
+        if kind == "fast":
+            return self.fe.fast(*req[1:])
+        if kind == "lk":
+            return self.fe.lk(*req[1:], **self.lk_kw)
+        if kind == "stereo_match":
+            return self.fe.stereo_match(*req[1:], **self.lk_kw)
+        if kind == "ransac":
+            fn = self.ransac_fn if self.ransac_fn is not None else self.fe.two_point_ransac
+            return fn(*req[1:])
+        if kind == "fast_grid":
+            return self.fe.fast_grid(*req[1:])
+        if kind == "undistort":
+            return [self.fe.undistort(*a) if len(a[0]) else np.zeros((0, 2)) for a in req[1]]
+        raise ValueError("unknown device request %r" % (kind,))
+
+    def _frame_steps(self, stereo_msg):
+        """stareo_callback; returns the published message."""
+        self.cam0_curr_img_msg = stereo_msg.cam0_msg
+        self.cam1_curr_img_msg = stereo_msg.cam1_msg
+        yield from self._upload_steps()
+        if self.is_first_img:
+            yield from self._first_frame_steps()
+            self.is_first_img = False
+        else:
+            yield from self._track_steps()
+            yield from self._add_new_steps()
+            self.prune_features()
+        try:
+            return (yield from self._publish_steps())
+        finally:
+            self._end_frame()
+
+    def _upload_steps(self):
+        yield ("upload", [(self._slot_c0, self.cam0_curr_img_msg.image),
+                          (self._slot_c1, self.cam1_curr_img_msg.image)])
+
+    def _first_frame_steps(self):
+        xy, resp = yield ("fast", self._slot_c0, self.config.fast_threshold)
+        yield from self._collect_new_steps([tuple(p) for p in xy], list(resp))
+
+    def _collect_new_steps(self, cam0_points, responses):
+        cam1_points, inliers = yield from self._stereo_match_steps(cam0_points)
+        self._assign_new(cam0_points, responses, cam1_points, inliers)
+
+    def _track_steps(self):
+        """track_features, statement for statement, around its three requests."""
+        img = self.cam0_curr_img_msg.image
+        gh, gw = self.get_grid_size(img)
+        cam0_R_p_c, cam1_R_p_c = self.integrate_imu_data()
+        if self.config.ransac_enabled:   # once per tracked frame, whatever the frame holds: a replay repeats
+            draws = self.ransac_rng.integers(0, 1 << 32, size=(2, self.ransac_n_hyp, 2), dtype=np.uint32)
+        prev_ids, prev_lifetime, prev_cam0_points, prev_cam1_points = [], [], [], []
+        for f in chain.from_iterable(self.prev_features):
+            prev_ids.append(f.id)
+            prev_lifetime.append(f.lifetime)
+            prev_cam0_points.append(f.cam0_point)
+            prev_cam1_points.append(f.cam1_point)
+        prev_cam0_points = np.array(prev_cam0_points, dtype=np.float32).reshape(-1, 2)
+        self.num_features["before_tracking"] = len(prev_cam0_points)
+        if len(prev_cam0_points) == 0:
+            return
+        curr_cam0_points = self.predict_feature_tracking(prev_cam0_points, cam0_R_p_c, self.cam0_intrinsics)
+        curr_cam0_points, track_inliers = yield ("lk", self._slot_prev, self._slot_c0, prev_cam0_points,
+                                                 curr_cam0_points)
+        track_inliers = track_inliers.astype(bool)
+        for i, p in enumerate(curr_cam0_points):
+            if not track_inliers[i]:
+                continue
+            if p[0] < 0 or p[0] > img.shape[1] - 1 or p[1] < 0 or p[1] > img.shape[0] - 1:
+                track_inliers[i] = False
+        prev_tracked_ids = _select(prev_ids, track_inliers)
+        prev_tracked_lifetime = _select(prev_lifetime, track_inliers)
+        curr_tracked_cam0_points = _select(curr_cam0_points, track_inliers)
+        self.num_features["after_tracking"] = len(curr_tracked_cam0_points)
+        curr_cam1_points, match_inliers = yield from self._stereo_match_steps(curr_tracked_cam0_points)
+        prev_matched_ids = _select(prev_tracked_ids, match_inliers)
+        prev_matched_lifetime = _select(prev_tracked_lifetime, match_inliers)
+        curr_matched_cam0_points = _select(curr_tracked_cam0_points, match_inliers)
+        curr_matched_cam1_points = _select(curr_cam1_points, match_inliers)
+        self.num_features["after_matching"] = len(curr_matched_cam0_points)
+        ransac_inliers = None
+        if self.config.ransac_enabled:
+            (in0, _), (in1, _) = yield ("ransac", self._ransac_sets(
+                _select(_select(prev_cam0_points, track_inliers), match_inliers), curr_matched_cam0_points,
+                _select(_select(prev_cam1_points, track_inliers), match_inliers), curr_matched_cam1_points,
+                cam0_R_p_c, cam1_R_p_c), self.config.ransac_threshold, self.ransac_n_hyp, draws)
+            ransac_inliers = np.logical_and(in0, in1)
+        after_ransac = 0
+        for i in range(len(curr_matched_cam0_points)):
+            if ransac_inliers is not None and not ransac_inliers[i]:
+                continue
+            f = FeatureMetaData()
+            f.id = prev_matched_ids[i]
+            f.lifetime = prev_matched_lifetime[i] + 1
+            f.cam0_point = curr_matched_cam0_points[i]
+            f.cam1_point = curr_matched_cam1_points[i]
+            self.curr_features[self._grid_code(curr_matched_cam0_points[i], gh, gw)].append(f)
+            after_ransac += 1
+        self.num_features["after_ransac"] = after_ransac
+
+    def _stereo_match_steps(self, cam0_points):
         """stereo_match as the one call mfe_stereo_match.  The equidistant
         quirk of undistort_points (no rectification) is kept by passing the
         identity as the rotation of the initial guess."""
@@ -658,23 +931,43 @@ class ImageProcessor:
         t_cam0_cam1 = self.R_cam1_imu.T @ (self.t_cam0_imu - self.t_cam1_imu)
         E = _skew(t_cam0_cam1) @ R_cam0_cam1
         model0 = _model(self.cam0_distortion_model)
-        c1, inliers, _ = self.fe.stereo_match(
-            self._slot_c0, self._slot_c1, cam0_points,
+        c1, inliers, _ = yield (
+            "stereo_match", self._slot_c0, self._slot_c1, cam0_points,
             (self.cam0_intrinsics, model0, self.cam0_distortion_coeffs),
             (self.cam1_intrinsics, _model(self.cam1_distortion_model), self.cam1_distortion_coeffs),
-            np.identity(3) if model0 == EQUIDISTANT else R_cam0_cam1, E, self.config.stereo_threshold, **self.lk_kw)
+            np.identity(3) if model0 == EQUIDISTANT else R_cam0_cam1, E, self.config.stereo_threshold)
         return [tuple(p) for p in c1], list(inliers.astype(bool))
 
-    def _add_new_features_device(self):
+    def _add_new_steps(self):
         """add_new_features with the mask, the detection and the per-cell sieve
         as the one call mfe_fast_grid.  A cell comes back response-descending
         with raster ties where the sieve leaves a cell of at most
-        grid_max_feature_num in raster order; _collect_new sorts every cell by
+        grid_max_feature_num in raster order; _assign_new sorts every cell by
         response with a stable sort, so the features and their ids are the same."""
         occ = np.array([f.cam0_point for f in chain.from_iterable(self.curr_features)], np.float32).reshape(-1, 2)
-        xy, resp, _, _ = self.fe.fast_grid(self._slot_c0, self.config.fast_threshold, occ, self.config.grid_row,
-                                           self.config.grid_col, self.config.grid_max_feature_num)
-        self._collect_new([tuple(p) for p in xy], list(resp))
+        xy, resp, _, _ = yield ("fast_grid", self._slot_c0, self.config.fast_threshold, occ, self.config.grid_row,
+                                self.config.grid_col, self.config.grid_max_feature_num)
+        yield from self._collect_new_steps([tuple(p) for p in xy], list(resp))
+
+    def _publish_steps(self):
+        """publish: both cameras' points undistorted by one request."""
+        ids, c0, c1 = [], [], []
+        for f in chain.from_iterable(self.curr_features):
+            ids.append(f.id)
+            c0.append(f.cam0_point)
+            c1.append(f.cam1_point)
+        u0, u1 = yield ("undistort", [
+            self._undistort_args(c0, self.cam0_intrinsics, self.cam0_distortion_model, self.cam0_distortion_coeffs),
+            self._undistort_args(c1, self.cam1_intrinsics, self.cam1_distortion_model, self.cam1_distortion_coeffs)])
+        feats = [FeatureMeasurement(ids[i], u0[i][0], u0[i][1], u1[i][0], u1[i][1]) for i in range(len(ids))]
+        return FeatureMsg(self.cam0_curr_img_msg.vio_timestamp__, feats)
+
+    def _undistort_args(self, pts_in, intrinsics, distortion_model, distortion_coeffs):
+        """The arguments undistort_points (below) gives Frontend.undistort
+        without a rectification, the equidistant quirk included."""
+        model = _model(distortion_model)
+        R = np.identity(3)   # K_new of [1 1 0 0] in the R slot, or no rectification: the identity either way
+        return (pts_in, intrinsics, model, distortion_coeffs, R, np.array([1.0, 1.0, 0.0, 0.0]))
 
     def undistort_points(self, pts_in, intrinsics, distortion_model, distortion_coeffs,
                          rectification_matrix=np.identity(3), new_intrinsics=np.array([1, 1, 0, 0])):
@@ -697,3 +990,124 @@ class ImageProcessor:
         if len(pts_in) == 0:
             return np.zeros((0, 2))
         return self.fe.distort(pts_in, intrinsics, _model(distortion_model), distortion_coeffs)
+
+
+# pipeline order of a frame's device requests: a lane waiting at an earlier stage is served first
+_REQUEST_ORDER = {"upload": 0, "fast": 1, "lk": 2, "stereo_match": 3, "ransac": 4, "fast_grid": 5, "undistort": 6}
+# what the set calls share between lanes (msckf_lanes.h): the image size and these fields
+_SHARED_FIELDS = ("pyramid_levels", "patch_size", "max_iteration", "track_precision", "fast_threshold", "grid_row",
+                  "grid_col")
+
+
+class MultiImageProcessor:
+    """``n`` stereo streams (lanes) on one device context: the image-side
+    counterpart of ``scheduler.MultiMSCKF``.  Every lane is an
+    ``ImageProcessor(device_pipeline=True)`` with its own bookkeeping
+    (features, ids, IMU buffer, RANSAC generator) and three slots of the
+    shared context; ``stereo_callbacks`` advances the lanes' frames in lock
+    step and serves each kind of device request for all waiting lanes with ONE
+    call of include/msckf_lanes.h:
+
+      upload       -> mfe_upload_many          lk        -> mfe_lk_sets
+      stereo_match -> mfe_stereo_match_sets    ransac    -> mfe_two_point_ransac
+      fast_grid    -> mfe_fast_grid_sets       undistort -> mfe_undistort_sets
+
+    ``fast`` (a stream's first frame, no per-cell cap) is served per lane with
+    the single call.  Lanes whose frames diverge (one starts late, one runs
+    RANSAC) wait at the earliest stage of ``_REQUEST_ORDER`` first, so requests
+    of one kind merge again.  The set calls compute every set as the single
+    call does, so each lane publishes what an ImageProcessor alone publishes.
+
+    Lanes may differ in calibration, grid_min / grid_max_feature_num,
+    stereo_threshold and the RANSAC switch, threshold and seed; they must
+    agree on the resolution and the fields of ``_SHARED_FIELDS``."""
+
+    def __init__(self, n, config=None, lane_configs=None, device=0):
+        if lane_configs is None:
+            if config is None:
+                config = FrontendConfig()
+            elif not isinstance(config, FrontendConfig):
+                config = FrontendConfig.from_reference(config)
+            cfgs = [FrontendConfig(**{**vars(config), "device_pipeline": True}) for _ in range(n)]
+        else:
+            cfgs = [c if isinstance(c, FrontendConfig) else FrontendConfig.from_reference(c) for c in lane_configs]
+        if len(cfgs) != n or n < 1:
+            raise ValueError("%d lane configs for %d lanes" % (len(cfgs), n))
+        if 3 * n > _lib.MAX_SLOTS:
+            raise ValueError("%d lanes need %d slots, a context holds %d" % (n, 3 * n, _lib.MAX_SLOTS))
+        res = lambda c: (tuple(int(v) for v in c.cam0_resolution), tuple(int(v) for v in c.cam1_resolution))
+        for i, c in enumerate(cfgs):
+            if not c.device_pipeline:
+                raise ValueError("lane %d: device_pipeline is off" % i)
+            if res(c) != res(cfgs[0]) or res(c)[0] != res(c)[1]:
+                raise ValueError("lane %d: resolution %s differs from lane 0's %s" % (i, res(c), res(cfgs[0])))
+            for f in _SHARED_FIELDS:
+                if getattr(c, f) != getattr(cfgs[0], f):
+                    raise ValueError("lane %d: %s = %r differs from lane 0's %r"
+                                     % (i, f, getattr(c, f), getattr(cfgs[0], f)))
+        (W, H), _ = res(cfgs[0])
+        # a call's point limit covers all lanes: a first frame matches every keypoint it detects
+        self.fe = Frontend(W, H, nslot=3 * n, max_level=cfgs[0].pyramid_levels, max_points=n << 16, device=device)
+        self.lanes = [ImageProcessor(c, device=device, fe=self.fe, slot_base=3 * i) for i, c in enumerate(cfgs)]
+        self.lk_kw = self.lanes[0].lk_kw
+        self.launches = defaultdict(int)   # device calls per request kind
+
+    def __len__(self):
+        return len(self.lanes)
+
+    def close(self):
+        self.fe.close()
+
+    def imu_callback(self, i, msg):
+        self.lanes[i].imu_callback(msg)
+
+    def stereo_callbacks(self, msgs):
+        """``msgs``: {lane index: stereo_msg}.  Returns {lane index:
+        FeatureMsg}, as the lanes' own stareo_callback would."""
+        gens, pending, out = {}, {}, {}
+        for i, m in msgs.items():
+            gens[i] = self.lanes[i]._frame_steps(m)
+            self._advance(i, gens[i], None, pending, out, first=True)
+        while pending:
+            kind = min((r[0] for r in pending.values()), key=lambda k: _REQUEST_ORDER[k])
+            group = [i for i, r in pending.items() if r[0] == kind]
+            if kind == "ransac":       # inlier error and hypothesis count are per call
+                group = [i for i in group if pending[i][2:4] == pending[group[0]][2:4]]
+            elif kind == "fast_grid":  # and so is k (grid_max_feature_num)
+                group = [i for i in group if pending[i][6] == pending[group[0]][6]]
+            results = self._serve(kind, [pending[i] for i in group])
+            for i, res in zip(group, results):
+                del pending[i]
+                self._advance(i, gens[i], res, pending, out)
+        return out
+
+    def _advance(self, i, gen, value, pending, out, first=False):
+        try:
+            pending[i] = next(gen) if first else gen.send(value)
+        except StopIteration as e:
+            out[i] = e.value
+
+    def _serve(self, kind, reqs):
+        fe = self.fe
+        if kind == "fast":
+            self.launches[kind] += len(reqs)
+            return [fe.fast(*r[1:]) for r in reqs]
+        self.launches[kind] += 1
+        if kind == "upload":
+            pairs = [p for r in reqs for p in r[1]]
+            fe.upload_many([s for s, _ in pairs], np.stack([np.asarray(im, np.uint8) for _, im in pairs]))
+            return [None] * len(reqs)
+        if kind == "lk":
+            return fe.lk_sets([r[1:] for r in reqs], **self.lk_kw)
+        if kind == "stereo_match":
+            return fe.stereo_match_sets([r[1:] for r in reqs], **self.lk_kw)
+        if kind == "ransac":
+            res = fe.two_point_ransac([s for r in reqs for s in r[1]], reqs[0][2], reqs[0][3],
+                                      np.concatenate([r[4] for r in reqs]))
+            return [res[2 * j:2 * j + 2] for j in range(len(reqs))]
+        if kind == "fast_grid":
+            return fe.fast_grid_sets([(r[1], r[3]) for r in reqs], *reqs[0][2:3], *reqs[0][4:7])
+        if kind == "undistort":
+            res = fe.undistort_sets([a for r in reqs for a in r[1]])
+            return [res[2 * j:2 * j + 2] for j in range(len(reqs))]
+        raise ValueError("unknown device request %r" % (kind,))

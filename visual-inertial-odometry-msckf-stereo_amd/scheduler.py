@@ -31,6 +31,7 @@ import numpy as np
 
 from . import _lib
 from .config import FilterConfig
+from .frontend import MultiImageProcessor  # noqa: F401  (the image-side counterpart, same interface)
 from .msckf import MSCKF
 from .trajectory import Trajectory
 
