@@ -1,5 +1,13 @@
 """Debug: Kalman stage-A workspace (Lc, Vi, S_ii) after one golden update,
-against a numpy partial Cholesky of the input covariance."""
+against a numpy partial Cholesky of the input covariance.
+
+Stage C's buffers are not compared here.  Batches of 64 filters or more (or
+MSCKF_KALMAN_ORDER=reverse) run the register-tile stage C in the reverse pivot
+order (kalman_reverse_order, msckf_kalman.hip): workspace 4 (Tm) is then T in its
+original order, 3 (G, after C1) the factor of J T J, and 5 (W^T, leading
+dimension Dmax + 1) has its K index reversed -- row k belongs to cam index
+C - 1 - k -- and the entries k + r < C - 1 of cam row r are structural zeros
+that stage C2 never writes (they hold whatever was there before)."""
 import ctypes as C
 import os, sys
 import numpy as np

@@ -268,6 +268,7 @@ UpdWs<T> upd_ws(msckf_ctx* c, int b0 = 0) {
     w.W = reinterpret_cast<KT*>(c->W.p) + b * (c->Dmax + 1) * w.Cp;
     w.Wk = c->Wk.p ? reinterpret_cast<KT*>(c->Wk.p) + b * w.wk_stride : nullptr;
     w.s2 = (double)(T)c->cfg.observation_noise;
+    w.rev = kalman_reverse_order(c->B) ? 1 : 0;
     return w;
 }
 
@@ -1524,6 +1525,11 @@ int msckf_kernel_times(msckf_ctx_t* c, int max_k, double* ms_total, int32_t* lau
 
 // Debug (not in include/msckf_hip.h): copy the first `count` doubles of a
 // Kalman workspace buffer (0 Lc, 1 Vi, 2 Sii, 3 G, 4 Tm, 5 W, 6 H_thin [A | b], 7 afail (ints)) to the host.
+// Where stage C runs in the reverse pivot order (kalman_reverse_order, msckf_kalman.hip:
+// register-tile windows in batches of 64 filters or more, or MSCKF_KALMAN_ORDER=reverse),
+// 4 is T in its original order, 3 (after C1) the factor of J T J, and 5 is W J L~^-T
+// with its K index reversed -- row k of W^T belongs to cam index C - 1 - k, and the
+// entries k + r < C - 1 of cam row r are structural zeros that are never written.
 int msckf_debug_workspace(msckf_ctx_t* c, int which, double* out, size_t count) {
     if (!c || !out) FAIL(-1, "null argument");
     JOIN_LANES(c);
@@ -1537,13 +1543,15 @@ int msckf_debug_workspace(msckf_ctx_t* c, int which, double* out, size_t count) 
 }
 
 // Debug (not in include/msckf_hip.h): overwrite the first `count` doubles of a
-// Kalman workspace buffer (6: H_thin [A | b], [B][Cmax][Cmax + 1]) from the host.
+// Kalman workspace buffer (6: H_thin [A | b], [B][Cmax][Cmax + 1]; 5: W,
+// [B][Dmax + 1][Cp] -- to poison what stage E must not read) from the host.
 int msckf_debug_set_workspace(msckf_ctx_t* c, int which, const double* in, size_t count) {
     if (!c || !in) FAIL(-1, "null argument");
     JOIN_LANES(c);
-    void* dst = which == 6 ? (void*)c->Hthin.p : nullptr;
+    void* dst = which == 6 ? (void*)c->Hthin.p : which == 5 ? (void*)c->W.p : nullptr;
     if (!dst) FAIL(-1, "unknown workspace %d", which);
-    if (count * sizeof(double) > c->Hthin.cap) FAIL(-1, "%zu doubles exceed H_thin", count);
+    if (count * sizeof(double) > (which == 6 ? c->Hthin.cap : c->W.cap))
+        FAIL(-1, "%zu doubles exceed workspace %d", count, which);
     HIPSYNC(c, hipStreamSynchronize(c->stream));
     HIPC(hipMemcpy(dst, in, count * sizeof(double), hipMemcpyHostToDevice));
     return 0;

@@ -124,6 +124,7 @@ struct UpdWs {
     int* afail;  // [B]                  stage A status (1: P_cc not PD), written by every k_kal_a run
     size_t wk_stride;
     int Cp;
+    int rev;     // register-tile stage C in the reverse pivot order (kalman_reverse_order, msckf_kalman.hip)
     double s2;   // observation noise variance in the context's type, as Params::sigma2: T >= s2 I
 };
 

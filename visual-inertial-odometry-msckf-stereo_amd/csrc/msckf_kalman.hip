@@ -12,7 +12,9 @@
 //                pivots: Lc, Vc_i = P_ic Lc^-T, S_ii = P_ii - Vc_i Vc_i^T
 //   B  k_kal_b   [T | c] = s2 I + Lc^T [A Lc | b] (fp64 MFMA accumulators)
 //   C  k_kal_c1  Cholesky of T; k_kal_c2: W^T = L_T^-1 [Vc_i ; Lc]^T and
-//                y = L_T^-1 c (MFMA blocked forward substitution)
+//                y = L_T^-1 c (MFMA blocked forward substitution); large
+//                batches of register-tile windows factor T in the reverse
+//                pivot order, which leaves half of the Lc rows' W zero
 //   E  k_kal_e1  P+ = blockdiag(S_ii, 0) + s2 W W^T and dx = W y
 // Up to 32 cams A and C1 keep the matrix in registers as 4x4 tiles (one
 // workgroup per filter); larger windows run A and C as blocked global-memory
@@ -119,9 +121,21 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 2
 }
 
 // ---- stage C (register-tile windows, C <= 192) ----
-// C1: Cholesky of T alone (4x4 register tiles, one workgroup per filter), L_T
-//     written over the G workspace (free after stage B).
-// C2: W^T = L_T^-1 X^T with X = [Vc_i ; Lc ; c^T] (E = 22 + C rows) as a
+// With UpdWs::rev (kalman_reverse_order: batches of MK_MIN_B filters or more)
+// stage C works in the reverse pivot order: with J the reversal of the live
+// cam index 0 .. C-1 (the filter's own C, not Cmax; padding beyond C stays
+// identity), C1 factors J T J = L_T L_T^T and C2 solves the right-hand sides
+// X J.  W W^T = Vc T^-1 Vc^T and W y are the same in either order, so stage E
+// and dx do not change; what changes is where Lc's zeros fall: cam row r of
+// X J is Lc[r][C-1-k], zero for k < C-1-r, and a forward substitution keeps
+// leading zeros -- W[21 + r][k] = 0 for k + r < C - 1 (half of the Lc rows'
+// part of W), which C2 neither computes nor stores and E1 neither loads nor
+// multiplies.  (In the forward order the zeros trail each right-hand side and
+// the solution is dense.)  The loaders of C1 apply J; stage B and Tm keep the
+// original order.
+// C1: Cholesky of T (rev: J T J) alone (4x4 register tiles, one workgroup per
+//     filter), L_T written over the G workspace (free after stage B).
+// C2: W^T = L_T^-1 X^T with X = [Vc_i ; Lc ; c^T] (rev: X J; E = 22 + C rows) as a
 //     blocked forward substitution on MFMA: wave w owns the 16-row tiles
 //     ct = w + NW t of X and keeps the solved blocks Y'[K] (16 x 16, K < nT) in
 //     registers -- in the MFMA result layout (row = lane/16 + 4 r, col =
@@ -129,8 +143,11 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 2
 //     k-step r, so no block is re-read.  Step J:
 //         Y'[J] = Linv_JJ (X^T[J] - sum_{K<J} L_T[J, K] Y'[K])
 //     with -L_T[J, 0:16J] staged in LDS ([col][row], 17-double rows) and the
-//     16 x 16 inverses of the diagonal blocks formed once up front.  W^T is
-//     stored row-major over k (coalesced), the layout k_kal_e1 reads.
+//     16 x 16 inverses of the diagonal blocks formed once up front.  With rev a
+//     tile of Lc rows alone starts at step J0 = (C - 1 - its last cam row) / 16 (every
+//     earlier block is zero); tiles with an IMU row or the c row start at 0.
+//     W^T is stored row-major over k (coalesced), the layout k_kal_e1 reads;
+//     the blocks before J0 are not stored.
 template <typename T, int NT, int TPL>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 256 ? 2 : 1))) k_kal_c1(DevState<T> st, UpdWs<T> ws) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -144,9 +161,11 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 2
     const int ldt = ws.Cmax + 1;
     const KT* Tm = ws.Tm + (size_t)b * ws.Cmax * ldt;
     KT* L = ws.G + (size_t)b * ws.Cmax * ldt;
-    auto load = [&](int i, int j) -> double {
+    const bool rev = ws.rev;
+    auto load = [&](int i, int j) -> double {   // rev: J T J, the reversal of the live cam index (above)
         if (i >= C || j >= C) return i == j ? 1.0 : 0.0;
-        return i >= j ? Tm[(size_t)i * ldt + j] : Tm[(size_t)j * ldt + i];
+        const int ri = rev ? C - 1 - i : i, rj = rev ? C - 1 - j : j;
+        return ri >= rj ? Tm[(size_t)ri * ldt + rj] : Tm[(size_t)rj * ldt + ri];
     };
     auto panel = [&](int r, int c0, double w0, double w1, double w2, double w3) {
         if (r >= C) return;
@@ -224,14 +243,25 @@ __global__ void __launch_bounds__(64 * NW) k_kal_c2(DevState<T> st, UpdWs<T> ws)
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
-    auto Xv = [&](int e, int j) -> double {   // X[e][j]
-        if (j >= C) return 0.0;
+    const bool rev = ws.rev;
+    auto Xv = [&](int e, int k) -> double {   // X[e][k]; rev: (X J)[e][k] = X[e][C - 1 - k]; zero padding beyond C
+        if (k >= C) return 0.0;
+        const int j = rev ? C - 1 - k : k;
         if (e < 21) return Vi[(size_t)e * Cpw + j];
         if (e < 21 + C) return j <= e - 21 ? Lc[(size_t)(e - 21) * Cpw + j] : 0.0;
         if (e == 21 + C) return Tm[(size_t)j * ldt + C];
         return 0.0;
     };
     v4d yk[CT][NTM];
+    // first step of each tile: in the reverse order a tile of Lc rows alone (no
+    // IMU row, no c row) is zero in the columns k < C - 1 - r_max, r_max its last
+    // cam row
+    int J0[CT];
+#pragma unroll
+    for (int t = 0; t < CT; ++t) {
+        const int e0 = 16 * (wv + NW * t), e1 = e0 + 15;
+        J0[t] = __builtin_amdgcn_readfirstlane(rev && e0 >= 21 && e1 < 21 + C ? (C - 1 - (e1 - 21)) / 16 : 0);
+    }
     // -L_T[16J : 16J+16, 0 : 16J] is software-pipelined: block row J + 1 is
     // loaded into registers while step J runs its MFMAs, and stored to LDS
     // after step J's closing barrier
@@ -267,7 +297,7 @@ __global__ void __launch_bounds__(64 * NW) k_kal_c2(DevState<T> st, UpdWs<T> ws)
     for (int t = 0; t < CT; ++t) {
         const int ct = wv + NW * t;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) xn[t][q] = ct < nE ? Xv(16 * ct + lc, lr + 4 * q) : 0.0;
+        for (int q = 0; q < 4; ++q) xn[t][q] = ct < nE && J0[t] == 0 ? Xv(16 * ct + lc, lr + 4 * q) : 0.0;
     }
 #pragma unroll
     for (int J = 0; J < NTM; ++J) {
@@ -280,13 +310,18 @@ __global__ void __launch_bounds__(64 * NW) k_kal_c2(DevState<T> st, UpdWs<T> ws)
             const int ct = wv + NW * t;
             if (ct >= nE) continue;
             v4d a0 = xn[t], a1 = v4d{0.0, 0.0, 0.0, 0.0};
-            if (J + 1 < nT) {   // X^T[J + 1] for the next step, loaded under this one
+            if (J + 1 < nT && J + 1 >= J0[t]) {   // X^T[J + 1] for the next step, loaded under this one
 #pragma unroll
                 for (int q = 0; q < 4; ++q) xn[t][q] = Xv(16 * ct + lc, 16 * (J + 1) + lr + 4 * q);
+            }
+            if (J < J0[t]) {   // uniform: Y'[J] = 0, neither computed nor stored
+                yk[t][J] = a1;
+                continue;
             }
             const double* im = imgJ(J);
 #pragma unroll
             for (int K = 0; K < J; ++K) {
+                if (K < J0[t]) continue;   // uniform: Y'[K] = 0
 #pragma unroll
                 for (int kc = 0; kc < 4; ++kc) {
                     const double av = im[(16 * K + 4 * kc + lr) * C2S + lc];
@@ -308,7 +343,7 @@ __global__ void __launch_bounds__(64 * NW) k_kal_c2(DevState<T> st, UpdWs<T> ws)
         if (ct >= nE || col >= E) continue;
 #pragma unroll
         for (int J = 0; J < NTM; ++J) {
-            if (J >= nT) continue;
+            if (J >= nT || J < J0[t]) continue;   // (stage E masks the unwritten zeros by index)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int k = 16 * J + lr + 4 * q;
@@ -954,15 +989,30 @@ __global__ void __launch_bounds__(64 * NW) k_kal_e1(DevState<T> st, Params<T> pr
     const KT* W = ws.W + (size_t)b * (st.Dmax + 1) * Cpw;
     double* img = reinterpret_cast<double*>(smem_raw);   // [2][16][Dp] chunk images, then [2][16] y
     double* yb = img + 2 * 16 * Dp;
-    int ti[TPW], tj[TPW];
+    // W[21 + r][k] = 0 for k + r < C - 1 (reverse pivot order, header of stage
+    // C): the rows of tile column tj >= 2 are cam rows up to r_max, so a tile
+    // (ti >= tj) is zero in the chunks before kf = (C - 1 - r_max) / 16.  kf falls
+    // with tj; the tiles are dealt column by column, columns 0 and 1 (kf = 0)
+    // first and then from the last column down, so that every chunk's active
+    // tiles are a prefix of the deal and the round-robin spreads them evenly.
+    int ti[TPW], tj[TPW], kf[TPW];
 #pragma unroll
-    for (int s = 0; s < TPW; ++s) {   // row-major lower enumeration of the tile grid
+    for (int s = 0; s < TPW; ++s) {
         const int t = wv + NW * s;
-        int i = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-        while (i * (i + 1) / 2 > t) --i;
-        while ((i + 1) * (i + 2) / 2 <= t) ++i;
-        ti[s] = __builtin_amdgcn_readfirstlane(t < ntiles ? i : -1);
-        tj[s] = __builtin_amdgcn_readfirstlane(t - i * (i + 1) / 2);
+        int c = 0, rem = t;
+        if (rem >= nT) {
+            rem -= nT;
+            c = 1;
+            if (rem >= nT - 1) {
+                rem -= nT - 1;
+                c = nT - 1;
+                while (c > 1 && rem >= nT - c) { rem -= nT - c; --c; }
+            }
+        }
+        const int rmax = (16 * c + 15 < D ? 16 * c + 15 : D - 1) - 21;
+        ti[s] = __builtin_amdgcn_readfirstlane(t < ntiles ? c + rem : -1);
+        tj[s] = __builtin_amdgcn_readfirstlane(c);
+        kf[s] = __builtin_amdgcn_readfirstlane(ws.rev && c >= 2 ? (C - 1 - rmax) / 16 : 0);
     }
     v4d acc[TPW];
 #pragma unroll
@@ -978,8 +1028,11 @@ __global__ void __launch_bounds__(64 * NW) k_kal_e1(DevState<T> st, Params<T> pr
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
             const int e = tid + NT * q;
-            const int k = e / Dp, row = e - k * Dp;
-            rw[q] = (e < 16 * Dp && row < D && k0 + k < C) ? W[(size_t)(k0 + k) * ldw + row] : 0.0;
+            const int k = e / Dp, row = e - k * Dp, gk = k0 + k;
+            // the structural zeros are masked by index: C2 does not store them,
+            // and W keeps what earlier (larger) windows left there
+            const bool zero = ws.rev && row >= 21 && gk + row - 21 < C - 1;
+            rw[q] = (e < 16 * Dp && row < D && gk < C && !zero) ? W[(size_t)gk * ldw + row] : 0.0;
         }
         if (tid < 16) ry = k0 + tid < C ? W[(size_t)(k0 + tid) * ldw + D] : 0.0;
     };
@@ -1005,7 +1058,7 @@ __global__ void __launch_bounds__(64 * NW) k_kal_e1(DevState<T> st, Params<T> pr
             const double* kr = im + (4 * kc + lr) * Dp;
 #pragma unroll
             for (int s = 0; s < TPW; ++s) {
-                if (ti[s] < 0) continue;
+                if (ti[s] < 0 || it < kf[s]) continue;   // uniform
                 acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(kr[16 * ti[s] + lc], kr[16 * tj[s] + lc], acc[s], 0, 0, 0);
             }
         }
@@ -1093,7 +1146,8 @@ __device__ __forceinline__ bool mk_factor(const DevState<T>& st, const UpdWs<T>&
             return (double)P[(size_t)mi * ld + mj] + (i == j && i < C ? shift : 0.0);
         } else {
             if (i >= C || j >= C) return i == j ? 1.0 : 0.0;
-            return i >= j ? Tm[(size_t)i * ldt + j] : Tm[(size_t)j * ldt + i];
+            const int ri = ws.rev ? C - 1 - i : i, rj = ws.rev ? C - 1 - j : j;   // rev: J T J (k_kal_c1)
+            return ri >= rj ? Tm[(size_t)ri * ldt + rj] : Tm[(size_t)rj * ldt + ri];
         }
     };
     // blocks of this wave: t = wv + NW j, column-major lower order
@@ -1385,6 +1439,22 @@ static bool use_mk(int batch_B) {
     if (const char* e = getenv("MSCKF_KALMAN_CHOL")) {
         if (e[0] == 'm') return true;
         if (e[0] == 't') return false;
+    }
+    return batch_B >= MK_MIN_B;
+}
+
+// Stage C's pivot order (UpdWs::rev): batches that fill the chip factor T in
+// the reverse order, which halves the Lc rows' share of C2 and E1.  The
+// per-frame path (fewer than MK_MIN_B filters) keeps the forward order: it is
+// latency-bound either way, and on golden stream s4 (cond(T) beyond 1 / eps) the
+// reverse order floors other pivots and one falls below -T_FLOOR_NEG x max
+// diag(T) (test_sequence_s4_mfma_cholesky: rc -3 with the reverse order).
+// MSCKF_KALMAN_ORDER=reverse / forward (environment, read per update) forces
+// one order -- the parity tests run both on the same inputs.
+bool kalman_reverse_order(int batch_B) {
+    if (const char* e = getenv("MSCKF_KALMAN_ORDER")) {
+        if (e[0] == 'r') return true;
+        if (e[0] == 'f') return false;
     }
     return batch_B >= MK_MIN_B;
 }

@@ -151,6 +151,9 @@ bool info_fused_fits(int Nmax, int maxnf);
 inline bool feature_needs_compact(int maxM) { return maxM > GATE_TILE_MAXM; }
 bool kalman_chol_supported(int Cmax);
 size_t kalman_global_ws_doubles(int Cmax);
+// UpdWs::rev: whether the register-tile stage C of a batch of batch_B filters
+// factors T in the reverse pivot order (msckf_kalman.hip)
+bool kalman_reverse_order(int batch_B);
 // Stage A of the register-tile windows (kalman_chol_supported) reads only P and
 // writes only Lc / Vi / Sii / afail, so it is launched on a side stream at the
 // start of the update chain; launch_kalman_chol then skips it.
