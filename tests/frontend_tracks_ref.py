@@ -1,0 +1,190 @@
+"""CPU restatement of include/msckf_tracks.h (the header's text is the
+specification): steps 1-9 of mfe_tracks_step in numpy around an operator object
+``ops`` with the set calls of include/msckf_lanes.h (``lk_sets``,
+``stereo_match_sets``, ``two_point_ransac``, ``fast_grid_sets``,
+``undistort_sets``).  With the CPU stand-in as ``ops`` it is the reference of
+tests/test_tracks_ref.py; with the real ``Frontend`` every stage is a device
+call already pinned by tests/test_gpu_lanes.py and tests/test_gpu_ransac.py,
+and tests/test_gpu_tracks.py demands mfe_tracks_step equal it bit for bit.
+
+``step`` also counts what its inputs exercised (``cover``), so that a test can
+assert its scenes reach every branch from the reference alone.
+
+``TracksOracleFrontend`` is the CPU stand-in of msckf_amd.frontend.Frontend
+with the four tracks calls built on ``step``; it logs ONE ``tracks_step`` entry
+per call."""
+from collections import Counter, namedtuple
+
+import numpy as np
+
+import msckf_amd.frontend as fe_mod
+from msckf_amd import _lib
+import frontend_lanes_ref as lr
+
+Table = namedtuple("Table", ["ids", "life", "cam0", "cam1", "next_id"])
+Grid = namedtuple("Grid", ["rows", "cols", "gmin", "gmax"])
+
+
+def empty_table(next_id=0):
+    return Table(np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros((0, 2), np.float32),
+                 np.zeros((0, 2), np.float32), int(next_id))
+
+
+def make_table(ids, life, cam0, cam1, next_id):
+    return Table(np.asarray(ids, np.int64).reshape(-1).copy(), np.asarray(life, np.int32).reshape(-1).copy(),
+                 np.asarray(cam0, np.float32).reshape(-1, 2).copy(), np.asarray(cam1, np.float32).reshape(-1, 2).copy(),
+                 int(next_id))
+
+
+def min_cap(grid):
+    return grid.rows * grid.cols * (grid.gmin + grid.gmax)
+
+
+def cell_of(pts, W, H, grid):
+    """Step 5: _grid_code, the divisions in float32, truncated."""
+    p = np.asarray(pts, np.float32).reshape(-1, 2)
+    gh, gw = np.float32(-(-H // grid.rows)), np.float32(-(-W // grid.cols))
+    return (p[:, 1] / gh).astype(np.int64) * grid.cols + (p[:, 0] / gw).astype(np.int64)
+
+
+def predict(Hpred, cam0):
+    """Step 1, element by element: q_r = H[3r] x + H[3r+1] y + H[3r+2] left to right."""
+    h = np.asarray(Hpred, float).ravel()
+    x, y = cam0[:, 0].astype(float), cam0[:, 1].astype(float)
+    q = [(h[3 * r] * x + h[3 * r + 1] * y) + h[3 * r + 2] for r in range(3)]
+    with np.errstate(all="ignore"):
+        return np.stack([(q[0] / q[2]).astype(np.float32), (q[1] / q[2]).astype(np.float32)], axis=1).reshape(-1, 2)
+
+
+def step(ops, tables, lanes, grid, W, H, threshold, max_kp=1 << 16, inlier_error=0.0, n_hyp=0, **lk):
+    """One mfe_tracks_step.  ``tables``: {lane: Table} (not modified);
+    ``lanes``: msckf_amd.frontend.TracksLane per named lane.  Returns
+    (results, next tables {lane: Table}, cover Counter); results as
+    Frontend.tracks_step returns them."""
+    S, cells, cover = len(lanes), grid.rows * grid.cols, Counter()
+    tabs = [tables[a.lane] for a in lanes]
+    ctr = np.zeros((S, 4), np.int32)
+    # steps 1-2
+    got = ops.lk_sets([(a.slot_prev, a.slot_c0, t.cam0, predict(a.Hpred, t.cam0)) for a, t in zip(lanes, tabs)], **lk)
+    rows, c0 = [], []
+    for i, (t, (q, st)) in enumerate(zip(tabs, got)):
+        q = np.asarray(q, np.float32).reshape(-1, 2)
+        st = np.asarray(st).astype(bool)
+        outside = (q[:, 0] < 0) | (q[:, 0] > W - 1) | (q[:, 1] < 0) | (q[:, 1] > H - 1)
+        cover["lk_status"] += int((~st).sum())
+        cover["bounds"] += int((st & outside).sum())
+        cover["empty_table"] += int(len(t.ids) == 0)
+        rows.append(np.nonzero(st & ~outside)[0])
+        c0.append(q)
+        ctr[i, 0], ctr[i, 1] = len(t.ids), len(rows[i])
+    # step 3
+    stereo = lambda i, pts: (lanes[i].slot_c0, lanes[i].slot_c1, np.asarray(pts, np.float32).astype(float),
+                             lanes[i].cam0, lanes[i].cam1, lanes[i].R_guess, lanes[i].E, lanes[i].stereo_threshold)
+    got = ops.stereo_match_sets([stereo(i, c0[i][rows[i]]) for i in range(S)], **lk)
+    c1 = []
+    for i, (m, inl, _) in enumerate(got):
+        full = np.zeros((len(tabs[i].ids), 2), np.float32)
+        full[rows[i]] = np.asarray(m, np.float32).reshape(-1, 2)
+        c1.append(full)
+        inl = np.asarray(inl).astype(bool)
+        cover["stereo"] += int((~inl).sum())
+        rows[i] = rows[i][inl]
+        ctr[i, 2] = len(rows[i])
+    # step 4
+    rs = [i for i, a in enumerate(lanes) if a.ransac is not None]
+    if rs:
+        sets, draws = [], []
+        for i in rs:
+            a, t, r = lanes[i], tabs[i], rows[i]
+            sets += [(t.cam0[r].astype(float), c0[i][r].astype(float), a.ransac[0], a.cam0[0], a.cam0[1], a.cam0[2]),
+                     (t.cam1[r].astype(float), c1[i][r].astype(float), a.ransac[1], a.cam1[0], a.cam1[1], a.cam1[2])]
+            draws.append(np.asarray(a.ransac[2], np.uint32))
+        got = ops.two_point_ransac(sets, inlier_error, n_hyp, np.concatenate(draws))
+        for j, i in enumerate(rs):
+            keep = np.logical_and(got[2 * j][0], got[2 * j + 1][0])
+            cover["ransac"] += int((~keep).sum())
+            rows[i] = rows[i][keep]
+    ctr[:, 3] = [len(r) for r in rows]
+    # step 6
+    got = ops.fast_grid_sets([(a.slot_c0, c0[i][rows[i]]) for i, a in enumerate(lanes)], threshold, grid.rows,
+                             grid.cols, grid.gmax, max_kp)
+    cand = [(np.asarray(g[0], np.float32).reshape(-1, 2), np.asarray(g[2]), int(g[3])) for g in got]
+    # step 7
+    got = ops.stereo_match_sets([stereo(i, cand[i][0]) for i in range(S)], **lk)
+    results, nxt = [], {}
+    und = []
+    for i, (a, t) in enumerate(zip(lanes, tabs)):
+        xy, cnt, n_total = cand[i]
+        m1, inl = np.asarray(got[i][0], np.float32).reshape(-1, 2), np.asarray(got[i][1]).astype(bool)
+        r = rows[i]
+        code = cell_of(c0[i][r], W, H, grid)
+        cover["cell_change"] += int((code != cell_of(t.cam0[r], W, H, grid)).sum())
+        cover["no_survivors"] += int(len(t.ids) > 0 and len(r) == 0)
+        out, next_id, start = [], t.next_id, 0
+        for cell in range(cells):
+            kept = min(grid.gmax, int(cnt[cell]))
+            new = [start + q for q in range(kept) if inl[start + q]][:grid.gmin]
+            start += kept
+            cover["new_none"] += int(len(new) == 0)
+            cover["new_fewer"] += int(0 < len(new) < grid.gmin)
+            # (id, lifetime, cam0, cam1): the survivors in previous-table order, then the new rows
+            feats = [(int(t.ids[k]), int(t.life[k]) + 1, c0[i][k], c1[i][k]) for k in r[code == cell]]
+            for q in new:
+                feats.append((next_id, 1, xy[q], m1[q]))
+                next_id += 1
+            if len(feats) > grid.gmax:                               # step 8
+                lives = [f[1] for f in feats]
+                cover["pruned_tie"] += int(len(set(lives)) < len(lives))
+                feats = sorted(feats, key=lambda f: -f[1])[:grid.gmax]      # stable
+            out += feats
+        tab = make_table([f[0] for f in out], [f[1] for f in out], [f[2] for f in out], [f[3] for f in out], next_id)
+        nxt[a.lane] = tab
+        und += [(tab.cam0.astype(float), a.cam0[0], a.cam0[1], a.cam0[2], np.identity(3), np.array([1.0, 1.0, 0.0, 0.0])),
+                (tab.cam1.astype(float), a.cam1[0], a.cam1[1], a.cam1[2], np.identity(3), np.array([1.0, 1.0, 0.0, 0.0]))]
+        results.append([len(out), tab.ids.copy(), None, ctr[i].copy(), n_total, next_id])
+    uv = ops.undistort_sets(und)                                    # step 9
+    for i, res in enumerate(results):
+        res[2] = np.concatenate([np.asarray(uv[2 * i], float).reshape(-1, 2),
+                                 np.asarray(uv[2 * i + 1], float).reshape(-1, 2)], axis=1)
+    return [fe_mod.TracksResult(*r) for r in results], nxt, cover
+
+
+class TracksOracleFrontend(lr.LanesOracleFrontend):
+    """LanesOracleFrontend with the calls of include/msckf_tracks.h."""
+
+    def _fail(self, text):
+        raise _lib.MsckfError("mfe: %s (rc=-1)" % text)
+
+    def tracks_create(self, n_lanes, cap, grid_row, grid_col, grid_min, grid_max):
+        self.calls.append("tracks_create")
+        grid = Grid(int(grid_row), int(grid_col), int(grid_min), int(grid_max))
+        if hasattr(self, "grid"):
+            self._fail("the context has its track tables already")
+        if not (1 <= n_lanes and 3 * n_lanes <= self.nslot and 1 <= grid.gmax <= _lib.GRID_MAX_K and grid.gmin >= 0 and
+                1 <= grid.rows * grid.cols <= _lib.GRID_MAX_CELLS and
+                min_cap(grid) <= cap <= _lib.RANSAC_MAX_SET_POINTS):
+            self._fail("tracks_create arguments outside the limits of msckf_tracks.h")
+        self.grid, self.tracks_cap = grid, int(cap)
+        self.tables = {i: empty_table() for i in range(n_lanes)}
+
+    def tracks_put(self, lane, ids, lifetimes, cam0, cam1, next_id):
+        self.calls.append("tracks_put")
+        t = make_table(ids, lifetimes, cam0, cam1, next_id)
+        if lane not in self.tables or len(t.ids) + self.grid.rows * self.grid.cols * self.grid.gmin > self.tracks_cap:
+            self._fail("bad lane or n")
+        self.tables[lane] = t
+
+    def tracks_get(self, lane):
+        self.calls.append("tracks_get")
+        t = self.tables[lane]
+        return t.ids.copy(), t.life.copy(), t.cam0.copy(), t.cam1.copy(), t.next_id
+
+    def tracks_step(self, lanes, threshold, max_kp=1 << 16, inlier_error=0.0, n_hyp=0, **lk):
+        self.calls.append("tracks_step")
+        named = [a.lane for a in lanes]
+        if len(set(named)) != len(named) or any(a not in self.tables for a in named):
+            self._fail("bad lane list")
+        res, nxt, self.cover = self._quiet(step, self, self.tables, lanes, self.grid, self.W, self.H, threshold,
+                                           max_kp, inlier_error, n_hyp, **lk)
+        self.tables.update(nxt)
+        return res

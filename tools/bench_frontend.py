@@ -23,7 +23,13 @@ by lane.  Lane-frames/s of both as the means of two alternated runs, the
 device calls per step of each, and a cProfile split of (b)'s host time (a
 further, untimed run).
 
-    python tools/bench_frontend.py [--frames 60] [--device-pipeline] [--lanes S]
+--lanes S --device-tracks adds (c): the MultiImageProcessor with
+FrontendConfig.device_tracks (include/msckf_tracks.h: the tracks on the device,
+one call per tracked frame of all lanes).  Its messages must be identical too;
+(b) and (c) alternate, two runs each, and the JSON line gains (c)'s
+lane-frames/s, its device calls per step and a cProfile split of its host time.
+
+    python tools/bench_frontend.py [--frames 60] [--device-pipeline] [--lanes S [--device-tracks]]
 """
 import argparse
 import cProfile
@@ -184,6 +190,36 @@ def profile_split(prof):
             "lane_generators_s": round(adv, 4), "scheduling_rest_s": round(total - adv - sum(dev.values()), 4)}
 
 
+def profile_split_tracks(prof):
+    """Cumulative seconds of (c)'s steps: the two device calls of a tracked
+    frame through the binding, the host work per lane before the call
+    (_tracks_lane: IMU integration, draws, homography) and the rest (building
+    the messages)."""
+    st = pstats.Stats(prof).stats
+    cum = lambda name: sum(v[3] for (f, _, fn), v in st.items() if fn == name and f.endswith("frontend.py"))
+    total = cum("stereo_callbacks")
+    dev = {k: round(cum(k), 4) for k in ("upload_many", "tracks_step")}
+    args = cum("_tracks_lane")
+    return {"stereo_callbacks_s": round(total, 4), "device_calls_s": dev, "device_calls_total_s": round(sum(dev.values()), 4),
+            "lane_arguments_s": round(args, 4), "messages_rest_s": round(total - args - sum(dev.values()), 4)}
+
+
+def tracks_leg(cfg, streams, msgs_a, fb):
+    """(c) next to (b): b, c, b, c after lanes_main's first (b)."""
+    cfg_t = fe_mod.FrontendConfig(**{**vars(cfg), "device_tracks": True})
+    fc, msgs_c, calls_c = run_multi(cfg_t, streams)
+    for i, (ma, mc) in enumerate(zip(msgs_a, msgs_c)):
+        if ma != mc:
+            raise SystemExit("lane %d: MultiImageProcessor with device_tracks published different messages" % i)
+    runs_b, runs_c = [fb, run_multi(cfg, streams)[0]], [fc, run_multi(cfg_t, streams)[0]]
+    prof = cProfile.Profile()
+    run_multi(cfg_t, streams, profile=prof)
+    return {"lane_frames_per_s": {"multi_image_processor": [round(v, 1) for v in runs_b],
+                                  "device_tracks": [round(v, 1) for v in runs_c]},
+            "device_calls_per_step": round(calls_c, 2), "messages_identical": True,
+            "host_profile": profile_split_tracks(prof)}
+
+
 def lanes_main(a, cfg, W, H):
     cfg = fe_mod.FrontendConfig(**{**vars(cfg), "device_pipeline": True})
     streams = lane_streams(a.lanes, a.frames, W, H)       # rendered up front: not part of the timing
@@ -192,6 +228,7 @@ def lanes_main(a, cfg, W, H):
     for i, (ma, mb) in enumerate(zip(msgs_a, msgs_b)):
         if ma != mb:
             raise SystemExit("lane %d: MultiImageProcessor published different messages" % i)
+    tracks = {"device_tracks": tracks_leg(cfg, streams, msgs_a, fb)} if a.device_tracks else {}
     fa = 0.5 * (fa + run_singles(cfg, streams)[0])        # a, b, a, b: the means of two runs each
     fb = 0.5 * (fb + run_multi(cfg, streams)[0])
     prof = cProfile.Profile()
@@ -202,7 +239,7 @@ def lanes_main(a, cfg, W, H):
                       "lane_frames_per_s": {"single_processors": round(fa, 1), "multi_image_processor": round(fb, 1)},
                       "device_calls_per_step": {"single_processors": round(calls_a, 2),
                                                 "multi_image_processor": round(calls_b, 2)},
-                      "features_per_frame": nfeat, "multi_host_profile": profile_split(prof),
+                      "features_per_frame": nfeat, "multi_host_profile": profile_split(prof), **tracks,
                       "note": "timed from step 2 on; the profile is a separate run under cProfile, which slows "
                               "the host: read it as shares, not as times"}))
 
@@ -214,7 +251,11 @@ def main():
                     help="run this many streams through single processors and through MultiImageProcessor")
     ap.add_argument("--device-pipeline", action="store_true",
                     help="also run the stream with FrontendConfig.device_pipeline on")
+    ap.add_argument("--device-tracks", action="store_true",
+                    help="with --lanes: also run the MultiImageProcessor with FrontendConfig.device_tracks")
     a = ap.parse_args()
+    if a.device_tracks and not a.lanes:
+        ap.error("--device-tracks needs --lanes")
     W, H = 752, 480
     f = fs.texture_fn(4, W=W, H=H)
     K = np.array([450.0, 450.0, 376.0, 240.0])

@@ -133,6 +133,20 @@ FRONTEND_LANES_SIGS = {
 }
 FRONTEND_LANES_EXPORTED = tuple(FRONTEND_LANES_SIGS)
 
+_I64 = C.POINTER(C.c_int64)
+# the feature tracks kept on the device, one call per tracked frame (include/msckf_tracks.h),
+# same library and context
+TRACKS_COUNTERS = 4
+FRONTEND_TRACKS_SIGS = {
+    "mfe_tracks_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mfe_tracks_put": (C.c_int, [_P, C.c_int, C.c_int, _I64, _I, _F, _F, C.c_int64]),
+    "mfe_tracks_get": (C.c_int, [_P, C.c_int, _I, _I64, _I, _F, _F, _I64]),
+    "mfe_tracks_step": (C.c_int, [_P, C.c_int, _I, _I, _I, _I, _D, _D, _I, _D, _D, _I, _D, _D, _D, _D, _I, _D, _D,
+                                  _U32, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double,
+                                  C.c_int, _I, _I64, _D, _I, _I, _I64]),
+}
+TRACKS_EXPORTED = tuple(FRONTEND_TRACKS_SIGS)
+
 # multi-GPU replica transport, RCCL (include/msckf_replicas.h), same library
 REPLICA_SIGS = {
     "msckf_rccl_unique_id": (C.c_int, [_U8]),
@@ -160,7 +174,7 @@ def load_library(path: str = LIB_PATH):
         lib = C.CDLL(path)
         for name, (res, args) in (list(_SIGS.items()) + list(FRONTEND_SIGS.items()) +
                                   list(FRONTEND_RANSAC_SIGS.items()) + list(FRONTEND_PIPELINE_SIGS.items()) +
-                                  list(FRONTEND_LANES_SIGS.items()) +
+                                  list(FRONTEND_LANES_SIGS.items()) + list(FRONTEND_TRACKS_SIGS.items()) +
                                   list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res

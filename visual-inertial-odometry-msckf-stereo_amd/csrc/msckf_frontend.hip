@@ -29,6 +29,9 @@
 //               per-cell selection (include/msckf_pipeline.h) around k_fast and
 //               k_fast_rows: device-built mask, device scan of the row counts,
 //               one workgroup per grid cell
+//   k_trk_*     the feature tracks kept on the device (include/msckf_tracks.h): a
+//               whole tracked frame of many streams chained on the device, around
+//               lk_point, stereo_point, k_two_point_ransac and the detection stages
 // Images are 8-bit, small (752 x 480 for EuRoC) and read through the cache:
 // these kernels are latency-class work, not HBM-bound.
 #include <hip/hip_runtime.h>
@@ -44,6 +47,7 @@
 #include "../../include/msckf_lanes.h"
 #include "../../include/msckf_pipeline.h"
 #include "../../include/msckf_ransac.h"
+#include "../../include/msckf_tracks.h"
 
 namespace {
 
@@ -1086,6 +1090,368 @@ __global__ void __launch_bounds__(256) k_grid_select_sets(GridArgs a, int kp_cap
     grid_select_cell(a, blockIdx.x, s_key, s_cnt);
 }
 
+// ------------------------------------------------------ device-side tracks --
+// include/msckf_tracks.h states the steps.  The tables and every work area have
+// the fixed stride [lane][cap]; the counts live on the device, so the launches are
+// sized by cap and a wavefront or thread beyond its lane's count exits at once.
+// Per-row work (the new cam0 / cam1 point, the keep flag, the cell) is indexed by
+// the row of the previous table; the survivors of steps 2, 3 and 4 are index lists
+// into it, each an order-preserving compaction of the one before.
+constexpr int TRK_THREADS = 256, TRK_WAVES = TRK_THREADS / 64;
+
+struct TrkHdr {
+    long long next_id;
+    int n, pad;
+};
+
+struct TrkDev {
+    // the tables, [2][n_lanes] (a lane's current one is TrkLane::cur)
+    long long* ids;   // [..][cap]
+    int* life;        // [..][cap]
+    float* cam0;      // [..][cap][2]
+    float* cam1;
+    TrkHdr* hdr;
+    // work areas by the lane's place l in the call, rows as in the previous table
+    float* c0;        // [l][cap][2] the tracked cam0 point
+    float* c1;        // [l][cap][2] its stereo match
+    uint8_t* flag;    // [l][cap]
+    int* code;        // [l][cap] the cell of c0
+    int* idx;         // [3][n_lanes][cap] the rows left after steps 2, 3, 4
+    int* cnt;         // [3][n_lanes]
+    // detection: the outputs of k_grid_select_sets and the candidates' matches
+    int* g_cnt;       // [l][cells]
+    float* g_resp;    // [l][cells k]
+    float* g_xy;      // [l][cells k][2]
+    float* cand_c1;   // [l][cells k][2]
+    uint8_t* cand_inl;
+    int* new_off;     // [l][cells] new features / rows of the next table before the cell
+    int* out_off;
+    // two-point RANSAC: sets 2 i and 2 i + 1 of the call's i-th RANSAC lane
+    int* rs_off;      // [2 n_lanes + 1]
+    double *rs_prev, *rs_curr, *rs_work, *rs_info;
+    uint8_t* rs_inl;
+    int n_lanes, cap, cells, grid_col, grid_min, grid_max, gh, gw;
+};
+
+struct TrkLane {
+    StereoSet st;    // slot0 / slot1 = the current pair
+    CamModel pub0;   // cam0 as publish undistorts it (st.cam1 serves for cam1)
+    double H[9];
+    int lane, cur, slot_prev, rs;   // rs: the lane's place among the call's RANSAC lanes, or -1
+};
+
+// what comes back, [l] as the call names the lanes
+struct TrkOut {
+    int* n;             // [l]
+    int* counters;      // [l][4]
+    int* n_total;       // [l]
+    long long* next_id; // [l]
+    long long* ids;     // [l][cap]
+    double* uv;         // [l][cap][4]
+};
+
+__device__ __forceinline__ int trk_cell(const TrkDev& d, float x, float y) {
+    return (int)(y / (float)d.gh) * d.grid_col + (int)(x / (float)d.gw);
+}
+
+// steps 1-2: one wavefront per row of the lane's current table
+__global__ void __launch_bounds__(64) k_trk_lk(TrkDev d, const TrkLane* __restrict__ lanes,
+                                               const Pyr* __restrict__ tab, int win, int max_level, int max_iter,
+                                               double eps) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x, lane = threadIdx.x;
+    const int l = __builtin_amdgcn_readfirstlane(blockIdx.y);
+    const TrkLane& L = lanes[l];
+    const size_t t = (size_t)L.cur * d.n_lanes + L.lane;
+    if (r >= d.hdr[t].n) return;
+    const size_t row = t * d.cap + r, w = (size_t)l * d.cap + r;
+    const float px = d.cam0[2 * row], py = d.cam0[2 * row + 1];
+    const double x = (double)px, y = (double)py;
+    const double q0 = L.H[0] * x + L.H[1] * y + L.H[2];
+    const double q1 = L.H[3] * x + L.H[4] * y + L.H[5];
+    const double q2 = L.H[6] * x + L.H[7] * y + L.H[8];
+    float nx = (float)(q0 / q2), ny = (float)(q1 / q2);
+    const Pyr& N = tab[L.st.slot0];
+    const bool st = lk_point(tab[L.slot_prev], N, px, py, nx, ny, win, max_level, max_iter, eps, lane);
+    if (lane == 0) {
+        const float xmax = (float)(N.lv[0].w - 1), ymax = (float)(N.lv[0].h - 1);
+        d.c0[2 * w] = nx;
+        d.c0[2 * w + 1] = ny;
+        d.flag[w] = (st && !(nx < 0.f || nx > xmax || ny < 0.f || ny > ymax)) ? 1 : 0;
+    }
+}
+
+// step 3: one wavefront per row left after step 2
+__global__ void __launch_bounds__(64) k_trk_stereo(TrkDev d, const TrkLane* __restrict__ lanes,
+                                                   const Pyr* __restrict__ tab, int win, int max_level, int max_iter,
+                                                   double eps) {
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const int l = __builtin_amdgcn_readfirstlane(blockIdx.y);
+    if (j >= d.cnt[l]) return;
+    const StereoSet& S = lanes[l].st;
+    const size_t w = (size_t)l * d.cap + d.idx[(size_t)l * d.cap + j];
+    float c1x, c1y;
+    const int reason = stereo_point(tab[S.slot0], tab[S.slot1], S.cam0, S.cam1, S.E, S.epi_thr, eps, win, max_level,
+                                    max_iter, (double)d.c0[2 * w], (double)d.c0[2 * w + 1], lane, c1x, c1y);
+    if (lane == 0) {
+        d.c1[2 * w] = c1x;
+        d.c1[2 * w + 1] = c1y;
+        d.flag[w] = reason == 0 ? 1 : 0;
+    }
+}
+
+// step 7: one wavefront per candidate of the detection, b = cell k + place in the cell
+__global__ void __launch_bounds__(64) k_trk_stereo_new(TrkDev d, const TrkLane* __restrict__ lanes,
+                                                       const Pyr* __restrict__ tab, int win, int max_level,
+                                                       int max_iter, double eps) {
+    const int b = blockIdx.x, lane = threadIdx.x, k = d.grid_max;
+    const int l = __builtin_amdgcn_readfirstlane(blockIdx.y);
+    const int cell = b / k;
+    if (b - cell * k >= min(k, d.g_cnt[(size_t)l * d.cells + cell])) return;
+    const StereoSet& S = lanes[l].st;
+    const size_t g = (size_t)l * d.cells * k + b;
+    float c1x, c1y;
+    const int reason = stereo_point(tab[S.slot0], tab[S.slot1], S.cam0, S.cam1, S.E, S.epi_thr, eps, win, max_level,
+                                    max_iter, (double)d.g_xy[2 * g], (double)d.g_xy[2 * g + 1], lane, c1x, c1y);
+    if (lane == 0) {
+        d.cand_c1[2 * g] = c1x;
+        d.cand_c1[2 * g + 1] = c1y;
+        d.cand_inl[g] = reason == 0 ? 1 : 0;
+    }
+}
+
+// Order-preserving compaction, one workgroup per lane: the rows of list stage - 1
+// (stage 0: all rows of the table) whose flag is set become list stage.  256 rows at a
+// time: the rank within the wave from the ballot, the wave counts of the chunk through
+// LDS, added in wave order.
+__global__ void __launch_bounds__(TRK_THREADS) k_trk_compact(TrkDev d, const TrkLane* __restrict__ lanes, int stage) {
+    __shared__ int s_wcnt[2][TRK_WAVES];
+    const int l = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t NLC = (size_t)d.n_lanes * d.cap, base = (size_t)l * d.cap;
+    const int n_in = min(stage == 0 ? d.hdr[(size_t)lanes[l].cur * d.n_lanes + lanes[l].lane].n
+                                    : d.cnt[(stage - 1) * d.n_lanes + l], d.cap);
+    const int* in = stage == 0 ? nullptr : d.idx + (stage - 1) * NLC + base;
+    int* out = d.idx + stage * NLC + base;
+    int n_out = 0;
+    for (int c0 = 0, it = 0; c0 < n_in; c0 += TRK_THREADS, ++it) {
+        const int j = c0 + tid;
+        int r = 0;
+        bool keep = false;
+        if (j < n_in) {
+            r = in ? in[j] : j;
+            keep = d.flag[base + r] != 0;
+        }
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) s_wcnt[it & 1][wave] = __popcll(bal);
+        __syncthreads();
+        int off = n_out, tot = 0;
+#pragma unroll
+        for (int w = 0; w < TRK_WAVES; ++w) {
+            const int cw = s_wcnt[it & 1][w];
+            if (w < wave) off += cw;
+            tot += cw;
+        }
+        if (keep) out[off + __popcll(bal & ((1ull << lane) - 1ull))] = r;   // off + rank <= j < cap
+        n_out += tot;
+    }
+    if (tid == 0) d.cnt[stage * d.n_lanes + l] = n_out;
+}
+
+// step 4, before k_two_point_ransac: set_off of the call's 2 n_rs sets
+__global__ void __launch_bounds__(64) k_trk_rs_off(TrkDev d, const int32_t* __restrict__ rs_lane, int n_rs) {
+    if (threadIdx.x != 0) return;
+    int off = 0;
+    d.rs_off[0] = 0;
+    for (int i = 0; i < n_rs; ++i) {
+        const int c = d.cnt[d.n_lanes + rs_lane[i]];
+        d.rs_off[2 * i + 1] = off + c;
+        d.rs_off[2 * i + 2] = off + 2 * c;
+        off += 2 * c;
+    }
+}
+
+// blockIdx.y = the set: the matched rows' previous and current points as doubles
+__global__ void __launch_bounds__(256) k_trk_rs_pack(TrkDev d, const TrkLane* __restrict__ lanes,
+                                                     const int32_t* __restrict__ rs_lane) {
+    const int s = blockIdx.y, l = rs_lane[s >> 1], j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= d.cnt[d.n_lanes + l]) return;
+    const TrkLane& L = lanes[l];
+    const int r = d.idx[((size_t)d.n_lanes + l) * d.cap + j];
+    const size_t row = ((size_t)L.cur * d.n_lanes + L.lane) * d.cap + r, w = (size_t)l * d.cap + r;
+    const float* prev = (s & 1) ? d.cam1 : d.cam0;
+    const float* curr = (s & 1) ? d.c1 : d.c0;
+    const size_t g = (size_t)d.rs_off[s] + j;
+    d.rs_prev[2 * g] = (double)prev[2 * row];
+    d.rs_prev[2 * g + 1] = (double)prev[2 * row + 1];
+    d.rs_curr[2 * g] = (double)curr[2 * w];
+    d.rs_curr[2 * g + 1] = (double)curr[2 * w + 1];
+}
+
+// steps 4-5: the RANSAC verdict of the matched rows (all kept in a lane without RANSAC)
+// and the cell of each
+__global__ void __launch_bounds__(256) k_trk_rs_flag(TrkDev d, const TrkLane* __restrict__ lanes) {
+    const int l = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= d.cnt[d.n_lanes + l]) return;
+    const int rs = lanes[l].rs;
+    const size_t w = (size_t)l * d.cap + d.idx[((size_t)d.n_lanes + l) * d.cap + j];
+    bool keep = true;
+    if (rs >= 0) keep = d.rs_inl[d.rs_off[2 * rs] + j] != 0 && d.rs_inl[d.rs_off[2 * rs + 1] + j] != 0;
+    d.flag[w] = keep ? 1 : 0;
+    d.code[w] = trk_cell(d, d.c0[2 * w], d.c0[2 * w + 1]);
+}
+
+// step 6: the survivors' 7 x 7 blocks cleared in the lane's mask (k_mask_clear_sets with
+// the occupied list read through the survivor list)
+__global__ void __launch_bounds__(256) k_trk_mask_clear(TrkDev d, uint8_t* __restrict__ mask, int w, int h) {
+    const int l = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
+    const int p = t / 7, r = t - 7 * p;
+    if (p >= d.cnt[2 * d.n_lanes + l]) return;
+    const size_t o = (size_t)l * d.cap + d.idx[((size_t)2 * d.n_lanes + l) * d.cap + p];
+    mask_clear_row(d.c0[2 * o], d.c0[2 * o + 1], r, mask + (size_t)l * w * h, w, h);
+}
+
+// steps 7-9, one workgroup per lane: per cell the survivors and the new features (the
+// first grid_min inliers in candidate order), then the prefixes over the cells in cell
+// order; writes the next table's header and the lane's scalar outputs
+__global__ void __launch_bounds__(TRK_THREADS) k_trk_cells(TrkDev d, const TrkLane* __restrict__ lanes, TrkOut o) {
+    __shared__ int s_ns[MFE_GRID_MAX_CELLS], s_nn[MFE_GRID_MAX_CELLS];
+    const int l = blockIdx.x, tid = threadIdx.x, k = d.grid_max;
+    const TrkLane& L = lanes[l];
+    const size_t base = (size_t)l * d.cap;
+    const int n_sv = d.cnt[2 * d.n_lanes + l];
+    const int* sv = d.idx + ((size_t)2 * d.n_lanes + l) * d.cap;
+    for (int cell = tid; cell < d.cells; cell += TRK_THREADS) {
+        int ns = 0, nn = 0;
+        for (int j = 0; j < n_sv; ++j) ns += d.code[base + sv[j]] == cell ? 1 : 0;
+        const int nc = min(k, d.g_cnt[(size_t)l * d.cells + cell]);
+        const uint8_t* inl = d.cand_inl + ((size_t)l * d.cells + cell) * k;
+        for (int q = 0; q < nc && nn < d.grid_min; ++q) nn += inl[q] ? 1 : 0;
+        s_ns[cell] = ns;
+        s_nn[cell] = nn;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    int n_new = 0, n_rows = 0;
+    for (int cell = 0; cell < d.cells; ++cell) {
+        d.new_off[(size_t)l * d.cells + cell] = n_new;
+        d.out_off[(size_t)l * d.cells + cell] = n_rows;
+        n_new += s_nn[cell];
+        n_rows += min(s_ns[cell] + s_nn[cell], k);
+    }
+    const TrkHdr cur = d.hdr[(size_t)L.cur * d.n_lanes + L.lane];
+    TrkHdr nxt;
+    nxt.next_id = cur.next_id + n_new;
+    nxt.n = n_rows;
+    nxt.pad = 0;
+    d.hdr[(size_t)(L.cur ^ 1) * d.n_lanes + L.lane] = nxt;
+    o.n[l] = n_rows;
+    o.next_id[l] = nxt.next_id;
+    o.counters[4 * l] = cur.n;
+    o.counters[4 * l + 1] = d.cnt[l];
+    o.counters[4 * l + 2] = d.cnt[d.n_lanes + l];
+    o.counters[4 * l + 3] = n_sv;
+}
+
+// steps 8-9, one workgroup per (lane, cell): the cell's rows gathered in LDS (survivors
+// in previous-table order, then the new ones), ranked by counting the rows that precede
+// in the stable sort by lifetime when the cell is over grid_max, and written to the next
+// table.  s_src: a survivor's row, or -(1 + b) for candidate b.
+__global__ void __launch_bounds__(TRK_THREADS) k_trk_assemble(TrkDev d, const TrkLane* __restrict__ lanes, TrkOut o) {
+    __shared__ int s_src[RS_MAXN], s_life[RS_MAXN];
+    __shared__ int s_wcnt[2][TRK_WAVES];
+    __shared__ int s_nn;
+    const int cell = blockIdx.x, l = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, k = d.grid_max;
+    const TrkLane& L = lanes[l];
+    const size_t base = (size_t)l * d.cap, tcur = ((size_t)L.cur * d.n_lanes + L.lane) * d.cap;
+    const size_t tnxt = ((size_t)(L.cur ^ 1) * d.n_lanes + L.lane) * d.cap;
+    const int n_sv = d.cnt[2 * d.n_lanes + l];
+    const int* sv = d.idx + ((size_t)2 * d.n_lanes + l) * d.cap;
+    int ns = 0;
+    for (int c0 = 0, it = 0; c0 < n_sv; c0 += TRK_THREADS, ++it) {
+        const int j = c0 + tid;
+        int r = 0;
+        bool keep = false;
+        if (j < n_sv) {
+            r = sv[j];
+            keep = d.code[base + r] == cell;
+        }
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) s_wcnt[it & 1][wave] = __popcll(bal);
+        __syncthreads();
+        int off = ns, tot = 0;
+#pragma unroll
+        for (int w = 0; w < TRK_WAVES; ++w) {
+            const int cw = s_wcnt[it & 1][w];
+            if (w < wave) off += cw;
+            tot += cw;
+        }
+        if (keep) {
+            const int p = off + __popcll(bal & ((1ull << lane) - 1ull));   // p <= j < cap <= RS_MAXN
+            s_src[p] = r;
+            s_life[p] = d.life[tcur + r] + 1;
+        }
+        ns += tot;
+    }
+    if (tid == 0) {
+        const int nc = min(k, d.g_cnt[(size_t)l * d.cells + cell]);
+        const uint8_t* inl = d.cand_inl + ((size_t)l * d.cells + cell) * k;
+        int nn = 0;
+        for (int q = 0; q < nc && nn < d.grid_min && ns + nn < RS_MAXN; ++q)
+            if (inl[q]) {
+                s_src[ns + nn] = -(1 + cell * k + q);
+                s_life[ns + nn] = 1;
+                ++nn;
+            }
+        s_nn = nn;
+    }
+    __syncthreads();
+    const int m = ns + s_nn;
+    const bool prune = m > k;
+    const long long id0 = d.hdr[(size_t)L.cur * d.n_lanes + L.lane].next_id + d.new_off[(size_t)l * d.cells + cell];
+    const int o0 = d.out_off[(size_t)l * d.cells + cell];
+    for (int i = tid; i < m; i += TRK_THREADS) {
+        int pos = i;
+        const int life = s_life[i];
+        if (prune) {
+            pos = 0;
+            for (int j = 0; j < m; ++j) pos += (s_life[j] > life || (s_life[j] == life && j < i)) ? 1 : 0;
+            if (pos >= k) continue;
+        }
+        const size_t out = (size_t)o0 + pos;   // below cells grid_max <= cap
+        if (out >= (size_t)d.cap) continue;
+        const int src = s_src[i];
+        long long id;
+        float a0, a1, b0, b1;
+        if (src >= 0) {
+            id = d.ids[tcur + src];
+            a0 = d.c0[2 * (base + src)]; a1 = d.c0[2 * (base + src) + 1];
+            b0 = d.c1[2 * (base + src)]; b1 = d.c1[2 * (base + src) + 1];
+        } else {
+            const size_t g = (size_t)l * d.cells * k + (size_t)(-src - 1);
+            id = id0 + (i - ns);
+            a0 = d.g_xy[2 * g]; a1 = d.g_xy[2 * g + 1];
+            b0 = d.cand_c1[2 * g]; b1 = d.cand_c1[2 * g + 1];
+        }
+        d.ids[tnxt + out] = id;
+        d.life[tnxt + out] = life;
+        d.cam0[2 * (tnxt + out)] = a0; d.cam0[2 * (tnxt + out) + 1] = a1;
+        d.cam1[2 * (tnxt + out)] = b0; d.cam1[2 * (tnxt + out) + 1] = b1;
+        o.ids[base + out] = id;
+    }
+}
+
+// step 9: the published coordinates of the next table's rows, fp64, one thread per row
+__global__ void __launch_bounds__(256) k_trk_uv(TrkDev d, const TrkLane* __restrict__ lanes, TrkOut o) {
+    const int l = blockIdx.y, r = blockIdx.x * 256 + threadIdx.x;
+    const TrkLane& L = lanes[l];
+    const size_t t = (size_t)(L.cur ^ 1) * d.n_lanes + L.lane;
+    if (r >= min(d.hdr[t].n, d.cap)) return;
+    const size_t row = t * d.cap + r;
+    double* uv = o.uv + 4 * ((size_t)l * d.cap + r);
+    undistort_rect(L.pub0, (double)d.cam0[2 * row], (double)d.cam0[2 * row + 1], uv[0], uv[1]);
+    undistort_rect(L.st.cam1, (double)d.cam1[2 * row], (double)d.cam1[2 * row + 1], uv[2], uv[3]);
+}
+
 }  // namespace
 
 // ================================================================ C-ABI ====
@@ -1113,6 +1479,10 @@ struct mfe_ctx {
     Pyr* d_pyr = nullptr;
     GridWork lanes{};
     int lanes_cap = 0;
+    // the track tables (msckf_tracks.h), one block of the context's allocations; the host's
+    // record of each lane's current table and its row count
+    TrkDev trk{};
+    std::vector<int> trk_cur, trk_n;
 };
 
 namespace {
@@ -1852,6 +2222,273 @@ int mfe_undistort_sets(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const d
     MFE_HIP(hipMemcpyAsync(h + o_out, d + o_out, 16 * T, hipMemcpyDeviceToHost, s));
     MFE_HIP(hipStreamSynchronize(s));
     memcpy(pts_out, h + o_out, 16 * T);
+    return 0;
+}
+
+// ------------------------------------------ device-side tracks (msckf_tracks.h) --
+int mfe_tracks_create(mfe_ctx_t* c, int n_lanes, int cap, int grid_row, int grid_col, int grid_min, int grid_max) {
+    if (!c) MFE_FAIL(-1, "null context");
+    if (c->trk.ids) MFE_FAIL(-1, "the context has its track tables already");
+    if (n_lanes < 1 || 3 * (long long)n_lanes > c->nslot)
+        MFE_FAIL(-1, "n_lanes = %d outside [1, %d] (three slots per lane)", n_lanes, c->nslot / 3);
+    if (grid_row < 1 || grid_col < 1 || (long long)grid_row * grid_col > MFE_GRID_MAX_CELLS)
+        MFE_FAIL(-1, "grid %dx%d outside [1, %d] cells", grid_row, grid_col, MFE_GRID_MAX_CELLS);
+    if (grid_max < 1 || grid_max > MFE_GRID_MAX_K) MFE_FAIL(-1, "grid_max = %d outside [1, %d]", grid_max, MFE_GRID_MAX_K);
+    if (grid_min < 0) MFE_FAIL(-1, "grid_min = %d is negative", grid_min);
+    const long long cells = (long long)grid_row * grid_col;
+    if (cap > MFE_RANSAC_MAX_SET_POINTS || cap < cells * ((long long)grid_min + grid_max))
+        MFE_FAIL(-1, "cap = %d outside [%lld, %d]", cap, cells * ((long long)grid_min + grid_max),
+                 MFE_RANSAC_MAX_SET_POINTS);
+    MFE_HIP(hipSetDevice(c->device));
+    const size_t NL = (size_t)n_lanes, C = (size_t)cap, CK = (size_t)cells * grid_max;
+    Block b;
+    const size_t o_ids = b.add(8 * 2 * NL * C), o_life = b.add(4 * 2 * NL * C), o_cam0 = b.add(8 * 2 * NL * C),
+                 o_cam1 = b.add(8 * 2 * NL * C), o_hdr = b.add(sizeof(TrkHdr) * 2 * NL), o_c0 = b.add(8 * NL * C),
+                 o_c1 = b.add(8 * NL * C), o_flag = b.add(NL * C), o_code = b.add(4 * NL * C),
+                 o_idx = b.add(4 * 3 * NL * C), o_cnt = b.add(4 * 3 * NL), o_gcnt = b.add(4 * NL * cells),
+                 o_gresp = b.add(4 * NL * CK), o_gxy = b.add(8 * NL * CK), o_cc1 = b.add(8 * NL * CK),
+                 o_cinl = b.add(NL * CK), o_noff = b.add(4 * NL * cells), o_ooff = b.add(4 * NL * cells),
+                 o_rsoff = b.add(4 * (2 * NL + 1)), o_rsprev = b.add(16 * 2 * NL * C), o_rscurr = b.add(16 * 2 * NL * C),
+                 o_rswork = b.add(32 * 2 * NL * C), o_rsinfo = b.add(8 * MFE_RANSAC_INFO_LEN * 2 * NL),
+                 o_rsinl = b.add(2 * NL * C);
+    void* p;
+    if (int rc = dev_alloc(c, &p, b.size)) return rc;
+    MFE_HIP(hipMemset(p, 0, b.size));   // every lane empty, next_id = 0
+    unsigned char* m = (unsigned char*)p;
+    TrkDev& d = c->trk;
+    d.ids = (long long*)(m + o_ids); d.life = (int*)(m + o_life);
+    d.cam0 = (float*)(m + o_cam0); d.cam1 = (float*)(m + o_cam1); d.hdr = (TrkHdr*)(m + o_hdr);
+    d.c0 = (float*)(m + o_c0); d.c1 = (float*)(m + o_c1); d.flag = m + o_flag; d.code = (int*)(m + o_code);
+    d.idx = (int*)(m + o_idx); d.cnt = (int*)(m + o_cnt);
+    d.g_cnt = (int*)(m + o_gcnt); d.g_resp = (float*)(m + o_gresp); d.g_xy = (float*)(m + o_gxy);
+    d.cand_c1 = (float*)(m + o_cc1); d.cand_inl = m + o_cinl;
+    d.new_off = (int*)(m + o_noff); d.out_off = (int*)(m + o_ooff);
+    d.rs_off = (int*)(m + o_rsoff); d.rs_prev = (double*)(m + o_rsprev); d.rs_curr = (double*)(m + o_rscurr);
+    d.rs_work = (double*)(m + o_rswork); d.rs_info = (double*)(m + o_rsinfo); d.rs_inl = m + o_rsinl;
+    d.n_lanes = n_lanes; d.cap = cap; d.cells = (int)cells; d.grid_col = grid_col;
+    d.grid_min = grid_min; d.grid_max = grid_max;
+    d.gh = (c->H + grid_row - 1) / grid_row; d.gw = (c->W + grid_col - 1) / grid_col;
+    c->trk_cur.assign(n_lanes, 0);
+    c->trk_n.assign(n_lanes, 0);
+    return 0;
+}
+
+static int check_trk_lane(mfe_ctx_t* c, int lane) {
+    if (!c) MFE_FAIL(-1, "null context");
+    if (!c->trk.ids) MFE_FAIL(-1, "the context has no track tables (mfe_tracks_create)");
+    if (lane < 0 || lane >= c->trk.n_lanes) MFE_FAIL(-1, "lane %d outside [0, %d)", lane, c->trk.n_lanes);
+    return 0;
+}
+
+int mfe_tracks_put(mfe_ctx_t* c, int lane, int n, const int64_t* ids, const int32_t* lifetimes, const float* cam0,
+                   const float* cam1, int64_t next_id) {
+    if (check_trk_lane(c, lane)) return -1;
+    const TrkDev& d = c->trk;
+    if (n < 0 || (long long)n + (long long)d.cells * d.grid_min > d.cap)
+        MFE_FAIL(-1, "n = %d outside [0, %lld] (cap %d less grid_min per cell)", n,
+                 (long long)d.cap - (long long)d.cells * d.grid_min, d.cap);
+    if (n > 0 && (!ids || !lifetimes || !cam0 || !cam1)) MFE_FAIL(-1, "null table array");
+    MFE_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t t = (size_t)c->trk_cur[lane] * d.n_lanes + lane, row = t * d.cap, N = (size_t)n;
+    TrkHdr hdr;
+    hdr.next_id = next_id; hdr.n = n; hdr.pad = 0;
+    if (n > 0) {
+        MFE_HIP(hipMemcpyAsync(d.ids + row, ids, 8 * N, hipMemcpyHostToDevice, s));
+        MFE_HIP(hipMemcpyAsync(d.life + row, lifetimes, 4 * N, hipMemcpyHostToDevice, s));
+        MFE_HIP(hipMemcpyAsync(d.cam0 + 2 * row, cam0, 8 * N, hipMemcpyHostToDevice, s));
+        MFE_HIP(hipMemcpyAsync(d.cam1 + 2 * row, cam1, 8 * N, hipMemcpyHostToDevice, s));
+    }
+    MFE_HIP(hipMemcpyAsync(d.hdr + t, &hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
+    MFE_HIP(hipStreamSynchronize(s));
+    c->trk_n[lane] = n;
+    return 0;
+}
+
+int mfe_tracks_get(mfe_ctx_t* c, int lane, int32_t* n, int64_t* ids, int32_t* lifetimes, float* cam0, float* cam1,
+                   int64_t* next_id) {
+    if (check_trk_lane(c, lane)) return -1;
+    if (!n || !ids || !lifetimes || !cam0 || !cam1 || !next_id) MFE_FAIL(-1, "null output");
+    const TrkDev& d = c->trk;
+    MFE_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t t = (size_t)c->trk_cur[lane] * d.n_lanes + lane, row = t * d.cap;
+    TrkHdr hdr;
+    MFE_HIP(hipMemcpyAsync(&hdr, d.hdr + t, sizeof(hdr), hipMemcpyDeviceToHost, s));
+    MFE_HIP(hipStreamSynchronize(s));
+    if (hdr.n < 0 || hdr.n > d.cap) MFE_FAIL(-2, "lane %d: the device table holds n = %d", lane, hdr.n);
+    const size_t N = (size_t)hdr.n;
+    if (N > 0) {
+        MFE_HIP(hipMemcpyAsync(ids, d.ids + row, 8 * N, hipMemcpyDeviceToHost, s));
+        MFE_HIP(hipMemcpyAsync(lifetimes, d.life + row, 4 * N, hipMemcpyDeviceToHost, s));
+        MFE_HIP(hipMemcpyAsync(cam0, d.cam0 + 2 * row, 8 * N, hipMemcpyDeviceToHost, s));
+        MFE_HIP(hipMemcpyAsync(cam1, d.cam1 + 2 * row, 8 * N, hipMemcpyDeviceToHost, s));
+        MFE_HIP(hipStreamSynchronize(s));
+    }
+    *n = hdr.n;
+    *next_id = hdr.next_id;
+    return 0;
+}
+
+int mfe_tracks_step(mfe_ctx_t* c, int n_lanes, const int32_t* lanes, const int32_t* slot_prev, const int32_t* slot_c0,
+                    const int32_t* slot_c1, const double* Hpred, const double* intrinsics0, const int32_t* model0,
+                    const double* coeffs0, const double* intrinsics1, const int32_t* model1, const double* coeffs1,
+                    const double* R_guess, const double* E, const double* stereo_threshold, const int32_t* ransac,
+                    const double* R0, const double* R1, const uint32_t* draws, int win, int max_level, int max_iter,
+                    double eps, int threshold, int max_kp, double inlier_error, int n_hyp, int32_t* n_out,
+                    int64_t* ids_out, double* uv_out, int32_t* counters, int32_t* n_total, int64_t* next_id_out) {
+    if (!c) MFE_FAIL(-1, "null context");
+    if (!c->trk.ids) MFE_FAIL(-1, "the context has no track tables (mfe_tracks_create)");
+    TrkDev d = c->trk;
+    if (n_lanes < 0 || n_lanes > d.n_lanes) MFE_FAIL(-1, "n_lanes = %d outside [0, %d]", n_lanes, d.n_lanes);
+    if (n_lanes == 0) return 0;
+    if (!lanes || !Hpred || !ransac) MFE_FAIL(-1, "null lane argument");
+    if (!n_out || !ids_out || !uv_out || !counters || !n_total || !next_id_out) MFE_FAIL(-1, "null output");
+    int n_rs = 0;
+    for (int l = 0; l < n_lanes; ++l) {
+        if (lanes[l] < 0 || lanes[l] >= d.n_lanes) MFE_FAIL(-1, "lanes[%d] = %d outside [0, %d)", l, lanes[l], d.n_lanes);
+        for (int j = 0; j < l; ++j)
+            if (lanes[j] == lanes[l]) MFE_FAIL(-1, "lane %d is named twice (entries %d and %d)", lanes[l], j, l);
+        if ((long long)c->trk_n[lanes[l]] + (long long)d.cells * d.grid_min > d.cap)
+            MFE_FAIL(-1, "lane %d: %d rows leave no room for %d new ones (cap %d)", lanes[l], c->trk_n[lanes[l]],
+                     d.cells * d.grid_min, d.cap);
+        n_rs += ransac[l] ? 1 : 0;
+    }
+    if (check_slots(c, n_lanes, slot_prev, "slot_prev") || check_slots(c, n_lanes, slot_c0, "slot_c0") ||
+        check_slots(c, n_lanes, slot_c1, "slot_c1") || check_lk_args(c, win, max_level, max_iter))
+        return -1;
+    if (!intrinsics0 || !coeffs0 || !intrinsics1 || !coeffs1 || !R_guess || !E || !stereo_threshold)
+        MFE_FAIL(-1, "null camera argument");
+    if (check_models(n_lanes, model0, "model0") || check_models(n_lanes, model1, "model1")) return -1;
+    if (n_rs > 0) {
+        if (!R0 || !R1 || !draws) MFE_FAIL(-1, "null RANSAC argument");
+        if (n_hyp < 1 || n_hyp > MFE_RANSAC_MAX_HYP) MFE_FAIL(-1, "n_hyp %d outside [1, %d]", n_hyp, MFE_RANSAC_MAX_HYP);
+    }
+    if (c->W < 16 || c->H < 16) MFE_FAIL(-1, "image %dx%d is smaller than 16x16", c->W, c->H);
+    if (max_kp < 1 || max_kp > c->kp_cap) MFE_FAIL(-1, "max_kp = %d outside [1, %d]", max_kp, c->kp_cap);
+    MFE_HIP(hipSetDevice(c->device));
+    if (int rc = ensure_pyr_table(c)) return rc;
+    if (int rc = grow_grid_work(c, n_lanes)) return rc;
+    threshold = threshold < 0 ? 0 : (threshold > 255 ? 255 : threshold);
+    hipStream_t s = c->stream;
+    const int W = c->W, H = c->H;
+    const size_t NL = (size_t)n_lanes, NR = (size_t)n_rs, C = (size_t)d.cap, HY = (size_t)(n_rs ? n_hyp : 0);
+    Block b;
+    const size_t o_lanes = b.add(sizeof(TrkLane) * NL), o_slots = b.add(4 * NL), o_rsl = b.add(4 * NR),
+                 o_rsR = b.add(72 * 2 * NR), o_rsK = b.add(32 * 2 * NR), o_rsk = b.add(32 * 2 * NR),
+                 o_rsm = b.add(4 * 2 * NR), o_draw = b.add(8 * 2 * NR * HY), in_bytes = b.size,
+                 o_n = b.add(4 * NL), o_ctr = b.add(16 * NL), o_tot = b.add(4 * NL), o_next = b.add(8 * NL),
+                 o_ids = b.add(8 * NL * C), o_uv = b.add(32 * NL * C), out_bytes = b.size - o_n;
+    if (int rc = grow_scratch(c, b.size, b.size)) return rc;
+    unsigned char *h = c->rs_host, *dv = c->rs_dev;
+    TrkLane* tl = (TrkLane*)(h + o_lanes);
+    int32_t* rsl = (int32_t*)(h + o_rsl);
+    for (size_t i = 0, r = 0; i < NL; ++i) {
+        const double *K0 = intrinsics0 + 4 * i, *K1 = intrinsics1 + 4 * i;
+        TrkLane& L = tl[i];
+        L.st.cam0 = make_model(K0, model0[i], coeffs0 + 4 * i, R_guess + 9 * i, nullptr);
+        L.st.cam1 = make_model(K1, model1[i], coeffs1 + 4 * i, nullptr, nullptr);
+        for (int j = 0; j < 9; ++j) L.st.E[j] = E[9 * i + j];
+        L.st.epi_thr = stereo_threshold[i] * (4.0 / (K0[0] + K0[1] + K1[0] + K1[1]));
+        L.st.slot0 = slot_c0[i];
+        L.st.slot1 = slot_c1[i];
+        L.pub0 = make_model(K0, model0[i], coeffs0 + 4 * i, nullptr, nullptr);
+        for (int j = 0; j < 9; ++j) L.H[j] = Hpred[9 * i + j];
+        L.lane = lanes[i];
+        L.cur = c->trk_cur[lanes[i]];
+        L.slot_prev = slot_prev[i];
+        L.rs = -1;
+        ((int32_t*)(h + o_slots))[i] = slot_c0[i];
+        if (ransac[i]) {   // sets 2 r (cam0, R0, draws[0]) and 2 r + 1 (cam1, R1, draws[1])
+            L.rs = (int)r;
+            rsl[r] = (int32_t)i;
+            memcpy(h + o_rsR + 72 * (2 * r), R0 + 9 * i, 72);
+            memcpy(h + o_rsR + 72 * (2 * r + 1), R1 + 9 * i, 72);
+            memcpy(h + o_rsK + 32 * (2 * r), K0, 32);
+            memcpy(h + o_rsK + 32 * (2 * r + 1), K1, 32);
+            memcpy(h + o_rsk + 32 * (2 * r), coeffs0 + 4 * i, 32);
+            memcpy(h + o_rsk + 32 * (2 * r + 1), coeffs1 + 4 * i, 32);
+            ((int32_t*)(h + o_rsm))[2 * r] = model0[i];
+            ((int32_t*)(h + o_rsm))[2 * r + 1] = model1[i];
+            memcpy(h + o_draw + 8 * (2 * r) * HY, draws + 4 * i * HY, 16 * HY);
+            ++r;
+        }
+    }
+    MFE_HIP(hipMemcpyAsync(dv, h, in_bytes, hipMemcpyHostToDevice, s));
+    const TrkLane* dl = (const TrkLane*)(dv + o_lanes);
+    const int32_t* drsl = (const int32_t*)(dv + o_rsl);
+    const Pyr* tab = c->d_pyr;
+    TrkOut o;
+    o.n = (int*)(dv + o_n); o.counters = (int*)(dv + o_ctr); o.n_total = (int*)(dv + o_tot);
+    o.next_id = (long long*)(dv + o_next); o.ids = (long long*)(dv + o_ids); o.uv = (double*)(dv + o_uv);
+    const dim3 rows(d.cap, n_lanes), per256((d.cap + 255) / 256, n_lanes);
+    // steps 1-3
+    hipLaunchKernelGGL(k_trk_lk, rows, dim3(64), 0, s, d, dl, tab, win, max_level, max_iter, eps);
+    hipLaunchKernelGGL(k_trk_compact, dim3(n_lanes), dim3(TRK_THREADS), 0, s, d, dl, 0);
+    hipLaunchKernelGGL(k_trk_stereo, rows, dim3(64), 0, s, d, dl, tab, win, max_level, max_iter, eps);
+    hipLaunchKernelGGL(k_trk_compact, dim3(n_lanes), dim3(TRK_THREADS), 0, s, d, dl, 1);
+    // step 4
+    if (n_rs > 0) {
+        hipLaunchKernelGGL(k_trk_rs_off, dim3(1), dim3(64), 0, s, d, drsl, n_rs);
+        hipLaunchKernelGGL(k_trk_rs_pack, dim3((d.cap + 255) / 256, 2 * n_rs), dim3(256), 0, s, d, dl, drsl);
+        RansacArgs a;
+        a.set_off = d.rs_off;
+        a.pts_prev = d.rs_prev; a.pts_curr = d.rs_curr;
+        a.R = (const double*)(dv + o_rsR); a.intr = (const double*)(dv + o_rsK);
+        a.coeffs = (const double*)(dv + o_rsk); a.model = (const int32_t*)(dv + o_rsm);
+        a.draws = (const uint32_t*)(dv + o_draw);
+        a.work = d.rs_work; a.inlier = d.rs_inl; a.info = d.rs_info;
+        a.inlier_error = inlier_error; a.n_hyp = n_hyp;
+        hipLaunchKernelGGL(k_two_point_ransac, dim3(2 * n_rs), dim3(RS_THREADS), 0, s, a);
+    }
+    hipLaunchKernelGGL(k_trk_rs_flag, per256, dim3(256), 0, s, d, dl);
+    hipLaunchKernelGGL(k_trk_compact, dim3(n_lanes), dim3(TRK_THREADS), 0, s, d, dl, 2);
+    // step 6: the stages of mfe_fast_grid_sets
+    const GridWork& g = c->lanes;
+    const int32_t* dslots = (const int32_t*)(dv + o_slots);
+    MFE_HIP(hipMemsetAsync(g.mask, 1, NL * W * H, s));
+    hipLaunchKernelGGL(k_trk_mask_clear, dim3((7 * d.cap + 255) / 256, n_lanes), dim3(256), 0, s, d, g.mask, W, H);
+    hipLaunchKernelGGL(k_fast_sets, dim3((W + 15) / 16, (H + 15) / 16, n_lanes), dim3(256), 0, s, tab, dslots,
+                       threshold, g.score);
+    hipLaunchKernelGGL(k_fast_rows_sets, dim3((H + 3) / 4, n_lanes), dim3(256), 0, s, g, 0, 0);
+    hipLaunchKernelGGL(k_row_scan_sets, dim3(n_lanes), dim3(256), 0, s, g, o.n_total);
+    hipLaunchKernelGGL(k_fast_rows_sets, dim3((H + 3) / 4, n_lanes), dim3(256), 0, s, g, 1, max_kp);
+    GridArgs ga;
+    ga.xy = g.kp; ga.resp = g.kp + 2 * (size_t)g.kp_cap; ga.total = o.n_total;
+    ga.out_xy = d.g_xy; ga.out_resp = d.g_resp; ga.cell_count = d.g_cnt;
+    ga.cap = max_kp; ga.gh = d.gh; ga.gw = d.gw; ga.grid_col = d.grid_col; ga.k = d.grid_max;
+    hipLaunchKernelGGL(k_grid_select_sets, dim3(d.cells, n_lanes), dim3(256), 0, s, ga, g.kp_cap);
+    // steps 7-9
+    hipLaunchKernelGGL(k_trk_stereo_new, dim3(d.cells * d.grid_max, n_lanes), dim3(64), 0, s, d, dl, tab, win,
+                       max_level, max_iter, eps);
+    hipLaunchKernelGGL(k_trk_cells, dim3(n_lanes), dim3(TRK_THREADS), 0, s, d, dl, o);
+    hipLaunchKernelGGL(k_trk_assemble, dim3(d.cells, n_lanes), dim3(TRK_THREADS), 0, s, d, dl, o);
+    hipLaunchKernelGGL(k_trk_uv, per256, dim3(256), 0, s, d, dl, o);
+    MFE_HIP(hipGetLastError());
+    MFE_HIP(hipMemcpyAsync(h + o_n, dv + o_n, out_bytes, hipMemcpyDeviceToHost, s));
+    MFE_HIP(hipStreamSynchronize(s));
+    const int32_t* tot = (const int32_t*)(h + o_tot);
+    int over = -1;
+    for (size_t i = 0; i < NL; ++i) {
+        n_total[i] = tot[i];
+        if (tot[i] > max_kp && over < 0) over = (int)i;
+    }
+    if (over >= 0)   // the next tables hold a truncated frame: they stay the next ones
+        MFE_FAIL(-3, "lane %d: %d keypoints exceed the capacity of %d", lanes[over], tot[over], max_kp);
+    const int32_t* hn = (const int32_t*)(h + o_n);
+    for (size_t i = 0; i < NL; ++i)
+        if (hn[i] < 0 || (long long)hn[i] + (long long)d.cells * d.grid_min > d.cap)
+            MFE_FAIL(-2, "lane %d: the step left n = %d", lanes[i], hn[i]);
+    for (size_t i = 0; i < NL; ++i) {
+        const size_t N = (size_t)hn[i];
+        n_out[i] = hn[i];
+        next_id_out[i] = ((const int64_t*)(h + o_next))[i];
+        memcpy(counters + 4 * i, h + o_ctr + 16 * i, 16);
+        memcpy(ids_out + i * C, h + o_ids + 8 * i * C, 8 * N);
+        memcpy(uv_out + 4 * i * C, h + o_uv + 32 * i * C, 32 * N);
+        c->trk_cur[lanes[i]] ^= 1;
+        c->trk_n[lanes[i]] = hn[i];
+    }
     return 0;
 }
 

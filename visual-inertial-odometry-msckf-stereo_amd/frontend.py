@@ -22,6 +22,10 @@ published message -- and every image operator runs in the HIP kernels of
                                                 (mfe_upload_many, mfe_lk_sets, mfe_stereo_match_sets,
                                                 mfe_fast_grid_sets, mfe_undistort_sets,
                                                 include/msckf_lanes.h)
+  ids, lifetimes, grid lists (image.py:219-404)   with FrontendConfig.device_tracks the lanes' track
+                                                tables live on the device and a tracked frame of
+                                                all lanes is ONE call (mfe_tracks_step,
+                                                include/msckf_tracks.h), opt-in
 
 cv2 is absent here and on the GPU box: the kernels restate the published
 OpenCV 4.x algorithms (oracle/frontend_oracle.py), parity unpinned against cv2
@@ -55,6 +59,7 @@ from .config import _default_T_imu_cam0
 
 RADTAN, EQUIDISTANT = 0, 1
 _I32P = C.POINTER(C.c_int32)
+_I64P = C.POINTER(C.c_int64)
 
 FeatureMeasurement = namedtuple("FeatureMeasurement", ["id", "u0", "v0", "u1", "v1"])
 FeatureMsg = namedtuple("vio_feature_msg__", ["timestamp", "vio_features"])
@@ -124,6 +129,10 @@ class FrontendConfig:
     # one device call (include/msckf_pipeline.h) instead of Python around many small ones;
     # the published messages are the same
     device_pipeline: bool = False
+    # not in the reference: a MultiImageProcessor keeps the feature tracks on the device and runs a
+    # whole tracked frame of all lanes as one call (include/msckf_tracks.h); needs device_pipeline;
+    # the published messages are the same
+    device_tracks: bool = False
 
     @property
     def grid_num(self):
@@ -191,6 +200,7 @@ class Frontend:
         h = C.c_void_p()
         self._check(self.lib.mfe_create(device, self.W, self.H, nslot, max_level, self.max_points, C.byref(h)))
         self.h = h
+        self.tracks_cap = 0   # tracks_create
 
     def _check(self, rc):
         if rc < 0:
@@ -467,6 +477,100 @@ class Frontend:
                                                 R.ctypes.data_as(dp), nK.ctypes.data_as(dp)))
         return [out[off[i]:off[i + 1]] for i in range(S)]
 
+    # ---- the feature tracks kept on the device (include/msckf_tracks.h) ----
+    def tracks_create(self, n_lanes, cap, grid_row, grid_col, grid_min, grid_max):
+        """mfe_tracks_create: two tables of ``cap`` rows per lane, in this context."""
+        self._check(self.lib.mfe_tracks_create(self.h, int(n_lanes), int(cap), int(grid_row), int(grid_col),
+                                               int(grid_min), int(grid_max)))
+        self.tracks_cap = int(cap)
+
+    def tracks_put(self, lane, ids, lifetimes, cam0, cam1, next_id):
+        """mfe_tracks_put: the lane's current table (rows in publish order)."""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        life = np.ascontiguousarray(lifetimes, np.int32).reshape(-1)
+        c0 = np.ascontiguousarray(np.asarray(cam0, np.float32).reshape(-1, 2))
+        c1 = np.ascontiguousarray(np.asarray(cam1, np.float32).reshape(-1, 2))
+        if not len(ids) == len(life) == len(c0) == len(c1):
+            raise ValueError("table columns of %d, %d, %d, %d rows" % (len(ids), len(life), len(c0), len(c1)))
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.mfe_tracks_put(self.h, int(lane), len(ids), ids.ctypes.data_as(_I64P),
+                                            life.ctypes.data_as(_I32P), c0.ctypes.data_as(fp), c1.ctypes.data_as(fp),
+                                            int(next_id)))
+
+    def tracks_get(self, lane):
+        """mfe_tracks_get: (ids int64, lifetimes int32, cam0 float32 (n, 2), cam1, next_id)."""
+        cap = self.tracks_cap
+        ids, life = np.zeros(cap, np.int64), np.zeros(cap, np.int32)
+        c0, c1 = np.zeros((cap, 2), np.float32), np.zeros((cap, 2), np.float32)
+        n, nxt = C.c_int32(0), C.c_int64(0)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.mfe_tracks_get(self.h, int(lane), C.byref(n), ids.ctypes.data_as(_I64P),
+                                            life.ctypes.data_as(_I32P), c0.ctypes.data_as(fp), c1.ctypes.data_as(fp),
+                                            C.byref(nxt)))
+        k = n.value
+        return ids[:k].copy(), life[:k].copy(), c0[:k].copy(), c1[:k].copy(), nxt.value
+
+    def tracks_step(self, lanes, threshold, max_kp=1 << 16, inlier_error=0.0, n_hyp=0, win=15, max_level=3,
+                    max_iter=30, eps=0.01):
+        """mfe_tracks_step: one tracked frame for each ``TracksLane`` of
+        ``lanes``.  Returns one ``TracksResult`` per lane.  If a lane's
+        detection exceeds ``max_kp`` the MsckfError raised carries every
+        lane's ``n_total`` and no table has changed."""
+        S, cap = len(lanes), self.tracks_cap
+        i32 = lambda get: np.array([int(get(a)) for a in lanes], np.int32)
+        row = lambda get, w: np.ascontiguousarray(
+            np.array([np.asarray(get(a), float).ravel()[:w] for a in lanes], float).reshape(S, w))
+        ln, sp, s0, s1 = i32(lambda a: a.lane), i32(lambda a: a.slot_prev), i32(lambda a: a.slot_c0), \
+            i32(lambda a: a.slot_c1)
+        Hp = row(lambda a: a.Hpred, 9)
+        K0, k0, m0 = row(lambda a: a.cam0[0], 4), row(lambda a: a.cam0[2], 4), i32(lambda a: a.cam0[1])
+        K1, k1, m1 = row(lambda a: a.cam1[0], 4), row(lambda a: a.cam1[2], 4), i32(lambda a: a.cam1[1])
+        Rg, E = row(lambda a: a.R_guess, 9), row(lambda a: a.E, 9)
+        thr = np.array([float(a.stereo_threshold) for a in lanes], float)
+        flag = i32(lambda a: a.ransac is not None)
+        n_hyp = int(n_hyp)
+        R0, R1 = np.zeros((S, 9)), np.zeros((S, 9))
+        draws = np.zeros((S, 2, max(n_hyp, 0), 2), np.uint32)
+        for i, a in enumerate(lanes):
+            if a.ransac is not None:
+                R0[i], R1[i] = np.asarray(a.ransac[0], float).ravel(), np.asarray(a.ransac[1], float).ravel()
+                dr = np.asarray(a.ransac[2], np.uint32)
+                if dr.shape != draws.shape[1:]:
+                    raise ValueError("draws of shape %s, expected %s" % (dr.shape, draws.shape[1:]))
+                draws[i] = dr
+        n = np.zeros(S, np.int32)
+        ids = np.zeros((S, cap), np.int64)
+        uv = np.zeros((S, cap, 4))
+        ctr = np.zeros((S, _lib.TRACKS_COUNTERS), np.int32)
+        tot = np.zeros(S, np.int32)
+        nxt = np.zeros(S, np.int64)
+        dp = C.POINTER(C.c_double)
+        rc = self.lib.mfe_tracks_step(
+            self.h, S, ln.ctypes.data_as(_I32P), sp.ctypes.data_as(_I32P), s0.ctypes.data_as(_I32P),
+            s1.ctypes.data_as(_I32P), Hp.ctypes.data_as(dp), K0.ctypes.data_as(dp), m0.ctypes.data_as(_I32P),
+            k0.ctypes.data_as(dp), K1.ctypes.data_as(dp), m1.ctypes.data_as(_I32P), k1.ctypes.data_as(dp),
+            Rg.ctypes.data_as(dp), E.ctypes.data_as(dp), thr.ctypes.data_as(dp), flag.ctypes.data_as(_I32P),
+            R0.ctypes.data_as(dp), R1.ctypes.data_as(dp), draws.ctypes.data_as(C.POINTER(C.c_uint32)), int(win),
+            int(max_level), int(max_iter), float(eps), int(threshold), int(max_kp), float(inlier_error), n_hyp,
+            n.ctypes.data_as(_I32P), ids.ctypes.data_as(_I64P), uv.ctypes.data_as(dp), ctr.ctypes.data_as(_I32P),
+            tot.ctypes.data_as(_I32P), nxt.ctypes.data_as(_I64P))
+        if rc == -3:
+            err = _lib.MsckfError("mfe: %s (rc=%d)" % (self.lib.mfe_last_error().decode(), rc))
+            err.n_total = tot.copy()
+            raise err
+        self._check(rc)
+        return [TracksResult(int(n[i]), ids[i, :n[i]].copy(), uv[i, :n[i]].copy(), ctr[i].copy(), int(tot[i]),
+                             int(nxt[i])) for i in range(S)]
+
+
+# one lane's arguments of Frontend.tracks_step (include/msckf_tracks.h): cam0 / cam1 are (intrinsics,
+# model, coeffs); ransac is None or (R0, R1, draws uint32 (2, n_hyp, 2))
+TracksLane = namedtuple("TracksLane", ["lane", "slot_prev", "slot_c0", "slot_c1", "Hpred", "cam0", "cam1", "R_guess",
+                                       "E", "stereo_threshold", "ransac"])
+# counters: before_tracking, after_tracking, after_matching, after_ransac
+TracksResult = namedtuple("TracksResult", ["n", "ids", "uv", "counters", "n_total", "next_id"])
+TRACKS_COUNTER_NAMES = ("before_tracking", "after_tracking", "after_matching", "after_ransac")
+
 
 def _model(name):
     return EQUIDISTANT if name == "equidistant" else RADTAN
@@ -490,6 +594,10 @@ class ImageProcessor:
         elif not isinstance(config, FrontendConfig):
             config = FrontendConfig.from_reference(config)
         self.config = config
+        if config.device_tracks and not config.device_pipeline:
+            raise ValueError("device_tracks needs device_pipeline")
+        if config.device_tracks and fe is None:
+            raise ValueError("device_tracks is a switch of MultiImageProcessor's lanes (one lane serves one stream)")
         self.is_first_img = True
         self.next_feature_id = 0
         self.imu_msg_buffer = []
@@ -938,6 +1046,27 @@ class ImageProcessor:
             np.identity(3) if model0 == EQUIDISTANT else R_cam0_cam1, E, self.config.stereo_threshold)
         return [tuple(p) for p in c1], list(inliers.astype(bool))
 
+    def _tracks_lane(self, lane):
+        """This lane's arguments of Frontend.tracks_step for the frame at hand:
+        what _track_steps does on the host before its first request (the IMU
+        rotations, the RANSAC draws, the homography of predict_feature_tracking)
+        and the stereo arguments of _stereo_match_steps."""
+        R0, R1 = self.integrate_imu_data()
+        ransac = None
+        if self.config.ransac_enabled:   # once per tracked frame, as in _track_steps
+            ransac = (R0, R1, self.ransac_rng.integers(0, 1 << 32, size=(2, self.ransac_n_hyp, 2), dtype=np.uint32))
+        k = self.cam0_intrinsics
+        K = np.array([[k[0], 0.0, k[2]], [0.0, k[1], k[3]], [0.0, 0.0, 1.0]])
+        Hm = K @ R0 @ np.linalg.inv(K)
+        R_cam0_cam1 = self.R_cam1_imu.T @ self.R_cam0_imu
+        t_cam0_cam1 = self.R_cam1_imu.T @ (self.t_cam0_imu - self.t_cam1_imu)
+        model0 = _model(self.cam0_distortion_model)
+        return TracksLane(lane, self._slot_prev, self._slot_c0, self._slot_c1, Hm,
+                          (self.cam0_intrinsics, model0, self.cam0_distortion_coeffs),
+                          (self.cam1_intrinsics, _model(self.cam1_distortion_model), self.cam1_distortion_coeffs),
+                          np.identity(3) if model0 == EQUIDISTANT else R_cam0_cam1, _skew(t_cam0_cam1) @ R_cam0_cam1,
+                          self.config.stereo_threshold, ransac)
+
     def _add_new_steps(self):
         """add_new_features with the mask, the detection and the per-cell sieve
         as the one call mfe_fast_grid.  A cell comes back response-descending
@@ -1020,7 +1149,15 @@ class MultiImageProcessor:
 
     Lanes may differ in calibration, grid_min / grid_max_feature_num,
     stereo_threshold and the RANSAC switch, threshold and seed; they must
-    agree on the resolution and the fields of ``_SHARED_FIELDS``."""
+    agree on the resolution and the fields of ``_SHARED_FIELDS``.
+
+    With ``device_tracks`` in every lane's config the per-feature bookkeeping
+    leaves the host: the lanes' track tables live on the device
+    (include/msckf_tracks.h) and a step is ``mfe_upload_many`` plus ONE
+    ``mfe_tracks_step`` for all tracking lanes; a lane's first frame runs as
+    above and enters its table through ``mfe_tracks_put``.  The lanes then
+    also agree on grid_min / grid_max_feature_num and, among the RANSAC lanes,
+    on the threshold and success probability.  ``tracks(i)`` reads a table."""
 
     def __init__(self, n, config=None, lane_configs=None, device=0):
         if lane_configs is None:
@@ -1045,12 +1182,34 @@ class MultiImageProcessor:
                 if getattr(c, f) != getattr(cfgs[0], f):
                     raise ValueError("lane %d: %s = %r differs from lane 0's %r"
                                      % (i, f, getattr(c, f), getattr(cfgs[0], f)))
+        # device_tracks: all lanes or none, and what mfe_tracks_step shares between lanes
+        self.device_tracks = bool(cfgs[0].device_tracks)
+        ransac = [i for i, c in enumerate(cfgs) if c.ransac_enabled]
+        for i, c in enumerate(cfgs):
+            if bool(c.device_tracks) != self.device_tracks:
+                raise ValueError("lane %d: device_tracks = %r differs from lane 0's %r"
+                                 % (i, c.device_tracks, cfgs[0].device_tracks))
+            if not self.device_tracks:
+                continue
+            shared = [("grid_min_feature_num", 0), ("grid_max_feature_num", 0)]
+            if c.ransac_enabled:   # the RANSAC lanes among themselves
+                shared += [("ransac_threshold", ransac[0]), ("ransac_success_probability", ransac[0])]
+            for f, j in shared:
+                if getattr(c, f) != getattr(cfgs[j], f):
+                    raise ValueError("lane %d: %s = %r differs from lane %d's %r (device_tracks)"
+                                     % (i, f, getattr(c, f), j, getattr(cfgs[j], f)))
         (W, H), _ = res(cfgs[0])
         # a call's point limit covers all lanes: a first frame matches every keypoint it detects
         self.fe = Frontend(W, H, nslot=3 * n, max_level=cfgs[0].pyramid_levels, max_points=n << 16, device=device)
         self.lanes = [ImageProcessor(c, device=device, fe=self.fe, slot_base=3 * i) for i, c in enumerate(cfgs)]
         self.lk_kw = self.lanes[0].lk_kw
         self.launches = defaultdict(int)   # device calls per request kind
+        if self.device_tracks:   # the smallest tables the grid allows
+            c = cfgs[0]
+            self.fe.tracks_create(n, c.grid_num * (c.grid_min_feature_num + c.grid_max_feature_num), c.grid_row,
+                                  c.grid_col, c.grid_min_feature_num, c.grid_max_feature_num)
+            self._tracks_ransac = ((cfgs[ransac[0]].ransac_threshold, self.lanes[ransac[0]].ransac_n_hyp)
+                                   if ransac else (0.0, 0))
 
     def __len__(self):
         return len(self.lanes)
@@ -1064,10 +1223,20 @@ class MultiImageProcessor:
     def stereo_callbacks(self, msgs):
         """``msgs``: {lane index: stereo_msg}.  Returns {lane index:
         FeatureMsg}, as the lanes' own stareo_callback would."""
-        gens, pending, out = {}, {}, {}
+        if self.device_tracks:
+            return self._tracks_callbacks(msgs)
+        gens, out = {}, {}
         for i, m in msgs.items():
             gens[i] = self.lanes[i]._frame_steps(m)
-            self._advance(i, gens[i], None, pending, out, first=True)
+        self._pump(gens, out)
+        return out
+
+    def _pump(self, gens, out):
+        """Runs the lanes' generators to their ends, each kind of request served
+        for all lanes waiting at it with one call; out[lane] = its generator's value."""
+        pending = {}
+        for i, gen in gens.items():
+            self._advance(i, gen, None, pending, out, first=True)
         while pending:
             kind = min((r[0] for r in pending.values()), key=lambda k: _REQUEST_ORDER[k])
             group = [i for i, r in pending.items() if r[0] == kind]
@@ -1079,7 +1248,53 @@ class MultiImageProcessor:
             for i, res in zip(group, results):
                 del pending[i]
                 self._advance(i, gens[i], res, pending, out)
+
+    def tracks(self, i):
+        """Lane i's track table on the device (device_tracks): (ids, lifetimes,
+        cam0, cam1, next_id), rows in publish order."""
+        return self.fe.tracks_get(i)
+
+    def _tracks_callbacks(self, msgs):
+        """stereo_callbacks with the tracks on the device: one upload for all
+        lanes, the first-frame lanes on their generators (then tracks_put), and
+        ONE tracks_step for all tracking lanes."""
+        lanes, out = self.lanes, {}
+        for i, m in msgs.items():
+            lanes[i].cam0_curr_img_msg, lanes[i].cam1_curr_img_msg = m.cam0_msg, m.cam1_msg
+        self._serve("upload", [next(lanes[i]._upload_steps()) for i in msgs])
+        first = [i for i in msgs if lanes[i].is_first_img]
+        if first:
+            self._pump({i: self._first_frame_tracks_steps(i) for i in first}, out)
+        tracking = [i for i in msgs if i not in first]
+        if tracking:
+            self.launches["tracks_step"] += 1
+            inlier_error, n_hyp = self._tracks_ransac
+            res = self.fe.tracks_step([lanes[i]._tracks_lane(i) for i in tracking], lanes[0].config.fast_threshold,
+                                      inlier_error=inlier_error, n_hyp=n_hyp, **self.lk_kw)
+            for i, r in zip(tracking, res):
+                ip = lanes[i]
+                ip.num_features.update(zip(TRACKS_COUNTER_NAMES, (int(v) for v in r.counters)))
+                ip.next_feature_id = r.next_id
+                out[i] = FeatureMsg(ip.cam0_curr_img_msg.vio_timestamp__,
+                                    [FeatureMeasurement(k, *u) for k, u in zip(r.ids.tolist(), r.uv.tolist())])
+                ip._end_frame()
         return out
+
+    def _first_frame_tracks_steps(self, i):
+        """A lane's first frame (the images are uploaded) on the existing path;
+        its features then enter the lane's device table."""
+        ip = self.lanes[i]
+        yield from ip._first_frame_steps()
+        ip.is_first_img = False
+        try:
+            msg = yield from ip._publish_steps()
+            feats = list(chain.from_iterable(ip.curr_features))
+            self.launches["tracks_put"] += 1
+            self.fe.tracks_put(i, [f.id for f in feats], [f.lifetime for f in feats], [f.cam0_point for f in feats],
+                               [f.cam1_point for f in feats], ip.next_feature_id)
+            return msg
+        finally:
+            ip._end_frame()
 
     def _advance(self, i, gen, value, pending, out, first=False):
         try:
