@@ -7,9 +7,13 @@ frames/s of both, the batched launch counts, and ATE vs ground truth.  The
 replayed messages (the front-end's output) are built before both timed
 regions.
 
-    python tools/bench_sequences.py [--seqs 11] [--frames 200] [--fp32]
+    python tools/bench_sequences.py [--seqs 11] [--frames 200] [--fp32] [--device-map]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         tools/bench_sequences.py --seqs 11      # sequences dealt round-robin over N GPUs
+
+--device-map keeps the lanes' feature maps on the device (msckf_map.h) and
+feeds the frames as array messages (msckf.FeatureArrays); --profile prints a
+cProfile split of the batched replay to stderr.
 
 On N GPUs every rank replays its share of the sequences (replicas.shard) on
 its own device; the replicas' host TCP hub (msckf_amd.replicas, no RCCL:
@@ -40,20 +44,32 @@ def main():
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--fp32", action="store_true")
     ap.add_argument("--no-single", action="store_true")
+    ap.add_argument("--device-map", action="store_true")
+    ap.add_argument("--profile", action="store_true")
     a = ap.parse_args()
     dtype = np.float32 if a.fp32 else np.float64
     grp = replicas.init()
     mine = replicas.shard(list(range(a.seqs)), grp.rank, grp.world)
     streams = [FeatureStream.from_synthetic(synth.make_sequence(a.frames, 100 + i)) for i in mine]
     n_frames = sum(s.n_frames for s in streams)
-    multi = MultiMSCKF(len(streams), dtype=dtype, device=grp.local_rank) if streams else None
+    multi = MultiMSCKF(len(streams), dtype=dtype, device=grp.local_rank,
+                       device_map=a.device_map) if streams else None
     # the messages are the front-end's output: built before either timed
     # region (as the bench's ATE leg does), fresh objects for each run
-    msgs = [s.messages() for s in streams]
+    msgs = [s.messages(arrays=a.device_map) for s in streams]
     grp.barrier()
+    prof = None
+    if a.profile:
+        import cProfile
+        prof = cProfile.Profile()
+        prof.enable()
     t0 = time.perf_counter()
     trajs = multi.run_streams(streams, messages=msgs) if multi else []
     el_b = grp.max_over_ranks(time.perf_counter() - t0)
+    if prof is not None:
+        import pstats
+        prof.disable()
+        pstats.Stats(prof, stream=sys.stderr).sort_stats("tottime").print_stats(25)
     total_frames = grp.sum_over_ranks(n_frames)
     launches = dict(multi.launches) if multi else {}
     if multi:
@@ -61,13 +77,16 @@ def main():
     out = {"config": "SURVEY config 4 shape: %d synthetic stereo+IMU sequences x %d frames, %s, %d GPU(s)"
                      % (a.seqs, a.frames, "fp32" if a.fp32 else "fp64", grp.world),
            "batched_frames_per_s": round(total_frames / el_b, 1), "batched_s": round(el_b, 2),
-           "batched_launches_rank0": launches,
+           "device_map": bool(a.device_map), "batched_launches_rank0": launches,
            "ate_vs_gt_m_rank0": [round(ate(t, s.gt), 5) for t, s in zip(trajs, streams)]}
     if not a.no_single and grp.world == 1:
         evs = [s.events() for s in streams]
+        if a.device_map:
+            evs = [[(k, m if k == 0 else s.frame_arrays(j)) for (k, m), j in
+                    zip(ev, np.cumsum([k for k, _ in ev]) - 1)] for s, ev in zip(streams, evs)]
         t0 = time.perf_counter()
         for s, ev in zip(streams, evs):
-            flt = msckf_amd.MSCKF(dtype=dtype)
+            flt = msckf_amd.MSCKF(dtype=dtype, device_map=a.device_map)
             replay(flt, s, events=ev)
             flt.close()
         el_s = time.perf_counter() - t0

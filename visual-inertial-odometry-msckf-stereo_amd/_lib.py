@@ -147,6 +147,22 @@ FRONTEND_TRACKS_SIGS = {
 }
 TRACKS_EXPORTED = tuple(FRONTEND_TRACKS_SIGS)
 
+_U64 = C.POINTER(C.c_uint64)
+# the filter's feature map kept on the device (include/msckf_map.h), same library and context
+MAP_LOAD_LOST, MAP_LOAD_PRUNE_TRI, MAP_LOAD_PRUNE_UPDATE = 0, 1, 2
+MAP_INFO = 4
+MAP_SIGS = {
+    "msckf_map_create": (C.c_int, [_P, C.c_int, _D]),
+    "msckf_map_clear": (C.c_int, [_P, C.c_int, _I]),
+    "msckf_map_put": (C.c_int, [_P, C.c_int, C.c_int, _I64, _U64, _D, _D, _U8]),
+    "msckf_map_get": (C.c_int, [_P, C.c_int, _I, _I64, _U64, _D, _D, _U8]),
+    "msckf_map_add_lost": (C.c_int, [_P, C.c_int, _I, _I, _I64, _D, _I, _I, _I, _I64, _I]),
+    "msckf_map_prune_select": (C.c_int, [_P, C.c_int, _I, _I, _I, _I, _I64, _I]),
+    "msckf_map_load": (C.c_int, [_P, C.c_int, C.c_int, _I, _I, _I, _I, _D]),
+    "msckf_map_prune_commit": (C.c_int, [_P, C.c_int, _I, _I, _I, _U8, _D]),
+}
+MAP_EXPORTED = tuple(MAP_SIGS)
+
 # multi-GPU replica transport, RCCL (include/msckf_replicas.h), same library
 REPLICA_SIGS = {
     "msckf_rccl_unique_id": (C.c_int, [_U8]),
@@ -175,6 +191,7 @@ def load_library(path: str = LIB_PATH):
         for name, (res, args) in (list(_SIGS.items()) + list(FRONTEND_SIGS.items()) +
                                   list(FRONTEND_RANSAC_SIGS.items()) + list(FRONTEND_PIPELINE_SIGS.items()) +
                                   list(FRONTEND_LANES_SIGS.items()) + list(FRONTEND_TRACKS_SIGS.items()) +
+                                  list(MAP_SIGS.items()) +
                                   list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res
@@ -234,6 +251,7 @@ class Context:
         self.h = h
         self.lock = threading.RLock()
         self._pending = None   # the loaded batch's results, not read back yet (Pending)
+        self.map_cap = None    # rows per filter of the feature map (map_create); None: the context has none
 
     def _check(self, rc):
         if rc < 0:
@@ -460,6 +478,104 @@ class Context:
         self._check(self.lib.msckf_batch_results(self.h, _ptr(acc, C.c_uint8), _ptr(gam, C.c_double),
                                                  _ptr(p, C.c_double), _ptr(v, C.c_uint8), _ptr(rows, C.c_int32)))
         return acc.astype(bool), gam, p, v.astype(bool), rows
+
+    # ---- the feature map on the device (msckf_map.h) ----
+    def map_create(self, cap):
+        from .config import CHI2_05
+        tab = _f64(CHI2_05[:99])
+        with self.lock:
+            self._check(self.lib.msckf_map_create(self.h, int(cap), _ptr(tab, C.c_double)))
+        self.map_cap = int(cap)
+
+    def map_clear(self, filters):
+        filters = _i32(filters)
+        with self.lock:
+            self._check(self.lib.msckf_map_clear(self.h, len(filters), _ptr(filters, C.c_int32)))
+
+    def map_put(self, f, ids, mask, z, p_w, init):
+        """Writes filter ``f``'s table: ids [n], mask uint64 [n][2], z
+        [n][n_cam_capacity][4], p_w [n][3], init [n]."""
+        ids = np.ascontiguousarray(ids, np.int64)
+        n = len(ids)
+        mask = np.ascontiguousarray(mask, np.uint64).reshape(n, 2)
+        z = _f64(z, (n, self.Nmax, 4))
+        p_w = _f64(p_w, (n, 3))
+        init = np.ascontiguousarray(init, np.uint8).reshape(n)
+        with self.lock:
+            self._check(self.lib.msckf_map_put(self.h, f, n, _ptr(ids, C.c_int64), _ptr(mask, C.c_uint64),
+                                               _ptr(z, C.c_double), _ptr(p_w, C.c_double), _ptr(init, C.c_uint8)))
+
+    def map_get(self, f):
+        """Filter ``f``'s table: (ids, mask, z, p_w, init), n rows each."""
+        cap = self.map_cap or 1   # without a map the library refuses (-1) before it writes anything
+        n = C.c_int32(0)
+        ids, mask = np.zeros(cap, np.int64), np.zeros((cap, 2), np.uint64)
+        z, p_w, init = np.zeros((cap, self.Nmax, 4)), np.zeros((cap, 3)), np.zeros(cap, np.uint8)
+        with self.lock:
+            self._check(self.lib.msckf_map_get(self.h, f, C.byref(n), _ptr(ids, C.c_int64), _ptr(mask, C.c_uint64),
+                                               _ptr(z, C.c_double), _ptr(p_w, C.c_double), _ptr(init, C.c_uint8)))
+        n = n.value
+        return ids[:n].copy(), mask[:n].copy(), z[:n].copy(), p_w[:n].copy(), init[:n].astype(bool)
+
+    def _map_desc(self, nfilt):
+        cap = self.map_cap or 1   # without a map the library refuses (-1) before it writes anything
+        return np.zeros((nfilt, cap), np.int64), np.zeros((nfilt, cap, MAP_INFO), np.int32)
+
+    def map_add_lost(self, filters, msg_off, ids, z):
+        """One message per listed filter.  Returns per filter (tracked,
+        n_before, candidate ids, candidate info [n][4] = M, 0, initialised, row)."""
+        filters, msg_off = _i32(filters), _i32(msg_off)
+        ids = np.ascontiguousarray(ids, np.int64)
+        z = _f64(z, (len(ids), 4))
+        k = len(filters)
+        tracked, nbef, ncand = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        did, dinfo = self._map_desc(k)
+        with self.lock:
+            self._check(self.lib.msckf_map_add_lost(
+                self.h, k, _ptr(filters, C.c_int32), _ptr(msg_off, C.c_int32), _ptr(ids, C.c_int64),
+                _ptr(z, C.c_double), _ptr(tracked, C.c_int32), _ptr(nbef, C.c_int32), _ptr(ncand, C.c_int32),
+                _ptr(did, C.c_int64), _ptr(dinfo, C.c_int32)))
+        return [(int(tracked[w]), int(nbef[w]), did[w, :ncand[w]].copy(), dinfo[w, :ncand[w]].copy())
+                for w in range(k)]
+
+    def map_prune_select(self, filters, slot_off, slots):
+        """Per listed filter (involved ids, info [n][4] = M, involved count, initialised, row)."""
+        filters, slot_off, slots = _i32(filters), _i32(slot_off), _i32(slots)
+        k = len(filters)
+        ninv = np.zeros(k, np.int32)
+        did, dinfo = self._map_desc(k)
+        with self.lock:
+            self._check(self.lib.msckf_map_prune_select(
+                self.h, k, _ptr(filters, C.c_int32), _ptr(slot_off, C.c_int32), _ptr(slots, C.c_int32),
+                _ptr(ninv, C.c_int32), _ptr(did, C.c_int64), _ptr(dinfo, C.c_int32)))
+        return [(did[w, :ninv[w]].copy(), dinfo[w, :ninv[w]].copy()) for w in range(k)]
+
+    def map_load(self, mode, filters, feat_off, rows, counts, p_w=None):
+        """msckf_map_load; the batch holds the features in ascending filter
+        slot.  Returns {slot: (first, end)} feature ranges of the batch."""
+        self.settle()
+        filters, feat_off, rows, counts = _i32(filters), _i32(feat_off), _i32(rows), _i32(counts)
+        p_w = _f64(p_w, (len(rows), 3)) if p_w is not None else None
+        with self.lock:
+            self._check(self.lib.msckf_map_load(self.h, int(mode), len(filters), _ptr(filters, C.c_int32),
+                                                _ptr(feat_off, C.c_int32), _ptr(rows, C.c_int32),
+                                                _ptr(counts, C.c_int32), _ptr(p_w, C.c_double)))
+        self._nf = int(feat_off[-1]) if len(feat_off) else 0
+        ranges, a = {}, 0
+        for w in np.argsort(filters, kind="stable"):
+            nfw = int(feat_off[w + 1] - feat_off[w])
+            ranges[int(filters[w])] = (a, a + nfw)
+            a += nfw
+        return ranges
+
+    def map_prune_commit(self, filters, ent_off, rows, valid, p_w):
+        filters, ent_off, rows = _i32(filters), _i32(ent_off), _i32(rows)
+        valid = np.ascontiguousarray(valid, np.uint8).reshape(len(rows))
+        p_w = _f64(p_w, (len(rows), 3))
+        with self.lock:
+            self._check(self.lib.msckf_map_prune_commit(self.h, len(filters), _ptr(filters, C.c_int32),
+                                                        _ptr(ent_off, C.c_int32), _ptr(rows, C.c_int32),
+                                                        _ptr(valid, C.c_uint8), _ptr(p_w, C.c_double)))
 
     def device_info(self):
         """(HIP device index, PCI bus id) this context runs on."""

@@ -12,8 +12,10 @@
 #include <vector>
 
 #include "../../include/msckf_hip.h"
+#include "../../include/msckf_map.h"
 #include "msckf_common.h"
 #include "msckf_launch.h"
+#include "msckf_map_dev.h"
 #include "msckf_subbatch.h"
 
 using namespace msckf;
@@ -209,6 +211,18 @@ struct msckf_ctx {
     bool has_snapshot = false;
     PinnedRing up;      // upload staging
     PinnedBuf down;     // download staging
+    // the feature map on the device (msckf_map.h): absent until msckf_map_create
+    struct Map {
+        bool on = false;
+        int cap = 0;
+        DBuf<unsigned char> store;         // both table sets
+        MapDev dev{};
+        std::vector<int> n, cur, nprev;    // per filter: rows, which set is current, rows of the table add_lost read
+        std::vector<char> lost_ok, sel_ok; // per filter: the other set still holds what add_lost read / a select is open
+        std::vector<unsigned long long> rm; // [B][2]: the removed slots of the open select
+        DBuf<unsigned char> in, out, aux;  // a call's input block, a select's outputs, a load's fill inputs
+        DBuf<double> chi2;                 // CHI2_05, 99 entries
+    } map;
 };
 
 namespace {
@@ -430,33 +444,61 @@ int check_ctx(msckf_ctx* c, int filter) {
     return 0;
 }
 
-// Load a feature batch (all filters) into HBM.  feat_off == nullptr means
-// all nf features belong to `single_filter`.
-template <typename T>
-int load_features(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filter, const int32_t* obs_off,
-                  const int32_t* obs_cam, const double* obs_z, const double* p_w, const double* chi2) {
-    std::vector<int> h_off(c->B + 1, 0);
+// Loading a feature batch is a PLAN and a FILL.  The plan is everything derived
+// from the per-feature observation counts and the per-filter feature counts:
+// the checks of those, the workspace sizes, the gating lists by block count, the
+// segment classes, the ysq offsets, the arena layout, and the staging of the
+// offsets and lists.  The fill is obs_cam, obs_z, p_w, valid and chi2:
+// msckf_batch_load copies them from the host's arrays through the same pinned
+// buffer (one H2D copy for plan and fill together), msckf_map_load gathers them
+// on the device from the feature map's tables (msckf_map.hip).
+struct LoadPlan {
+    int nf = 0, maxM = 0;
+    size_t nobs = 0;
+    std::vector<int> h_off, h_filt, gflat, sflat;
+    std::vector<long long> ysq;
+    size_t o_cam = 0, o_z = 0, o_chi = 0, o_val = 0, o_pw = 0;   // arena offsets of the fill
+    unsigned char* h = nullptr;   // pinned staging of the inputs, [0, in_bytes)
+    size_t in_bytes = 0;
+};
+
+// Plan, part 1: the per-filter split and the per-feature counts.  feat_off ==
+// nullptr means all nf features belong to `single_filter`.
+int plan_counts(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filter, const int32_t* obs_off,
+                LoadPlan& pl) {
+    std::vector<int>& h_off = pl.h_off;
+    h_off.assign(c->B + 1, 0);
     if (feat_off) {
         for (int b = 0; b <= c->B; ++b) h_off[b] = feat_off[b];
         nf = h_off[c->B];
     } else {
         for (int b = 0; b <= c->B; ++b) h_off[b] = b <= single_filter ? 0 : nf;
     }
-    std::vector<int> h_filt(std::max(nf, 1), 0);
+    pl.nf = nf;
+    pl.h_filt.assign(std::max(nf, 1), 0);
     for (int b = 0; b < c->B; ++b) {
         if (h_off[b + 1] < h_off[b]) FAIL(-1, "feat_off not monotone");
-        for (int f = h_off[b]; f < h_off[b + 1]; ++f) h_filt[f] = b;
+        for (int f = h_off[b]; f < h_off[b + 1]; ++f) pl.h_filt[f] = b;
     }
     if (obs_off[0] != 0) FAIL(-1, "obs_off[0] must be 0");
-    const size_t nobs = nf > 0 ? (size_t)obs_off[nf] : 0;
-    std::vector<long long> ysq(nf + 1, 0);
-    int maxM = 0;
+    pl.nobs = nf > 0 ? (size_t)obs_off[nf] : 0;
+    pl.ysq.assign(nf + 1, 0);
+    pl.maxM = 0;
     for (int f = 0; f < nf; ++f) {
         int M = obs_off[f + 1] - obs_off[f];
-        maxM = std::max(maxM, M);
-        int b = h_filt[f];
+        pl.maxM = std::max(pl.maxM, M);
+        int b = pl.h_filt[f];
         if (M < 1 || M > 128) FAIL(-1, "feature %d has %d observations (1..128 supported)", f, M);
         if (M > c->h_ncams[b]) FAIL(-1, "feature %d has more observations than cam states", f);
+        pl.ysq[f + 1] = pl.ysq[f] + 16LL * M * M;
+    }
+    return 0;
+}
+
+// The host's observation lists: cam slots in range and distinct per feature.
+int check_obs_cams(msckf_ctx* c, const LoadPlan& pl, const int32_t* obs_off, const int32_t* obs_cam) {
+    for (int f = 0; f < pl.nf; ++f) {
+        const int b = pl.h_filt[f];
         unsigned long long seen[2] = {0, 0};   // cam slots < 128: k_info's cam -> record table needs them distinct
         for (int i = obs_off[f]; i < obs_off[f + 1]; ++i) {
             const int cam = obs_cam[i];
@@ -465,8 +507,19 @@ int load_features(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filt
             if ((seen[cam >> 6] >> (cam & 63)) & 1ull) FAIL(-1, "feature %d observes cam slot %d twice", f, cam);
             seen[cam >> 6] |= 1ull << (cam & 63);
         }
-        ysq[f + 1] = ysq[f] + 16LL * M * M;
     }
+    return 0;
+}
+
+// Plan, part 2: workspaces, lists, the arena and the staging of the plan's own
+// arrays.  fill_to: 0 = the staging ends before obs_z (the fill is the
+// device's), 1 = before p_w, 2 = after p_w.
+template <typename T>
+int plan_stage(msckf_ctx* c, const int32_t* obs_off, int fill_to, LoadPlan& pl) {
+    const int nf = pl.nf, maxM = pl.maxM;
+    const size_t nobs = pl.nobs;
+    const std::vector<long long>& ysq = pl.ysq;
+    const std::vector<int>& h_off = pl.h_off;
     const size_t ts = sizeof(T);
     HIPC(c->row_off.ensure(nf + 1));
     HIPC(c->obs_ws.ensure(((feature_needs_compact(maxM) ? nobs : 0) * OBS_WS + OBS_WS) * ts));
@@ -476,7 +529,7 @@ int load_features(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filt
     // the (4M)^2 global gating scratch is k_gate's alone (M > GATE_TILE_MAXM)
     if (feature_needs_compact(maxM)) HIPC(c->ysq.ensure((size_t)(ysq[nf] + 16) * ts));
     // the gating lists (msckf_gate_routes.h), ascending feature index inside a list
-    std::vector<int> gflat;
+    std::vector<int>& gflat = pl.gflat;
     GateClasses gc;
     {
         std::vector<int> lists[GATE_NLIST];
@@ -492,7 +545,7 @@ int load_features(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filt
         gc.off[GATE_NLIST] = (int)gflat.size();
     }
     // segment classes of the per-feature kernels (M <= S)
-    std::vector<int> sflat;
+    std::vector<int>& sflat = pl.sflat;
     SegClasses sc;
     for (int k = 0; k < SegClasses::NC; ++k) {
         sc.off[k] = (int)sflat.size();
@@ -518,7 +571,8 @@ int load_features(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filt
     const size_t o_gl = seg(gflat.size() * sizeof(int)), o_sl = seg(sflat.size() * sizeof(int));
     const size_t o_z = seg(nobs * 4 * ts), o_chi = seg(nf * ts);
     const size_t o_val = seg(nf), o_pw = seg(nf * 3 * ts);
-    const size_t in_bytes = p_w ? total : o_pw;   // p_w uploaded only when given (else triangulation writes it)
+    // p_w uploaded only when given (else triangulation writes it)
+    const size_t in_bytes = fill_to == 2 ? total : fill_to == 1 ? o_pw : o_z;
     const size_t o_inc = seg(nf), o_gam = seg(nf * ts), o_acc = seg(nf);
     HIPC(c->batch.ensure(total + 256));
     unsigned char* d = c->batch.p;
@@ -545,39 +599,25 @@ int load_features(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filt
     unsigned char* h = nullptr;
     HIPC(c->up.get(in_bytes, &h));
     auto put = [&](size_t o, const void* src, size_t bytes) { if (bytes) std::memcpy(h + o, src, bytes); };
-    auto putT = [&](size_t o, const double* src, size_t n) {
-        T* v = reinterpret_cast<T*>(h + o);
-        for (size_t i = 0; i < n; ++i) v[i] = (T)src[i];
-    };
-    put(o_filt, h_filt.data(), nf * sizeof(int));
+    put(o_filt, pl.h_filt.data(), nf * sizeof(int));
     put(o_off, h_off.data(), (c->B + 1) * sizeof(int));
     put(o_obs, obs_off, (nf + 1) * sizeof(int));
-    put(o_cam, obs_cam, nobs * sizeof(int));
     put(o_ysq, ysq.data(), (nf + 1) * sizeof(long long));
     put(o_gl, gflat.data(), gflat.size() * sizeof(int));
     put(o_sl, sflat.data(), sflat.size() * sizeof(int));
-    putT(o_z, obs_z, nobs * 4);
-    if (chi2) {
-        putT(o_chi, chi2, nf);
-    } else {
-        T* v = reinterpret_cast<T*>(h + o_chi);
-        for (int i = 0; i < nf; ++i) v[i] = (T)1e300;
-    }
-    // valid: 2 = position given by the host (never re-triangulated), 0 = to be
-    // triangulated (p_w NULL, or a NaN row: triangulation fused into the update)
-    if (p_w) {
-        putT(o_pw, p_w, (size_t)nf * 3);
-        for (int f = 0; f < nf; ++f) {
-            const double* r = p_w + 3 * (size_t)f;
-            h[o_val + f] = (std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2])) ? 2 : 0;
-        }
-    } else {
-        std::memset(h + o_val, 0, nf);
-    }
-    HIPC(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, c->stream));
+    pl.o_cam = o_cam, pl.o_z = o_z, pl.o_chi = o_chi, pl.o_val = o_val, pl.o_pw = o_pw;
+    pl.h = h;
+    pl.in_bytes = in_bytes;
+    return 0;
+}
+
+// Plan, part 3: the copy of the staged inputs and the context's record of the batch.
+int plan_commit(msckf_ctx* c, const int32_t* obs_off, const LoadPlan& pl) {
+    const std::vector<int>& h_off = pl.h_off;
+    HIPC(hipMemcpyAsync(c->batch.p, pl.h, pl.in_bytes, hipMemcpyHostToDevice, c->stream));
     HIPC(c->up.mark(c->stream));
-    c->nf = nf;
-    c->maxM = maxM;
+    c->nf = pl.nf;
+    c->maxM = pl.maxM;
     c->max_nf = c->max_obs = 0;
     for (int b = 0; b < c->B; ++b) {
         c->max_nf = std::max(c->max_nf, h_off[b + 1] - h_off[b]);
@@ -588,9 +628,46 @@ int load_features(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filt
     c->gram = !info_fused_fits(c->Nmax, c->max_nf);
     // (allocated in either case: k_feature writes the records of ill-conditioned
     // features for the fused assembly too -- FQR_FLAG)
-    HIPC(c->obs_g.ensure(((size_t)nobs + 1) * OBG_STRIDE * sizeof(double)));
+    HIPC(c->obs_g.ensure(((size_t)pl.nobs + 1) * OBG_STRIDE * sizeof(double)));
     c->h_feat_off = h_off;
     return 0;
+}
+
+// Load a feature batch (all filters) into HBM from the host's arrays: the plan
+// and the fill in one pinned buffer, one copy.
+template <typename T>
+int load_features(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filter, const int32_t* obs_off,
+                  const int32_t* obs_cam, const double* obs_z, const double* p_w, const double* chi2) {
+    LoadPlan pl;
+    if (int r = plan_counts(c, nf, feat_off, single_filter, obs_off, pl)) return r;
+    if (int r = check_obs_cams(c, pl, obs_off, obs_cam)) return r;
+    if (int r = plan_stage<T>(c, obs_off, p_w ? 2 : 1, pl)) return r;
+    nf = pl.nf;
+    unsigned char* h = pl.h;
+    auto putT = [&](size_t o, const double* src, size_t n) {
+        T* v = reinterpret_cast<T*>(h + o);
+        for (size_t i = 0; i < n; ++i) v[i] = (T)src[i];
+    };
+    if (pl.nobs) std::memcpy(h + pl.o_cam, obs_cam, pl.nobs * sizeof(int));
+    putT(pl.o_z, obs_z, pl.nobs * 4);
+    if (chi2) {
+        putT(pl.o_chi, chi2, nf);
+    } else {
+        T* v = reinterpret_cast<T*>(h + pl.o_chi);
+        for (int i = 0; i < nf; ++i) v[i] = (T)1e300;
+    }
+    // valid: 2 = position given by the host (never re-triangulated), 0 = to be
+    // triangulated (p_w NULL, or a NaN row: triangulation fused into the update)
+    if (p_w) {
+        putT(pl.o_pw, p_w, (size_t)nf * 3);
+        for (int f = 0; f < nf; ++f) {
+            const double* r = p_w + 3 * (size_t)f;
+            h[pl.o_val + f] = (std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2])) ? 2 : 0;
+        }
+    } else {
+        std::memset(h + pl.o_val, 0, nf);
+    }
+    return plan_commit(c, obs_off, pl);
 }
 
 // ---- lanes (msckf_subbatch.h) ----
@@ -1230,8 +1307,10 @@ int msckf_destroy(msckf_ctx_t* c) {
     for (hipStream_t s : {c->stream, c->side, c->stream1})
         if (s) (void)hipStreamSynchronize(s);
     for (auto* b : {&c->P, &c->imu, &c->cams, &c->P_snap, &c->imu_snap, &c->cams_snap, &c->Hthin, &c->Lc, &c->Vi, &c->Sii, &c->G, &c->Tm, &c->W, &c->Wk,
-                    &c->dx, &c->batch, &c->obs_ws, &c->obs_ht, &c->obs_g, &c->fqr, &c->tau, &c->ysq, &c->scratch})
+                    &c->dx, &c->batch, &c->obs_ws, &c->obs_ht, &c->obs_g, &c->fqr, &c->tau, &c->ysq, &c->scratch,
+                    &c->map.store, &c->map.in, &c->map.out, &c->map.aux})
         b->release();
+    c->map.chi2.release();
     for (auto* b : {&c->ncams, &c->ncams_snap, &c->ident, &c->info, &c->afail, &c->row_off, &c->iscratch})
         b->release();
     c->up.release();
@@ -1576,3 +1655,7 @@ int msckf_debug_kalman(msckf_ctx_t* c) {
 }
 
 }  // extern "C"
+
+// definitions, not declarations: the host side of include/msckf_map.h, kept in a file of its own but part of
+// this translation unit because it uses the context, the staging helpers and the loader plan above
+#include "msckf_map_api.inc"

@@ -1,0 +1,47 @@
+// msckf_map_dev.h -- device views and launcher declarations of the feature
+// map kept on the device (include/msckf_map.h; kernels in msckf_map.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace msckf {
+
+// One of a context's two table sets, fixed stride [filter][cap]:
+//   ids [B][cap], mask [B][cap][2], z [B][cap][Nmax][4], pw [B][cap][3], init [B][cap]
+struct MapTab {
+    int64_t* ids;
+    unsigned long long* mask;
+    double* z;
+    double* pw;
+    uint8_t* init;
+};
+struct MapDev {
+    MapTab t[2];
+    int cap, Nmax;
+};
+
+constexpr int MAP_HDR = 8;        // ints per named filter in a call's header (see each kernel)
+constexpr int MAP_OUT = 4;        // ints per named filter a select call returns
+constexpr int MAP_INFO = 4;       // ints per descriptor entry: M, involved count, initialised flag, row
+constexpr int MAP_MAX_CAP = 2048; // ids + two int tables in LDS: 16 B per row
+
+size_t map_lds_bytes(int cap);
+
+// hdr: [filter, n, table read, newest slot, msg first, msg end, descriptor stride (>= every n), -]
+void launch_map_add_lost(hipStream_t, const MapDev&, int nfilt, const int* hdr, const int64_t* msg_ids,
+                         const double* msg_z, int* out, int64_t* desc_id, int* desc_info);
+// hdr: [filter, n, table read, -, -, -, descriptor stride, -]; rm: the removed slots as a mask, two words per named filter
+void launch_map_prune_select(hipStream_t, const MapDev&, int nfilt, const int* hdr, const unsigned long long* rm,
+                             int* out, int64_t* desc_id, int* desc_info);
+// hdr: [filter, n, table read, -, entry first, entry end, -, -]; entries: row, valid flag, position
+void launch_map_prune_commit(hipStream_t, const MapDev&, int nfilt, const int* hdr, const unsigned long long* rm,
+                             const int* ent_row, const int* ent_valid, const double* ent_pw);
+// The fill of a loaded batch (msckf_map_load): per feature f of the arena,
+// row frow[f] of filter feat_filter[f]'s table sel[filter]; mode as MSCKF_MAP_LOAD_*.
+template <typename T>
+void launch_map_gather(hipStream_t, const MapDev&, int mode, int nf, const int* feat_filter, const int* obs_off,
+                       const int* frow, const int* sel, const unsigned long long* rm, const double* host_pw,
+                       const double* chi2_tab, T big, int* obs_cam, T* obs_z, T* chi2, uint8_t* valid, T* p_w);
+
+}  // namespace msckf

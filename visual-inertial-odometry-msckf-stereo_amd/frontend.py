@@ -56,6 +56,7 @@ import numpy as np
 
 from . import _lib
 from .config import _default_T_imu_cam0
+from .msckf import FeatureArrays, message_arrays
 
 RADTAN, EQUIDISTANT = 0, 1
 _I32P = C.POINTER(C.c_int32)
@@ -63,6 +64,14 @@ _I64P = C.POINTER(C.c_int64)
 
 FeatureMeasurement = namedtuple("FeatureMeasurement", ["id", "u0", "v0", "u1", "v1"])
 FeatureMsg = namedtuple("vio_feature_msg__", ["timestamp", "vio_features"])
+
+
+def _as_arrays(msg):
+    """A FeatureMsg as msckf.FeatureArrays (an array message stays as it is; None stays None)."""
+    if msg is None or isinstance(msg, FeatureArrays):
+        return msg
+    ids, uv = message_arrays(msg)
+    return FeatureArrays(msg.timestamp, ids, uv)
 
 
 class RansacInfo(namedtuple("RansacInfo", ["status", "n_raw", "scale", "unit", "mean_dist", "best_h", "best_count",
@@ -1220,16 +1229,19 @@ class MultiImageProcessor:
     def imu_callback(self, i, msg):
         self.lanes[i].imu_callback(msg)
 
-    def stereo_callbacks(self, msgs):
+    def stereo_callbacks(self, msgs, arrays=False):
         """``msgs``: {lane index: stereo_msg}.  Returns {lane index:
-        FeatureMsg}, as the lanes' own stareo_callback would."""
+        FeatureMsg}, as the lanes' own stareo_callback would.  ``arrays``:
+        array messages (msckf.FeatureArrays) instead -- with the tracks on the
+        device straight from the step's ids / uv, no tuple per feature;
+        otherwise converted once."""
         if self.device_tracks:
-            return self._tracks_callbacks(msgs)
+            return self._tracks_callbacks(msgs, arrays)
         gens, out = {}, {}
         for i, m in msgs.items():
             gens[i] = self.lanes[i]._frame_steps(m)
         self._pump(gens, out)
-        return out
+        return {i: _as_arrays(m) for i, m in out.items()} if arrays else out
 
     def _pump(self, gens, out):
         """Runs the lanes' generators to their ends, each kind of request served
@@ -1254,7 +1266,7 @@ class MultiImageProcessor:
         cam0, cam1, next_id), rows in publish order."""
         return self.fe.tracks_get(i)
 
-    def _tracks_callbacks(self, msgs):
+    def _tracks_callbacks(self, msgs, arrays=False):
         """stereo_callbacks with the tracks on the device: one upload for all
         lanes, the first-frame lanes on their generators (then tracks_put), and
         ONE tracks_step for all tracking lanes."""
@@ -1275,9 +1287,15 @@ class MultiImageProcessor:
                 ip = lanes[i]
                 ip.num_features.update(zip(TRACKS_COUNTER_NAMES, (int(v) for v in r.counters)))
                 ip.next_feature_id = r.next_id
-                out[i] = FeatureMsg(ip.cam0_curr_img_msg.vio_timestamp__,
-                                    [FeatureMeasurement(k, *u) for k, u in zip(r.ids.tolist(), r.uv.tolist())])
+                if arrays:
+                    out[i] = FeatureArrays(ip.cam0_curr_img_msg.vio_timestamp__, np.asarray(r.ids, np.int64),
+                                           np.asarray(r.uv, np.float64).reshape(-1, 4))
+                else:
+                    out[i] = FeatureMsg(ip.cam0_curr_img_msg.vio_timestamp__,
+                                        [FeatureMeasurement(k, *u) for k, u in zip(r.ids.tolist(), r.uv.tolist())])
                 ip._end_frame()
+        if arrays:   # the first-frame lanes' messages come from the existing path
+            out = {i: _as_arrays(m) for i, m in out.items()}
         return out
 
     def _first_frame_tracks_steps(self, i):

@@ -12,7 +12,10 @@ What runs on the GPU (through the C-ABI, libmsckf_hip.so): IMU covariance
 propagation, state augmentation, triangulation, measurement Jacobians +
 nullspace projection, gating, stacking, compression of the stacked rows
 (information assembly), the Kalman update and covariance compaction.  There is
-no CPU fallback.
+no CPU fallback.  With ``device_map=True`` the feature map is device state as
+well (include/msckf_map.h): adding observations, the lost-feature and prune
+selections and the packing of an update's observations are device calls, the
+host keeps the decisions' descriptors (ids, track lengths) for its logs.
 
 Every device interaction of a frame is expressed as a request yielded by a
 step generator (``_frame_steps``); ``feature_callback`` serves the requests
@@ -34,10 +37,24 @@ from collections import OrderedDict, namedtuple
 import numpy as np
 
 from . import _lib
-from .config import FilterConfig, chi2_threshold
+from .config import CHI2_05, FilterConfig, chi2_threshold
 from .geometry import Isometry3d, from_two_vectors, to_quaternion, to_rotation
 
 VioResult = namedtuple("vio_result", ["timestamp", "pose", "velocity", "cam0_pose"])
+# A feature message as arrays: ids int64 [n], uv float64 [n][4] (u0 v0 u1 v1).
+# Accepted wherever the reference's feature_msg tuple is.
+FeatureArrays = namedtuple("FeatureArrays", ["timestamp", "ids", "uv"])
+
+
+def message_arrays(feature_msg):
+    """(ids int64 [n], uv float64 [n][4]) of either message type."""
+    if isinstance(feature_msg, FeatureArrays):
+        return (np.ascontiguousarray(feature_msg.ids, np.int64),
+                np.ascontiguousarray(feature_msg.uv, np.float64).reshape(-1, 4))
+    fs = feature_msg.vio_features
+    ids = np.fromiter((f.id for f in fs), np.int64, len(fs))
+    uv = np.array([(f.u0, f.v0, f.u1, f.v1) for f in fs], np.float64).reshape(-1, 4)
+    return ids, uv
 
 
 class Feature:
@@ -49,6 +66,18 @@ class Feature:
         self.observations: "OrderedDict[int, np.ndarray]" = OrderedDict()
         self.position = np.zeros(3)
         self.is_initialized = False
+
+
+_CHI2 = np.array(CHI2_05[:99])
+
+
+def _chi2_of(dofs):
+    """chi2_threshold of an array of dofs (KeyError outside 1..99, as the dict)."""
+    dofs = np.asarray(dofs, np.int64)
+    bad = (dofs < 1) | (dofs > 99)
+    if bad.any():
+        raise KeyError(int(dofs[bad][0]))
+    return _CHI2[dofs - 1]
 
 
 def check_motion(observations, cams, threshold):
@@ -70,12 +99,20 @@ def check_motion(observations, cams, threshold):
 class MSCKF:
     ROW_CAP = 1500   # msckf.py:678
 
-    def __init__(self, config=None, dtype=np.float64, device=0, cam_capacity=None, ctx=None, slot=0):
+    def __init__(self, config=None, dtype=np.float64, device=0, cam_capacity=None, ctx=None, slot=0,
+                 device_map=False, map_capacity=1024):
+        """``device_map``: keep the feature map in the context's tables
+        (msckf_map.h) instead of ``map_server``'s dicts; ``map_capacity``: rows
+        per filter.  A shared ``ctx`` must already have its tables."""
         if config is None:
             config = FilterConfig()
         elif not isinstance(config, FilterConfig):
             config = FilterConfig.from_reference(config)
         self.config = config
+        self.device_map = bool(device_map)
+        if self.device_map and config.optimization.translation_threshold >= 0:
+            raise ValueError("device_map=True needs optimization.translation_threshold < 0 (it is %r): check_motion "
+                             "reads the cam poses on the host" % (config.optimization.translation_threshold,))
         cap = cam_capacity or (config.max_cam_state_size + 2)
         self._own_ctx = ctx is None
         self.ctx = ctx if ctx is not None else _lib.Context(config, n_filters=1, n_cam_capacity=cap, dtype=dtype,
@@ -83,7 +120,12 @@ class MSCKF:
         self.slot = slot
         self._lock = threading.RLock()
         self.imu_msg_buffer = []
-        self.map_server: "OrderedDict[int, Feature]" = OrderedDict()
+        if self.device_map:   # map_server is then a snapshot read from the device (a property of a subclass)
+            self.__class__ = _device_map_class(type(self))
+            if self._own_ctx:
+                self.ctx.map_create(map_capacity)
+        else:
+            self.map_server: "OrderedDict[int, Feature]" = OrderedDict()
         self.cam_ids: list = []            # cam-state ids in slot order (oldest first)
         self.imu_timestamp = None
         self.imu_id = None
@@ -133,6 +175,20 @@ class MSCKF:
     def state_cov(self):
         return self.ctx.get_state(self.slot, want_P=True)[2]
 
+    def _map_snapshot(self):
+        """Read-only copy of the device table in map_server's form."""
+        ids, mask, z, p_w, init = self.ctx.map_get(self.slot)
+        out = OrderedDict()
+        for i, fid in enumerate(ids):
+            feat = Feature(int(fid))
+            for s, cid in enumerate(self.cam_ids):
+                if (int(mask[i, s >> 6]) >> (s & 63)) & 1:
+                    feat.observations[cid] = tuple(float(v) for v in z[i, s])
+            feat.position = p_w[i].copy()
+            feat.is_initialized = bool(init[i])
+            out[feat.id] = feat
+        return out
+
     # ------------------------------------------------- device request server --
     def _serve(self, req):
         """Executes one request of the step generators on this filter's slot."""
@@ -154,6 +210,23 @@ class MSCKF:
             return ctx.cov_diag(f, req[1], req[2])
         if kind == "set_state":
             return ctx.set_state(f, req[1], req[2], req[3])
+        if kind == "map_add_lost":
+            return ctx.map_add_lost([f], [0, len(req[1])], req[1], req[2])[0]
+        if kind == "map_prune_select":
+            return ctx.map_prune_select([f], [0, len(req[1])], req[1])[0]
+        if kind == "map_triangulate":
+            ctx.map_load(_lib.MAP_LOAD_PRUNE_TRI, [f], [0, len(req[1])], req[1], req[2])
+            ctx.batch_triangulate()
+            _, _, p, v, _ = ctx.batch_results()
+            return p, v
+        if kind == "map_update":   # (kind, form, rows, counts, p_w, triangulate, row cap)
+            ctx.map_load(req[1], [f], [0, len(req[2])], req[2], req[3], req[4])
+            ctx.batch_update(row_cap=req[6], triangulate=req[5])
+            return ctx.pending([(f, 0, len(req[2]))])[0]
+        if kind == "map_prune_commit":
+            return ctx.map_prune_commit([f], [0, len(req[1])], req[1], req[2], req[3])
+        if kind == "map_clear":
+            return ctx.map_clear([f])
         raise ValueError("unknown request %r" % (kind,))
 
     def _settle(self):
@@ -213,9 +286,13 @@ class MSCKF:
             self.imu_timestamp = feature_msg.timestamp
         yield from self._batch_imu_processing(feature_msg.timestamp)
         yield from self._state_augmentation()
-        self._add_feature_observations(feature_msg)
-        yield from self._remove_lost_features()
-        yield from self._prune_cam_state_buffer()
+        if self.device_map:
+            yield from self._map_add_and_remove_lost(feature_msg)
+            yield from self._map_prune_cam_state_buffer()
+        else:
+            self._add_feature_observations(feature_msg)
+            yield from self._remove_lost_features()
+            yield from self._prune_cam_state_buffer()
         # publish and online_reset's position variances in one read
         thr = self.config.position_std_threshold
         st = yield (("states", 12, 3) if thr > 0 else ("states",))
@@ -262,6 +339,17 @@ class MSCKF:
         get = ms.get
         cur = len(ms)
         tracked = 0
+        if isinstance(feature_msg, FeatureArrays):   # an array message, walked row by row
+            for fid, z in zip(feature_msg.ids.tolist(), np.asarray(feature_msg.uv, float).tolist()):
+                feat = get(fid)
+                if feat is None:
+                    feat = Feature(fid)
+                    ms[fid] = feat
+                else:
+                    tracked += 1
+                feat.observations[sid] = tuple(z)
+            self.tracking_rate = tracked / (cur + 1e-5)
+            return
         for f in feature_msg.vio_features:
             z = (float(f.u0), float(f.v0), float(f.u1), float(f.v1))   # packed into arrays once per request (_pack)
             feat = get(f.id)
@@ -443,6 +531,75 @@ class MSCKF:
         for c in rm:
             self.cam_ids.remove(c)
 
+    # ------------------------------------------------- the map on the device --
+    def _log_update(self, pend, ids, counts, dofs, row_cap):
+        """Defers the decision log of an update loaded from the device map:
+        what ``_update.apply`` does, from the descriptors (arrays, no loop per
+        feature)."""
+        dofs = np.asarray(dofs, np.int64)
+        chi2 = _chi2_of(dofs)
+        k = 4 * np.asarray(counts, np.int64) - 3
+        ids = np.asarray(ids, np.int64)
+        frame, D = self._n_published, 21 + 6 * len(self.cam_ids)
+
+        def apply(acc, gam, p, valid, rows):
+            v = np.flatnonzero(valid)     # a failed triangulation never reaches measurement_update
+            ok = gam[v] < chi2[v]
+            if row_cap:                   # features after the row-cap break are never gated
+                over = np.flatnonzero(np.cumsum(np.where(ok, k[v], 0)) > row_cap)
+                if len(over):
+                    v, ok = v[:over[0] + 1], ok[:over[0] + 1]
+            self.gate_log.extend(zip([frame] * len(v), dofs[v].tolist(), k[v].tolist(), ok.astype(int).tolist()))
+            self.gamma_log.extend(zip(ids[v].tolist(), np.asarray(gam, float)[v].tolist()))
+            if np.any(valid):
+                self.shape_log.append((frame, rows, D))
+        self._deferred.append((pend, apply))
+
+    def _map_add_and_remove_lost(self, feature_msg):
+        """msckf.py:409-427 and 616-689 on the device table."""
+        ids, uv = message_arrays(feature_msg)
+        tracked, cur, cand_ids, info = yield ("map_add_lost", ids, uv)
+        self.tracking_rate = tracked / (cur + 1e-5)
+        if not len(cand_ids):
+            return
+        M = info[:, 0]
+        _chi2_of(M - 1)   # KeyError for a dof outside the table, as the host path
+        pend = yield ("map_update", _lib.MAP_LOAD_LOST, info[:, 3], M, None, not bool(info[:, 2].all()),
+                      self.ROW_CAP)
+        self._log_update(pend, cand_ids, M, M - 1, self.ROW_CAP)
+
+    def _map_prune_cam_state_buffer(self):
+        """msckf.py:730-818 on the device table."""
+        if len(self.cam_ids) < self.config.max_cam_state_size:
+            return
+        _, cams_arr = yield ("states",)
+        self._settle()
+        rm = self._find_redundant_cam_states(cams_arr)
+        slots = np.array([self.cam_ids.index(c) for c in rm], np.int32)
+        inv_ids, info = yield ("map_prune_select", slots)
+        init = info[:, 2].astype(bool)
+        tri = np.flatnonzero(~init)
+        pw = np.full((len(inv_ids), 3), np.nan)
+        ok = init.copy()
+        if len(tri):
+            p, v = yield ("map_triangulate", info[tri, 3], info[tri, 0])
+            pw[tri] = p
+            ok[tri] = v
+        upd = np.flatnonzero(ok)
+        if len(upd):
+            k = info[upd, 1]
+            _chi2_of(k)
+            pw_u = pw[upd]
+            pw_u[~np.isfinite(pw_u).all(axis=1)] = np.nan
+            pend = yield ("map_update", _lib.MAP_LOAD_PRUNE_UPDATE, info[upd, 3], k, pw_u, False, 0)
+            self._log_update(pend, inv_ids[upd], k, k, 0)
+        else:   # the reference still calls measurement_update with an empty H
+            self.shape_log.append((self._n_published, 0, 21 + 6 * len(self.cam_ids)))
+        yield ("map_prune_commit", info[tri, 3], ok[tri], pw[tri])
+        yield ("prune", slots)
+        for c in rm:
+            self.cam_ids.remove(c)
+
     # ------------------------------------------------------ output / reset --
     def publish(self, time):
         """msckf.py:888-908"""
@@ -466,7 +623,10 @@ class MSCKF:
         if np.max(np.sqrt(d)) < thr:
             return
         self.cam_ids.clear()
-        self.map_server.clear()
+        if self.device_map:
+            yield ("map_clear",)
+        else:
+            self.map_server.clear()
         self.reset_log.append(self._n_published - 1)   # the frame just published
         imu, _ = yield ("states",)
         yield ("set_state", imu, None, self._initial_cov())
@@ -474,3 +634,22 @@ class MSCKF:
     def close(self):
         if self._own_ctx:
             self.ctx.close()
+
+
+_DEVICE_MAP_CLASSES = {}
+
+
+def _device_map_class(cls):
+    """The class a ``cls(device_map=True)`` instance becomes: ``cls`` itself --
+    MSCKF or a user's subclass, whose overrides stay -- plus ``map_server`` as a
+    read-only snapshot of the device table.  (A subclass rather than a
+    ``__getattr__`` on MSCKF, which would slow every attribute read of the
+    host-map instances too.)"""
+    sub = _DEVICE_MAP_CLASSES.get(cls)
+    if sub is None:
+        sub = type(cls.__name__ + "DeviceMap", (cls,), {
+            "map_server": property(lambda self: self._map_snapshot(),
+                                   doc="read-only snapshot of the device table (msckf_map_get)"),
+            "__module__": cls.__module__})
+        _DEVICE_MAP_CLASSES[cls] = sub
+    return sub

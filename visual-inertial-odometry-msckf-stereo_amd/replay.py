@@ -78,10 +78,19 @@ class FeatureStream:
                  for i in range(a, b)]
         return FeatureMsg(float(self.frame_t[k]), feats)
 
-    def messages(self):
+    def frame_arrays(self, k):
+        """Frame k as an array message (msckf.FeatureArrays): slices of
+        feat_id / feat_z, no tuples."""
+        from .msckf import FeatureArrays
+        a, b = int(self.frame_off[k]), int(self.frame_off[k + 1])
+        return FeatureArrays(float(self.frame_t[k]), self.feat_id[a:b], self.feat_z[a:b])
+
+    def messages(self, arrays=False):
         """(IMU messages, frame messages) of the whole stream: the front-end's
-        output, built once (a timed replay leaves their construction out)."""
-        return self.imu_msgs(), [self.frame_msg(k) for k in range(self.n_frames)]
+        output, built once (a timed replay leaves their construction out).
+        ``arrays``: the frames as array messages."""
+        frame = self.frame_arrays if arrays else self.frame_msg
+        return self.imu_msgs(), [frame(k) for k in range(self.n_frames)]
 
     def events(self):
         """(kind, msg) in strict time order, IMU first on ties; kind 0 = IMU,

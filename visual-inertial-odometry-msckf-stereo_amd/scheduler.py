@@ -36,15 +36,19 @@ from .msckf import MSCKF
 from .trajectory import Trajectory
 
 # pipeline order: a lane waiting at an earlier stage is served first
-_ORDER = {"set_state": 0, "propagate": 1, "augment": 2, "triangulate": 3, "update": 4, "states": 5,
-          "prune": 6, "cov_diag": 7}
+_ORDER = {"set_state": 0, "propagate": 1, "augment": 2, "map_add_lost": 2.5, "triangulate": 3,
+          "map_triangulate": 3, "update": 4, "map_update": 4, "states": 5, "map_prune_select": 5.3,
+          "map_prune_commit": 5.6, "prune": 6, "cov_diag": 7, "map_clear": 8}
 
 
 class MultiMSCKF:
     """``n`` filters (one per sequence) on one device context."""
 
-    def __init__(self, n, config=None, dtype=np.float64, device=0, cam_capacity=None, lane_configs=None):
-        """``lane_configs`` (optional, one per lane): per-sequence host-side
+    def __init__(self, n, config=None, dtype=np.float64, device=0, cam_capacity=None, lane_configs=None,
+                 device_map=False, map_capacity=1024):
+        """``device_map`` / ``map_capacity``: every lane keeps its feature map
+        in the context's tables (msckf_map.h), as ``MSCKF(device_map=True)``.
+        ``lane_configs`` (optional, one per lane): per-sequence host-side
         settings (check_motion's translation threshold, online_reset's
         position std threshold, window size).  The device context is shared,
         so every lane must agree on what the device computes with (noise,
@@ -63,7 +67,14 @@ class MultiMSCKF:
         cap = cam_capacity or max(c.max_cam_state_size for c in cfgs) + 2
         self.config = cfgs[0]
         self.ctx = _lib.Context(cfgs[0], n_filters=n, n_cam_capacity=cap, dtype=dtype, device=device)
-        self.lanes = [MSCKF(cfgs[i], ctx=self.ctx, slot=i) for i in range(n)]
+        self.device_map = bool(device_map)
+        if self.device_map:
+            for i, c in enumerate(cfgs):   # before the tables are made: MSCKF's own rule, per lane
+                if c.optimization.translation_threshold >= 0:
+                    self.ctx.close()
+                    raise ValueError("lane %d: device_map=True needs optimization.translation_threshold < 0" % i)
+            self.ctx.map_create(map_capacity)
+        self.lanes = [MSCKF(cfgs[i], ctx=self.ctx, slot=i, device_map=self.device_map) for i in range(n)]
         self.launches = defaultdict(int)       # batched device calls per request kind
 
     def __len__(self):
@@ -87,7 +98,7 @@ class MultiMSCKF:
         while pending:
             kind = min((r[0] for r in pending.values()), key=lambda k: _ORDER[k])
             group = [i for i, r in pending.items() if r[0] == kind]
-            if kind == "update":          # the row cap is per call: lost path 1500, prune path none
+            if kind in ("update", "map_update"):   # the row cap is per call: lost path 1500, prune path none
                 cap = min(pending[i][6] for i in group)
                 group = [i for i in group if pending[i][6] == cap]
             elif kind in ("cov_diag", "states"):
@@ -146,6 +157,36 @@ class MultiMSCKF:
             for s, r in zip(slots, reqs):
                 ctx.set_state(s, r[1], r[2], r[3])
             return [None] * len(group)
+        cat = lambda xs, dt: np.concatenate([np.asarray(x, dt) for x in xs])  # noqa: E731
+        offs = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int32)  # noqa: E731
+        if kind == "map_add_lost":
+            return ctx.map_add_lost(slots, offs([r[1] for r in reqs]), cat([r[1] for r in reqs], np.int64),
+                                    np.concatenate([np.asarray(r[2], float).reshape(-1, 4) for r in reqs]))
+        if kind == "map_prune_select":
+            return ctx.map_prune_select(slots, offs([r[1] for r in reqs]), cat([r[1] for r in reqs], np.int32))
+        if kind == "map_triangulate":
+            self._ranges = ctx.map_load(_lib.MAP_LOAD_PRUNE_TRI, slots, offs([r[1] for r in reqs]),
+                                        cat([r[1] for r in reqs], np.int32), cat([r[2] for r in reqs], np.int32))
+            ctx.batch_triangulate()
+            _, _, p, v, _ = ctx.batch_results()
+            return self._split(slots, reqs, lambda a, b, _s: (p[a:b].copy(), v[a:b].copy()))
+        if kind == "map_update":   # one form per call (the row cap decides it); deferred like "update"
+            form = reqs[0][1]
+            pw = None
+            if form == _lib.MAP_LOAD_PRUNE_UPDATE:
+                pw = np.concatenate([np.asarray(r[4], float).reshape(-1, 3) for r in reqs])
+            self._ranges = ctx.map_load(form, slots, offs([r[2] for r in reqs]), cat([r[2] for r in reqs], np.int32),
+                                        cat([r[3] for r in reqs], np.int32), pw)
+            ctx.batch_update(row_cap=reqs[0][6], triangulate=any(r[5] for r in reqs))
+            return ctx.pending([(s,) + self._ranges[s] for s in slots])
+        if kind == "map_prune_commit":
+            ctx.map_prune_commit(slots, offs([r[1] for r in reqs]), cat([r[1] for r in reqs], np.int32),
+                                 cat([r[2] for r in reqs], np.uint8),
+                                 np.concatenate([np.asarray(r[3], float).reshape(-1, 3) for r in reqs]))
+            return [None] * len(group)
+        if kind == "map_clear":
+            ctx.map_clear(slots)
+            return [None] * len(group)
         raise ValueError("unknown request %r" % (kind,))
 
     def _load(self, slots, reqs, with_pw):
@@ -183,13 +224,14 @@ class MultiMSCKF:
         return out
 
     # -------------------------------------------------------------- streams --
-    def run_streams(self, streams, on_frame=None, messages=None):
+    def run_streams(self, streams, on_frame=None, messages=None, arrays=False):
         """Replays ``streams`` (replay.FeatureStream, one per lane) in lock
         step -- frame k of every stream in one batched round, each lane fed
         its own IMU samples up to its frame stamp first (IMU first on ties,
         as replay.FeatureStream.events) -- and returns one Trajectory per lane.
         ``messages``: the streams' ``messages()`` built by the caller
-        beforehand (the front-end's output; a timed run leaves them out)."""
+        beforehand (the front-end's output; a timed run leaves them out).
+        ``arrays``: feed the frames as array messages (FeatureStream.frame_arrays)."""
         if len(streams) > len(self.lanes):
             raise ValueError("%d streams for %d filter slots" % (len(streams), len(self.lanes)))
         if messages is not None and len(messages) != len(streams):
@@ -207,7 +249,7 @@ class MultiMSCKF:
                 if messages is None:
                     for r in st.imu[imu_pos[i]:j]:
                         self.imu_callback(i, _imu_msg(r))
-                    msgs[i] = st.frame_msg(k)
+                    msgs[i] = st.frame_arrays(k) if arrays else st.frame_msg(k)
                 else:
                     for m in messages[i][0][imu_pos[i]:j]:
                         self.imu_callback(i, m)
