@@ -56,12 +56,16 @@ def predict(Hpred, cam0):
         return np.stack([(q[0] / q[2]).astype(np.float32), (q[1] / q[2]).astype(np.float32)], axis=1).reshape(-1, 2)
 
 
-def step(ops, tables, lanes, grid, W, H, threshold, max_kp=1 << 16, inlier_error=0.0, n_hyp=0, **lk):
+def step(ops, tables, lanes, grid, W, H, threshold, max_kp=1 << 16, inlier_error=0.0, n_hyp=0, trace=None, **lk):
     """One mfe_tracks_step.  ``tables``: {lane: Table} (not modified);
     ``lanes``: msckf_amd.frontend.TracksLane per named lane.  Returns
     (results, next tables {lane: Table}, cover Counter); results as
-    Frontend.tracks_step returns them."""
+    Frontend.tracks_step returns them.  ``trace``: a dict that receives, per
+    place i in ``lanes``, ("keep", i): the keep flags of the three compactions
+    (after steps 2, 3 and 4) over the list each one reads, and ("cell", i): the
+    largest number of rows a cell holds before its prune."""
     S, cells, cover = len(lanes), grid.rows * grid.cols, Counter()
+    trace = {} if trace is None else trace
     tabs = [tables[a.lane] for a in lanes]
     ctr = np.zeros((S, 4), np.int32)
     # steps 1-2
@@ -75,6 +79,7 @@ def step(ops, tables, lanes, grid, W, H, threshold, max_kp=1 << 16, inlier_error
         cover["bounds"] += int((st & outside).sum())
         cover["empty_table"] += int(len(t.ids) == 0)
         rows.append(np.nonzero(st & ~outside)[0])
+        trace["keep", i] = [st & ~outside]
         c0.append(q)
         ctr[i, 0], ctr[i, 1] = len(t.ids), len(rows[i])
     # step 3
@@ -88,6 +93,7 @@ def step(ops, tables, lanes, grid, W, H, threshold, max_kp=1 << 16, inlier_error
         c1.append(full)
         inl = np.asarray(inl).astype(bool)
         cover["stereo"] += int((~inl).sum())
+        trace["keep", i].append(inl)
         rows[i] = rows[i][inl]
         ctr[i, 2] = len(rows[i])
     # step 4
@@ -104,6 +110,10 @@ def step(ops, tables, lanes, grid, W, H, threshold, max_kp=1 << 16, inlier_error
             keep = np.logical_and(got[2 * j][0], got[2 * j + 1][0])
             cover["ransac"] += int((~keep).sum())
             rows[i] = rows[i][keep]
+            trace["keep", i].append(keep)
+    for i in range(S):
+        if len(trace["keep", i]) < 3:                                # no RANSAC: the third compaction keeps every row
+            trace["keep", i].append(np.ones(len(rows[i]), bool))
     ctr[:, 3] = [len(r) for r in rows]
     # step 6
     got = ops.fast_grid_sets([(a.slot_c0, c0[i][rows[i]]) for i, a in enumerate(lanes)], threshold, grid.rows,
@@ -132,6 +142,7 @@ def step(ops, tables, lanes, grid, W, H, threshold, max_kp=1 << 16, inlier_error
             for q in new:
                 feats.append((next_id, 1, xy[q], m1[q]))
                 next_id += 1
+            trace["cell", i] = max(trace.get(("cell", i), 0), len(feats))
             if len(feats) > grid.gmax:                               # step 8
                 lives = [f[1] for f in feats]
                 cover["pruned_tie"] += int(len(set(lives)) < len(lives))

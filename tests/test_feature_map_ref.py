@@ -23,6 +23,7 @@ from msckf_amd.msckf import MSCKF, FeatureArrays
 from msckf_amd.replay import FeatureStream, replay
 from conftest import golden
 import feature_map_ref as fr
+import feature_map_cases as fc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -36,7 +37,9 @@ def streams():
     g = golden("sequence_s1")
     return [FeatureStream.from_synthetic(synth.make_sequence(int(g["n_frames"]), int(g["seed"]))),
             FeatureStream.from_synthetic(synth.make_sequence(90, 7)),
-            late_start(FeatureStream.from_synthetic(synth.make_sequence(140, 11)), 7)]
+            late_start(FeatureStream.from_synthetic(synth.make_sequence(140, 11)), 7),
+            # 400 features per frame: the map passes 256 rows (tests/test_gpu_feature_map.py's big_stream)
+            FeatureStream.from_synthetic(synth.make_sequence(30, 3, max_features=400, n_landmarks=2000))]
 
 
 STREAMS = None
@@ -80,13 +83,25 @@ def assert_same_sent(a, b):
             np.testing.assert_array_equal(x, y, err_msg="request %d (%s)" % (k, ra[0]))
 
 
-@pytest.mark.parametrize("which", [0, 1, 2])
+@pytest.mark.parametrize("which", [0, 1, 2, 3])
 def test_device_map_sends_what_the_host_map_sends(monkeypatch, which):
     st = get_streams()[which]
     fr.COUNTERS.clear()
     host = run(monkeypatch, st)
     assert not fr.COUNTERS
+    sizes, add_lost = [], fr.RecordingContext.map_add_lost
+
+    def sized(self, filters, msg_off, ids, z):
+        out = add_lost(self, filters, msg_off, ids, z)
+        sizes.extend(len(self.tab[f]["ids"]) for f in filters)
+        return out
+    monkeypatch.setattr(fr.RecordingContext, "map_add_lost", sized)
     dev = run(monkeypatch, st, device_map=True)
+    assert len(sizes) > 10
+    if which == 3:            # the stream whose map no single 256-row pass of a map kernel covers
+        assert max(sizes) > 256 and np.diff(st.frame_off).min() > 256, max(sizes)
+    else:
+        assert max(sizes) <= 256
     assert any(r[0] == "tri" for r in host.ctx.sent) and any(r[0] == "upd" for r in host.ctx.sent)
     assert_same_sent(host.ctx.sent, dev.ctx.sent)
     assert host.gate_log == dev.gate_log and len(host.gate_log) > 100
@@ -98,6 +113,32 @@ def test_device_map_sends_what_the_host_map_sends(monkeypatch, which):
         assert fr.COUNTERS[b] > 0, (b, dict(fr.COUNTERS))
     # the row-cap break and a failed fused triangulation occur in the lost updates
     assert any(r[0] == "upd" and r[6] == MSCKF.ROW_CAP and r[4].any() for r in dev.ctx.sent)
+
+
+@pytest.mark.parametrize("cap,n", fc.BIG)
+def test_the_big_map_cases_span_several_chunks(cap, n):
+    """A condition on the inputs of tests/test_gpu_feature_map.py's cases above 256
+    rows, from the reference's own outputs: see feature_map_cases."""
+    tabs, msgs, ncams = fc.add_lost_tables(n, cap)
+    name, ids, z = msgs[0][0]
+    assert name == "mixed" and {m[0] for m in msgs[0]} >= {"mixed", "tracked"} and len(tabs[0]["ids"]) == n
+    c = fc.assert_add_lost_spans_chunks(tabs[0], ids, z, ncams[0] - 1, cap)
+    assert len(c["table"]) == -(-(n + sum(m[0] for m in c["message"])) // 256)
+    for name, ids, z in msgs[0][1:]:
+        assert len(ids) > 256
+    assert (len(tabs[2]["ids"]) < 64) == (n in (513, 1023, 2047))
+    for nent, nent_hi in fc.prune_conditions(n):
+        if n >= 1023:             # prune_commit's entry loop runs more than once
+            assert nent > 256 and nent_hi > 0, (n, nent, nent_hi)
+
+
+def test_the_overflow_case_spans_several_chunks():
+    t, ids, z = fc.overflow_case(1024)
+    with pytest.raises(fr.MapError) as e:
+        fr.add_lost(t, ids, z, 5, 1024)
+    assert e.value.rc == -3 and "1025 rows" in str(e.value)
+    c = fc.add_lost_chunks(t, ids[:-1], z[:-1], 5, 1024)
+    assert len(c["message"]) == 3 and all(m[0] > 0 for m in c["message"]) and len(c["table"]) == 4
 
 
 def test_array_messages_equal_tuple_messages(monkeypatch):

@@ -1,7 +1,9 @@
 """The feature map kept on the device (include/msckf_map.h) on the GPU.  Every
 comparison is exact:
   * each call against the numpy reference tests/feature_map_ref.py, tables
-    written by msckf_map_put and read by msckf_map_get;
+    written by msckf_map_put and read by msckf_map_get -- within one 256-row
+    pass of the kernels (cap 256) and beyond it (cap 1024 and 2048, tables up
+    to 2048 rows, messages up to 800; the inputs are tests/feature_map_cases.py);
   * msckf_map_load + the unchanged update chain against msckf_batch_load of the
     reference's arrays + the same chain on a second context, all three forms;
   * MSCKF(device_map=True) / MultiMSCKF(.., device_map=True) against the host
@@ -19,6 +21,8 @@ from msckf_amd._lib import Context, pack_cams, pack_imu
 from msckf_amd.replay import FeatureStream, replay
 from msckf_amd.scheduler import MultiMSCKF
 import feature_map_ref as fr
+import feature_map_cases as fc
+from feature_map_cases import messages, random_table, weird_ids
 
 pytestmark = pytest.mark.gpu
 
@@ -42,35 +46,6 @@ def make_ctx(problems, Nmax, dtype=np.float64, cap=CAP, with_map=True):
     return ctx
 
 
-def weird_ids(rng, n):
-    """Distinct ids: non-monotone, negative, above 2**32."""
-    pool = np.concatenate([rng.choice(np.arange(-5000, 5000), n, replace=False),
-                           (1 << 32) + rng.choice(np.arange(1, 100000), n, replace=False) * 7,
-                           -(1 << 40) - np.arange(n)]).astype(np.int64)
-    return rng.permutation(pool)[:n]
-
-
-def random_table(rng, n, Nmax, ncams, newest_free=True):
-    """n rows over ``ncams`` cam slots: track lengths 0 (empty mask), 1, 2, 3 and
-    the whole window occur; ``newest_free``: no observation at the newest slot."""
-    t = fr.empty(Nmax)
-    hi = ncams - 1 if newest_free else ncams
-    obs = np.zeros((n, Nmax), bool)
-    for i in range(n):
-        M = [0, 1, 2, 3, hi][i % 5] if i < 10 else int(rng.integers(0, hi + 1))
-        M = min(M, hi)
-        a = int(rng.integers(0, hi - M + 1))
-        obs[i, a:a + M] = True
-        if i % 7 == 3 and M >= 2:          # a gap: observations need not be contiguous
-            obs[i, a + 1] = False
-    t["ids"] = weird_ids(rng, n)
-    t["obs"] = obs
-    t["z"] = rng.standard_normal((n, Nmax, 4))
-    t["p_w"] = rng.standard_normal((n, 3))
-    t["init"] = rng.random(n) < 0.5
-    return t
-
-
 def put(ctx, f, t):
     ctx.map_put(f, t["ids"], fr.mask_words(t["obs"]), t["z"], t["p_w"], t["init"])
 
@@ -84,21 +59,6 @@ def assert_table(ctx, f, t, msg=""):
     np.testing.assert_array_equal(init, t["init"], err_msg=msg)
 
 
-def messages(rng, t, cap):
-    """(name, ids, z): empty, all new, all tracked, mixed -- as far as cap allows."""
-    n = len(t["ids"])
-    fresh = (1 << 50) + rng.permutation(400)[:min(40, cap - n)].astype(np.int64)
-    some = rng.permutation(t["ids"])[:min(n, 90)]
-    out = [("empty", np.zeros(0, np.int64))]
-    if len(fresh):
-        out.append(("new", fresh))
-    if len(some):
-        out.append(("tracked", some))
-    if len(some) and len(fresh):
-        out.append(("mixed", rng.permutation(np.concatenate([some[::2], fresh[::2]]))))
-    return [(name, ids, rng.standard_normal((len(ids), 4))) for name, ids in out]
-
-
 def small_problem(N, seed, F=4):
     return synth.make_update_problem(N, F, seed=seed)
 
@@ -108,14 +68,11 @@ def rc_of(err):
 
 
 # ----------------------------------------------- per call vs the reference --
-@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 255, 256])
-def test_add_lost_vs_reference(n):
-    rng = np.random.default_rng(100 + n)
-    ncams = [6, None, 8]
-    ctx = make_ctx([small_problem(6, 1), None, small_problem(8, 2)], Nmax=8)
+def check_add_lost(cap, tabs, msgs, ncams):
+    """Every message pair through one launch naming filters 2 and 0, twice from the
+    same put state, against the reference; the idle slot 1 stays empty."""
+    ctx = make_ctx([small_problem(6, 1), None, small_problem(8, 2)], Nmax=8, cap=cap)
     try:
-        tabs = {f: random_table(rng, n if f == 0 else max(n - 3, 0), 8, ncams[f]) for f in (0, 2)}
-        msgs = {f: messages(rng, tabs[f], CAP) for f in (0, 2)}
         for k in range(max(len(m) for m in msgs.values())):
             first = None
             for rep in range(2):                       # a repeat from the same put state: the same bits
@@ -127,7 +84,7 @@ def test_add_lost_vs_reference(n):
                                        np.concatenate([mk[2][2], mk[0][2]]))
                 state = [ctx.map_get(f) for f in (0, 2)]
                 for w, f in enumerate((2, 0)):
-                    nxt, tracked, nb, cid, info = fr.add_lost(tabs[f], mk[f][1], mk[f][2], ncams[f] - 1, CAP)
+                    nxt, tracked, nb, cid, info = fr.add_lost(tabs[f], mk[f][1], mk[f][2], ncams[f] - 1, cap)
                     assert got[w][0] == tracked and got[w][1] == nb, (f, mk[f][0])
                     np.testing.assert_array_equal(got[w][2], cid)
                     np.testing.assert_array_equal(got[w][3], info)
@@ -146,14 +103,35 @@ def test_add_lost_vs_reference(n):
         ctx.close()
 
 
-@pytest.mark.parametrize("ncams", [4, 6, 8])
 @pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 255, 256])
-def test_prune_select_commit_vs_reference(ncams, n):
-    rng = np.random.default_rng(7 * ncams + n)
-    ctx = make_ctx([small_problem(ncams, 3), None, small_problem(ncams, 4)], Nmax=8)
+def test_add_lost_vs_reference(n):
+    rng = np.random.default_rng(100 + n)
+    ncams = [6, None, 8]
+    tabs = {f: random_table(rng, n if f == 0 else max(n - 3, 0), 8, ncams[f]) for f in (0, 2)}
+    msgs = {f: messages(rng, tabs[f], CAP) for f in (0, 2)}
+    check_add_lost(CAP, tabs, msgs, ncams)
+
+
+@pytest.mark.parametrize("cap,n", fc.BIG)
+def test_add_lost_beyond_one_chunk(cap, n):
+    """Tables and messages above 256 rows: the table loop of k_map_add_lost runs up
+    to 8 times and the message loop up to 4 times, nnew, nkeep and ncand carried
+    (tests/test_feature_map_ref.py asserts that of these inputs).  At n = 513, 1023
+    and 2047 the launch's other filter has 40 rows and a one-chunk message."""
+    tabs, msgs, ncams = fc.add_lost_tables(n, cap)
+    name, ids, z = msgs[0][0]
+    assert name == "mixed"
+    fc.assert_add_lost_spans_chunks(tabs[0], ids, z, ncams[0] - 1, cap)
+    check_add_lost(cap, tabs, msgs, ncams)
+
+
+def check_prune(cap, ncams, tables, rng):
+    """prune_select and prune_commit of filters 0 and 2 in one launch each, at the
+    three slot choices, against the reference.  ``tables()`` -> {filter: table}."""
+    ctx = make_ctx([small_problem(ncams, 3), None, small_problem(ncams, 4)], Nmax=8, cap=cap)
     try:
-        for slots in ([0, 1], [0, ncams // 2], [ncams - 3, ncams - 2]):
-            tabs = {f: random_table(rng, n, 8, ncams, newest_free=False) for f in (0, 2)}
+        for slots in fc.prune_slots(ncams):
+            tabs = tables()
             for f in (0, 2):
                 put(ctx, f, tabs[f])
             rm = fr.removed_mask(slots, 8)
@@ -164,8 +142,7 @@ def test_prune_select_commit_vs_reference(ncams, n):
                 np.testing.assert_array_equal(got[w][0], iid)
                 np.testing.assert_array_equal(got[w][1], info)
                 assert_table(ctx, f, tabs[f], "select %d %s" % (f, slots))
-                rows = info[~info[:, 2].astype(bool), 3]
-                ents.append((rows, rng.random(len(rows)) < 0.6, rng.standard_normal((len(rows), 3))))
+                ents.append(fc.prune_entries(rng, info))
             ctx.map_prune_commit([2, 0], [0, len(ents[1][0]), len(ents[1][0]) + len(ents[0][0])],
                                  np.concatenate([ents[1][0], ents[0][0]]), np.concatenate([ents[1][1], ents[0][1]]),
                                  np.concatenate([ents[1][2], ents[0][2]]))
@@ -175,6 +152,23 @@ def test_prune_select_commit_vs_reference(ncams, n):
                 assert_table(ctx, f, tabs[f], "commit %d %s" % (f, slots))
     finally:
         ctx.close()
+
+
+@pytest.mark.parametrize("ncams", [4, 6, 8])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 65, 255, 256])
+def test_prune_select_commit_vs_reference(ncams, n):
+    rng = np.random.default_rng(7 * ncams + n)
+    check_prune(CAP, ncams, lambda: {f: random_table(rng, n, 8, ncams, newest_free=False) for f in (0, 2)}, rng)
+
+
+@pytest.mark.parametrize("cap,n", fc.BIG)
+def test_prune_select_commit_beyond_one_chunk(cap, n):
+    """Tables above 256 rows: k_map_prune_select's loop runs up to 8 times with ninv
+    carried, k_map_prune_commit's entry loop more than once from n = 1023 on (more
+    than 256 entries, rows >= 256 among them; tests/test_feature_map_ref.py asserts
+    that of these inputs)."""
+    rng = fc.prune_rng(n)
+    check_prune(cap, 8, lambda: fc.prune_tables(n, rng), rng)
 
 
 # ------------------------------------------------------- load equals load --
@@ -195,6 +189,22 @@ def problem_table(pr, Nmax, rng, drop_newest):
     t["init"] = np.arange(F) % 2 == 0
     t["p_w"] = np.where(t["init"][:, None], pr.landmarks + 1e-3 * rng.standard_normal((F, 3)), 0.0)
     return t
+
+
+def padded(t, rng, total, pad_obs):
+    """t's rows, in their order, at random rows 256.. of a ``total``-row table on
+    both sides of row 512; the other rows observe the slots ``pad_obs[i % len]``
+    (rows no load names).  Returns the table and the rows of t in it."""
+    F, Nmax = t["obs"].shape
+    pos = np.sort(rng.choice(np.arange(256, total), F, replace=False))
+    assert pos[0] < 512 <= pos[-1]
+    T = dict(ids=weird_ids(rng, total), obs=np.zeros((total, Nmax), bool), z=rng.standard_normal((total, Nmax, 4)),
+             p_w=rng.standard_normal((total, 3)), init=rng.random(total) < 0.5)
+    for i in range(total):
+        T["obs"][i, np.array(pad_obs[i % len(pad_obs)], int)] = True
+    for k in ("obs", "z", "p_w", "init"):
+        T[k][pos] = t[k]
+    return T, pos
 
 
 def batch_from(per_slot, B, with_pw):
@@ -228,24 +238,30 @@ def assert_same_results(ra, rb):
         np.testing.assert_array_equal(x, y)
 
 
-@pytest.mark.parametrize("row_cap", [1500, 60])
-@pytest.mark.parametrize("dtype", [np.float64, np.float32])
-def test_lost_load_equals_batch_load(dtype, row_cap):
+def check_lost_load(dtype, row_cap, cap=CAP, pad=0):
+    """``pad``: the problems' rows among that many rows of a larger table, from row
+    256 on, the others too short to be candidates or observed at the newest slot."""
     rng = np.random.default_rng(5)
     prs = [synth.make_update_problem(8, 30, seed=11), None, synth.make_update_problem(6, 24, seed=12)]
-    dev, ref = make_ctx(prs, 10, dtype), make_ctx(prs, 10, dtype, with_map=False)
+    dev, ref = make_ctx(prs, 10, dtype, cap=cap), make_ctx(prs, 10, dtype, with_map=False)
     try:
         loads, rows, counts, off = {}, [], [], [0]
         tabs = {f: problem_table(prs[f], 10, rng, drop_newest=True) for f in (0, 2)}
+        if pad:
+            for f in (0, 2):
+                s = prs[f].N - 1
+                tabs[f], pos = padded(tabs[f], rng, pad, [[], [s], [0, s], [1], [2, 3], list(range(s + 1)), [s - 1]])
         for f in (0, 2):
             put(dev, f, tabs[f])
         msg = {f: (rng.permutation(tabs[f]["ids"])[:5], rng.standard_normal((5, 4))) for f in (0, 2)}
         got = dev.map_add_lost([0, 2], [0, 5, 10], np.concatenate([msg[0][0], msg[2][0]]),
                                np.concatenate([msg[0][1], msg[2][1]]))
         for w, f in enumerate((0, 2)):
-            _, _, _, cid, info = fr.add_lost(tabs[f], msg[f][0], msg[f][1], prs[f].N - 1, CAP)
+            _, _, _, cid, info = fr.add_lost(tabs[f], msg[f][0], msg[f][1], prs[f].N - 1, cap)
             np.testing.assert_array_equal(got[w][3], info)
             assert len(cid) >= 10 and (~info[:, 2].astype(bool)).any() and info[:, 2].any()
+            if pad:                            # every loaded row beyond the first chunk, in two chunks or more
+                assert info[:, 3].min() >= 256 and info[:, 3].max() >= 512 and len(cid) <= prs[f].F
             loads[f] = fr.load(tabs[f], _lib.MAP_LOAD_LOST, info[:, 3], info[:, 0])
             rows.append(info[:, 3])
             counts.append(info[:, 0])
@@ -268,13 +284,29 @@ def test_lost_load_equals_batch_load(dtype, row_cap):
         ref.close()
 
 
+@pytest.mark.parametrize("row_cap", [1500, 60])
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
-def test_prune_loads_equal_batch_load(dtype):
+def test_lost_load_equals_batch_load(dtype, row_cap):
+    check_lost_load(dtype, row_cap)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_lost_load_from_rows_beyond_256(dtype):
+    check_lost_load(dtype, 1500, cap=1024, pad=700)
+
+
+def check_prune_loads(dtype, cap=CAP, pad=0):
+    """``pad``: as in check_lost_load, the other rows observing at most one of the
+    removed slots."""
     rng = np.random.default_rng(6)
     prs = [synth.make_update_problem(8, 30, seed=21), None, synth.make_update_problem(7, 24, seed=22)]
-    dev, ref = make_ctx(prs, 10, dtype), make_ctx(prs, 10, dtype, with_map=False)
+    dev, ref = make_ctx(prs, 10, dtype, cap=cap), make_ctx(prs, 10, dtype, with_map=False)
     try:
         tabs = {f: problem_table(prs[f], 10, rng, drop_newest=False) for f in (0, 2)}
+        if pad:
+            for f in (0, 2):
+                tabs[f], pos = padded(tabs[f], rng, pad, [[], [0], [4, 5], [5], [prs[f].N - 1], [0, 2, 4]])
+                assert pos[0] >= 256
         slots = {0: [0, 1], 2: [0, 3]}
         for f in (0, 2):
             put(dev, f, tabs[f])
@@ -284,6 +316,8 @@ def test_prune_loads_equal_batch_load(dtype):
             rm[f] = fr.removed_mask(slots[f], 10)
             tabs[f], iid, infos[f] = fr.prune_select(tabs[f], rm[f])
             np.testing.assert_array_equal(got[w][1], infos[f])
+            if pad:
+                assert infos[f][:, 3].min() >= 256 and infos[f][:, 3].max() >= 512
         # triangulation form: the involved, uninitialised rows with all their observations
         tri = {f: infos[f][~infos[f][:, 2].astype(bool)] for f in (0, 2)}
         assert all(len(tri[f]) >= 1 for f in (0, 2))
@@ -331,6 +365,16 @@ def test_prune_loads_equal_batch_load(dtype):
     finally:
         dev.close()
         ref.close()
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_prune_loads_equal_batch_load(dtype):
+    check_prune_loads(dtype)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_prune_loads_from_rows_beyond_256(dtype):
+    check_prune_loads(dtype, cap=1024, pad=700)
 
 
 def test_second_mask_word():
@@ -385,7 +429,7 @@ def late_start(st, k0):
     return FeatureStream(st.imu, st.frame_t[k0:], st.frame_off[k0:] - a, st.feat_id[a:], st.feat_z[a:], st.gt)
 
 
-_STREAMS = []
+_STREAMS, _BIG_STREAM = [], []
 
 
 def streams():
@@ -420,6 +464,38 @@ def assert_same_run(a, b):
 def test_device_map_equals_host_map(dtype, which):
     st = streams()[which]
     assert_same_run(single(st, dtype, device_map=True), single(st, dtype))
+
+
+def big_stream():
+    """400 features in every frame: the map passes 256 rows (tests/test_feature_map_ref.py
+    asserts it on the stand-in), so every map kernel loops at the default map_capacity."""
+    if not _BIG_STREAM:
+        _BIG_STREAM.append(FeatureStream.from_synthetic(synth.make_sequence(30, 3, max_features=400, n_landmarks=2000)))
+    return _BIG_STREAM[0]
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_device_map_equals_host_map_above_256_rows(dtype):
+    st = big_stream()
+    assert np.diff(st.frame_off).min() > 256
+    assert_same_run(single(st, dtype, device_map=True), single(st, dtype))
+
+
+def test_multi_device_map_equals_host_map_mixed_sizes():
+    """A 400-feature lane next to a 150-feature lane: the two workgroups of one
+    launch loop a different number of times."""
+    sts = [big_stream(), streams()[1]]
+    out = []
+    for kw in ({"device_map": True}, {}):
+        ms = MultiMSCKF(2, **kw)
+        try:
+            trajs = ms.run_streams(sts, arrays=bool(kw))
+            out.append([(trajs[i], ln.gate_log, ln.gamma_log, ln.shape_log, ln.state_cov())
+                        for i, ln in enumerate(ms.lanes)])
+        finally:
+            ms.close()
+    for a, b in zip(*out):
+        assert_same_run(a, b)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -476,6 +552,7 @@ def test_errors_leave_the_tables():
     rng = np.random.default_rng(3)
     ctx = make_ctx([small_problem(6, 1), None, small_problem(6, 2)], Nmax=8)
     bare = make_ctx([small_problem(6, 1)], Nmax=8, with_map=False)
+    roomy = make_ctx([small_problem(6, 1), small_problem(6, 2)], Nmax=8, cap=1024)
     try:
         tabs = {0: random_table(rng, 250, 8, 6), 2: random_table(rng, 20, 8, 6)}
         for f in (0, 2):
@@ -536,9 +613,27 @@ def test_errors_leave_the_tables():
         ctx.map_clear([0])
         assert_table(ctx, 0, fr.empty(8))
         assert_table(ctx, 2, tabs[2])
+        # overflow beyond one pass: 700 rows + 325 new ids = cap + 1, the new ids in every chunk of a 625-row message
+        t, ids, z = fc.overflow_case(1024)
+        small = random_table(rng, 20, 8, 6)
+        put(roomy, 0, t)
+        put(roomy, 1, small)
+        with pytest.raises(MsckfError) as e:
+            roomy.map_add_lost([1, 0], [0, 0, len(ids)], ids, z)
+        assert rc_of(e) == -3
+        assert_table(roomy, 0, t)
+        assert_table(roomy, 1, small)
+        got = roomy.map_add_lost([0], [0, len(ids) - 1], ids[:-1], z[:-1])[0]      # one id fewer fills the map exactly
+        nxt = fr.add_lost(t, ids[:-1], z[:-1], 5, 1024)
+        assert got[0] == nxt[1] == 300 and got[1] == 700
+        np.testing.assert_array_equal(got[2], nxt[3])
+        np.testing.assert_array_equal(got[3], nxt[4])
+        assert_table(roomy, 0, nxt[0])
+        assert_table(roomy, 1, small)
     finally:
         ctx.close()
         bare.close()
+        roomy.close()
 
 
 def test_dof_above_99_is_refused():

@@ -195,7 +195,7 @@ def test_stereo_match_sets_equal_stereo_match(n_sets):
 
 
 # ----------------------------------------------------------- fast_grid_sets --
-def grid_images():
+def grid_images(W=W, H=H):
     """Six images for detection: textures with a flat band and a sparse corner,
     and one of single bright pixels (few keypoints)."""
     imgs = []
@@ -207,11 +207,12 @@ def grid_images():
     dots = np.full((H, W), 40, np.uint8)
     for x, y, v in [(10, 8, 200), (40, 30, 120), (70, 50, 160), (80, 5, 100), (140, 20, 160), (100, 25, 200),
                     (90, 40, 160), (120, 52, 180), (30, 100, 90)]:
-        dots[y, x] = v
+        if x < W:
+            dots[y, x] = v
     return imgs + [dots]
 
 
-def occupied(fe, slot, n, seed):
+def occupied(fe, slot, n, seed, W=W, H=H):
     """n occupied points: detected corners of the slot's image (so that the mask
     removes keypoints) and points in the edge bands."""
     xy, _ = fe.fast(slot, 15)
@@ -221,30 +222,42 @@ def occupied(fe, slot, n, seed):
     return np.concatenate([pick[:max(n - len(edge), 1)], edge])[:n].astype(np.float32)
 
 
-OCC = {1: [300], 2: [1, 0], 11: [0, 1, 300, 63, 64, 0, 65, 257, 1, 300, 0]}
+OCC = {1: [300], 2: [1, 0], 3: [300, 0, 65], 11: [0, 1, 300, 63, 64, 0, 65, 257, 1, 300, 0]}
+# (n_sets, rows, cols, k, image rows): above 256 image rows k_row_scan_sets gives a thread two rows
+GRID_SETS = [(1, 4, 5, 5, H), (2, 4, 5, 5, H), (11, 4, 5, 1, H), (11, 4, 5, 16, H), (11, 1, 1, 1, H), (11, 1, 1, 16, H),
+             (1, 4, 5, 5, 300), (3, 4, 5, 5, 300)]
 
 
-@pytest.mark.parametrize("n_sets,rows,cols,k", [(1, 4, 5, 5), (2, 4, 5, 5), (11, 4, 5, 1), (11, 4, 5, 16),
-                                                (11, 1, 1, 1), (11, 1, 1, 16)])
-def test_fast_grid_sets_equal_fast_grid(n_sets, rows, cols, k):
-    fe, _ = frontend()
-    fe.upload_many(list(range(NSLOT)), np.stack(grid_images()))
-    slots = [(5 * i + 1) % NSLOT for i in range(n_sets)]          # 1 0 5 4 3 2 1 ...: every image, repeats
-    sets = [(s, occupied(fe, s, n, i)) for i, (s, n) in enumerate(zip(slots, OCC[n_sets]))]
-    assert [len(o) for _, o in sets] == OCC[n_sets]
-    got = fe.fast_grid_sets(sets, 15, rows, cols, k)
-    assert len(got) == n_sets
-    for (s, occ), (xy, resp, cnt, n) in zip(sets, got):
-        rxy, rresp, rcnt, rn = fe.fast_grid(s, 15, occ, rows, cols, k)
-        assert n == rn and cnt.sum() == n
-        np.testing.assert_array_equal(cnt, rcnt)
-        np.testing.assert_array_equal(xy, rxy)
-        np.testing.assert_array_equal(resp, rresp)
-    for a, b in zip(got, fe.fast_grid_sets(sets, 15, rows, cols, k)):     # two consecutive calls: the same bits
-        assert a[3] == b[3] and all((x == y).all() for x, y in zip(a[:3], b[:3]))
-    if n_sets == 11:
-        free = fe.fast_grid(slots[2], 15, np.zeros((0, 2)), rows, cols, k)[3]
-        assert got[2][3] < free                                           # 300 occupied points masked keypoints
+@pytest.mark.parametrize("n_sets,rows,cols,k,Hi", GRID_SETS,
+                         ids=["-".join(str(v) for v in (c[:4] if c[4] == H else c)) for c in GRID_SETS])
+def test_fast_grid_sets_equal_fast_grid(n_sets, rows, cols, k, Hi):
+    if Hi == H:
+        fe, Wi = frontend()[0], W
+    else:                                            # 96 x 300: a narrow image holds no level above 0
+        fe, Wi = fe_mod.Frontend(96, Hi, nslot=NSLOT, max_level=0, max_points=MAXP), 96
+    try:
+        fe.upload_many(list(range(NSLOT)), np.stack(grid_images(Wi, Hi)))
+        slots = [(5 * i + 1) % NSLOT for i in range(n_sets)]          # 1 0 5 4 3 2 1 ...: every image, repeats
+        sets = [(s, occupied(fe, s, n, i, Wi, Hi)) for i, (s, n) in enumerate(zip(slots, OCC[n_sets]))]
+        assert [len(o) for _, o in sets] == OCC[n_sets]
+        got = fe.fast_grid_sets(sets, 15, rows, cols, k)
+        assert len(got) == n_sets
+        for (s, occ), (xy, resp, cnt, n) in zip(sets, got):
+            rxy, rresp, rcnt, rn = fe.fast_grid(s, 15, occ, rows, cols, k)
+            assert n == rn and cnt.sum() == n
+            np.testing.assert_array_equal(cnt, rcnt)
+            np.testing.assert_array_equal(xy, rxy)
+            np.testing.assert_array_equal(resp, rresp)
+        for a, b in zip(got, fe.fast_grid_sets(sets, 15, rows, cols, k)):     # two consecutive calls: the same bits
+            assert a[3] == b[3] and all((x == y).all() for x, y in zip(a[:3], b[:3]))
+        if n_sets == 11:
+            free = fe.fast_grid(slots[2], 15, np.zeros((0, 2)), rows, cols, k)[3]
+            assert got[2][3] < free                                           # 300 occupied points masked keypoints
+        if Hi > 256:                                 # keypoints from row 256 on, in the last row of cells
+            assert all((xy[:, 1] >= 256).any() for xy, _, _, _ in got[:1])
+    finally:
+        if Hi != H:
+            fe.close()
 
 
 def test_fast_grid_sets_overflow_is_an_error():

@@ -257,14 +257,23 @@ def test_fast_grid_occupied_counts(n_occ):
 
 
 @pytest.mark.parametrize("W,H,rows,cols,k", [(150, 110, 4, 5, 1), (150, 110, 4, 5, 16), (150, 110, 1, 1, 5),
-                                             (150, 110, 1, 1, 16), (150, 110, 3, 7, 3), (376, 240, 4, 5, 5)])
+                                             (150, 110, 1, 1, 16), (150, 110, 3, 7, 3), (376, 240, 4, 5, 5),
+                                             (96, 257, 4, 5, 5), (96, 300, 4, 5, 5), (96, 513, 4, 5, 5)])
 def test_fast_grid_grids(W, H, rows, cols, k):
-    img = grid_image(W, H) if W == 150 else fs.render(fs.texture_fn(7, W=W, H=H), W, H)
+    """H > 256: the row scan gives each of its 256 threads 2 rows (H = 257: thread
+    128 a single one; H = 300: the threads from 150 on none) or 3 (H = 513)."""
+    img = fs.render(fs.texture_fn(7, W=W, H=H), W, H) if W == 376 else grid_image(W, H)
+    if W == 96 and (W, H) not in _ctx:                             # a narrow image holds no level above 0
+        _ctx[(W, H)] = fe_mod.Frontend(W, H, nslot=2, max_level=0, max_points=1024)
     fe = frontend(W, H)
     fe.upload(0, img)
-    xy, resp, cnt, n = check_fast_grid(fe, img, occupied_points(img, 40, 1), rows, cols, k)
+    occ = occupied_points(img, 40, 1)
+    xy, resp, cnt, n = check_fast_grid(fe, img, occ, rows, cols, k)
     assert cnt.sum() == n and len(xy) == np.minimum(cnt, k).sum() > 0
     assert H % rows or W % cols or (rows, cols) == (1, 1)          # ragged last cells
+    if H > 256:                       # keypoints in the last row of cells, and from row 256 on where a corner can be
+        ry = pr.fast_grid(img, 15, occ, rows, cols, k)[0][:, 1]
+        assert (ry >= (rows - 1) * -(-H // rows)).any() and ((ry >= 256).any() or H - 3 <= 256)
 
 
 def test_fast_grid_cell_fill_and_tie():

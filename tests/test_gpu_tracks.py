@@ -19,6 +19,13 @@ top edge (the bounds test), rows with a displaced cam1 point (RANSAC) and
 lifetimes of 1..4 (ties in the prune); test_the_cases_cover_every_branch asserts
 from the reference's own counters that each branch occurs.
 
+BIG: the kernels' compactions and the per-cell gather walk 256 rows at a time,
+so three more CASES hold tables of 257, 600 and 700 rows (376 x 240 images for
+the latter two, ``cap`` no multiple of 256): the survivors of steps 2, 3 and 4
+each above 512 in a 4 x 5 grid, next to a lane of 40 rows and an empty one, and
+one cell of more than 512 rows in a 1 x 1 grid pruned to 16.
+test_the_big_cases_pass_one_chunk asserts that from the reference's lists.
+
 End to end: the lanes of tests/test_gpu_lanes.py's three-lane test publish, with
 device_tracks, what single ImageProcessors publish, bit for bit.  The lanes of
 one mfe_tracks_step share grid_min_feature_num (the constructor rejects a
@@ -49,7 +56,15 @@ CASES = {
     "1x1_1_1": ((1, 1, 1, 1), [(1, 0, False, 27), (0, 2, False, 28), (1, 1, True, 29)]),
     "1x1_2_16": ((1, 1, 2, 16), [(16, 0, True, 30)]),
     "1x1_3_5": ((1, 1, 3, 5), [(5, 1, False, 31), (2, 2, True, 32)]),
+    # beyond one 256-row chunk of k_trk_compact / k_trk_assemble (see BIG below)
+    "4x5_3_5_257": ((4, 5, 3, 5), [(257, 0, True, 33)]),
+    "4x5_3_5_700": ((4, 5, 3, 5), [(700, 0, True, 34), (40, 1, False, 35), (0, 2, False, 36)]),
+    "1x1_2_16_600": ((1, 1, 2, 16), [(600, 0, False, 37)]),
 }
+# The cases whose tables pass 256 rows: (W, H) where the 150 x 110 scene has too few corners, and a
+# ``cap`` a little above rows + cells grid_min that is no multiple of 256.  None of them uses H > 256:
+# the row scan's case of several rows per thread is tests/test_gpu_pipeline.py's and test_gpu_lanes.py's.
+BIG = {"4x5_3_5_257": ((W, H), 320), "4x5_3_5_700": ((376, 240), 765), "1x1_2_16_600": ((376, 240), 605)}
 _cache = {}
 
 
@@ -74,14 +89,14 @@ def camera(kind):
     return (K0, 1, k), (K1, 1, k), np.eye(3), E, 5.0      # equidistant: the reference never rectifies the guess
 
 
-def lane_frames(seed):
+def lane_frames(seed, W=W, H=H):
     """Three stereo frames of a texture moving by MOTION per frame."""
     f = fs.texture_fn(seed, W=W, H=H)
     out = []
     for k in range(3):
         dx, dy = MOTION[0] * k, MOTION[1] * k
         im0, im1 = fs.render(f, W, H, dx, dy).copy(), fs.render(f, W, H, dx - DISPARITY, dy).copy()
-        im0[:, 120:], im1[:, 115:] = 90, 90          # the last grid column holds no corner
+        im0[:, 4 * W // 5:], im1[:, 4 * W // 5 - 5:] = 90, 90     # the last grid column holds no corner
         im0[40:70, 60:90] = 128                      # rows here fail LK
         im1[:34, :55] = 70                           # candidates here fail the stereo match
         out.append((im0, im1))
@@ -91,13 +106,17 @@ def lane_frames(seed):
 def lane_table(ops, lane, n, kind, seed):
     """n rows for the lane whose slots hold frame 0 in (c0, c1): detected corners
     with their stereo matches, a row in the flat patch, rows at the top edge
-    and next to a cell boundary; every 6th row's cam1 displaced."""
+    and next to a cell boundary; every 6th row's cam1 displaced.  A table of more
+    rows than the frame has corners repeats corners, each row with its own offset."""
     if n == 0:
         return tr.empty_table(1000 * (lane + 1))
     cam0, cam1, R, E, thr = camera(kind)
     xy, _ = ops.fast(3 * lane + 1, THRESHOLD)
     rng = np.random.default_rng(seed)
-    p = xy[rng.permutation(len(xy))[:n]].astype(np.float32) + rng.uniform(0, 0.9, (n, 2)).astype(np.float32)
+    pick = rng.permutation(len(xy))[:n]
+    if len(pick) < n:
+        pick = np.concatenate([pick, rng.integers(0, len(xy), n - len(pick))])
+    p = xy[pick].astype(np.float32) + rng.uniform(0, 0.9, (n, 2)).astype(np.float32)
     extra = np.array([[75.25, 55.5], [70.5, 0.75], [31.0, 1.25], [28.75, 50.5], [100.5, 0.5], [58.5, 27.0]], np.float32)
     m = min((n + 1) // 2, len(extra))
     p[:m] = extra[:m]
@@ -123,16 +142,17 @@ def lane_args(lane, kind, ransac, step, seed):
 def run_case(ops, name, on_tables=None):
     """Two consecutive reference steps of the case on ``ops`` (a Frontend or its
     CPU stand-in).  ``on_tables(step, tables, lanes, args)`` runs before each
-    reference step, the images in place.  Returns [(results, tables after)] and
-    the cover counters."""
+    reference step, the images in place.  Returns [(results, tables after)], the
+    cover counters and the two steps' traces."""
     (rows, cols, gmin, gmax), lanes = CASES[name]
     grid = tr.Grid(rows, cols, gmin, gmax)
-    frames = [lane_frames(seed) for _, _, _, seed in lanes]
+    Wc, Hc = BIG.get(name, ((W, H), 0))[0]
+    frames = [lane_frames(seed, Wc, Hc) for _, _, _, seed in lanes]
     S = len(lanes)
     ops.upload_many([3 * l + 1 + j for l in range(S) for j in range(2)],
                     np.stack([frames[l][0][j] for l in range(S) for j in range(2)]))
     tables = {l: lane_table(ops, l, n, kind, seed) for l, (n, kind, _, seed) in enumerate(lanes)}
-    out, cover = [], Counter()
+    out, cover, traces = [], Counter(), []
     for step in range(2):
         # frame step + 1: cam0 into the slot that is not the previous image's, cam1 into the third
         c0 = [3 * l if step == 0 else 3 * l + 1 for l in range(S)]
@@ -141,11 +161,13 @@ def run_case(ops, name, on_tables=None):
         args = [lane_args(l, kind, ransac, step, seed) for l, (_, kind, ransac, seed) in enumerate(lanes)]
         if on_tables:
             on_tables(step, tables, lanes, args)
-        res, nxt, cov = tr.step(ops, tables, args, grid, W, H, THRESHOLD, inlier_error=INLIER_ERROR, n_hyp=N_HYP, **LK)
+        traces.append({})
+        res, nxt, cov = tr.step(ops, tables, args, grid, Wc, Hc, THRESHOLD, inlier_error=INLIER_ERROR, n_hyp=N_HYP,
+                                trace=traces[-1], **LK)
         tables = {**tables, **nxt}
         cover += cov
         out.append((res, tables))
-    return out, cover
+    return out, cover, traces
 
 
 def same_result(a, b):
@@ -169,10 +191,11 @@ def device_case(name):
         return _cache[name]
     (rows, cols, gmin, gmax), lanes = CASES[name]
     S = len(lanes)
-    fe = fe_mod.Frontend(W, H, nslot=3 * S, max_level=LK["max_level"], max_points=4096)
+    (Wc, Hc), cap = BIG.get(name, ((W, H), tr.min_cap(tr.Grid(rows, cols, gmin, gmax))))
+    fe = fe_mod.Frontend(Wc, Hc, nslot=3 * S, max_level=LK["max_level"], max_points=4096)
     got = []
     try:
-        fe.tracks_create(S, tr.min_cap(tr.Grid(rows, cols, gmin, gmax)), rows, cols, gmin, gmax)
+        fe.tracks_create(S, cap, rows, cols, gmin, gmax)
 
         def on_tables(step, tables, lanes_, args):
             if step == 0:
@@ -182,16 +205,16 @@ def device_case(name):
             # the second step reads what the first wrote
             res = fe.tracks_step(args, THRESHOLD, inlier_error=INLIER_ERROR, n_hyp=N_HYP, **LK)
             got.append((res, [fe.tracks_get(l) for l in range(S)]))
-        ref, cover = run_case(fe, name, on_tables)
+        ref, cover, traces = run_case(fe, name, on_tables)
     finally:
         fe.close()
-    _cache[name] = (got, ref, cover)
+    _cache[name] = (got, ref, cover, traces)
     return _cache[name]
 
 
 @pytest.mark.parametrize("name", list(CASES))
 def test_step_equals_the_composition_of_set_calls(name):
-    got, ref, _ = device_case(name)
+    got, ref = device_case(name)[:2]
     assert len(got) == len(ref) == 2
     for step, ((res, tabs), (rres, rtabs)) in enumerate(zip(got, ref)):
         assert len(res) == len(rres) == len(CASES[name][1])
@@ -215,10 +238,40 @@ def test_the_cases_cover_every_branch():
         assert cover[what] > 0, (what, dict(cover))
 
 
-def small_context(S=3, grid=(4, 5, 3, 5), rows=(40, 12, 0), seeds=(21, 22, 23)):
+def test_the_big_cases_pass_one_chunk():
+    """A condition on the inputs of the BIG cases, from the reference's counters and
+    lists at their first step: k_trk_compact and k_trk_assemble walk 256 rows at a
+    time and carry the rows kept so far from chunk to chunk."""
+    for name, (_, cap) in BIG.items():
+        (rows, cols, gmin, gmax), lanes = CASES[name]
+        assert cap % 256 and cap >= max(n for n, _, _, _ in lanes) + rows * cols * gmin
+    # tables of 257 and of 513 rows or more; next to the largest a lane below 64 rows and an empty one
+    assert [n for n, _, _, _ in CASES["4x5_3_5_257"][1]] == [257]
+    assert [(n >= 513, 0 < n < 64, n == 0) for n, _, _, _ in CASES["4x5_3_5_700"][1]] == [
+        (True, False, False), (False, True, False), (False, False, True)]
+    assert CASES["4x5_3_5_700"][1][0][2]                         # RANSAC in the large lane: its set grids pass a block
+    _, ref, _, traces = device_case("4x5_3_5_700")
+    ctr = ref[0][0][0].counters
+    assert ctr[0] == 700 and (ctr[:3] > 512).all() and (ctr[1:] > 256).all(), ctr    # each compaction reads three chunks
+    keep = traces[0]["keep", 0]
+    assert [len(k) for k in keep] == ctr[:3].tolist()
+    for stage, k in enumerate(keep):                             # dropped inside the first chunk, kept inside a later one
+        assert (~k[:256]).any() and k[256:].any(), stage
+        assert 0 < k[:256].sum() < 256                           # the carried count is neither 0 nor the chunk's start
+    keep = device_case("4x5_3_5_257")[3][0]["keep", 0][0]
+    assert len(keep) == 257 and (~keep[:256]).any() and keep[256]      # the one row of the second chunk is written
+    # one cell above 256 rows: gathered across chunks, ranked by lifetime with ties across the chunk edges
+    _, ref, _, traces = device_case("1x1_2_16_600")
+    res = ref[0][0][0]
+    assert res.counters[3] > 256 and traces[0]["cell", 0] >= res.counters[3] and res.n == 16
+    life = ref[0][1][0].life
+    assert (life == life[0]).all() and life[0] == 5              # the longest-lived alone fill the cell
+
+
+def small_context(S=3, grid=(4, 5, 3, 5), rows=(40, 12, 0), seeds=(21, 22, 23), cap=None):
     """A context with S lanes, frame 0 -> 1 in the slots and a table in each lane."""
     fe = fe_mod.Frontend(W, H, nslot=3 * S, max_level=LK["max_level"], max_points=4096)
-    fe.tracks_create(S, tr.min_cap(tr.Grid(*grid)), *grid)
+    fe.tracks_create(S, cap or tr.min_cap(tr.Grid(*grid)), *grid)
     frames = [lane_frames(s) for s in seeds]
     fe.upload_many([3 * l + 1 + j for l in range(S) for j in range(2)],
                    np.stack([frames[l][0][j] for l in range(S) for j in range(2)]))
@@ -240,6 +293,22 @@ def test_overflow_returns_minus_3_and_changes_no_table():
             same_table(fe.tracks_get(l), t)
         res = fe.tracks_step(args, THRESHOLD, inlier_error=INLIER_ERROR, n_hyp=N_HYP, **LK)
         assert e.value.n_total.tolist() == [r.n_total for r in res] and max(r.n_total for r in res) > 8
+    finally:
+        fe.close()
+    # a table above 256 rows at cap 320: 260 rows + 20 cells x grid_min 3 == cap
+    fe, tables, args = small_context(S=1, rows=(260,), seeds=(33,), cap=320)
+    try:
+        t = tables[0]
+        more = (np.append(t.ids, -5), np.append(t.life, 1), np.vstack([t.cam0, t.cam0[:1]]), np.vstack([t.cam1, t.cam1[:1]]))
+        with pytest.raises(_lib.MsckfError, match="rc=-1"):       # n + cells grid_min == cap + 1: no room for the new rows
+            fe.tracks_put(0, *more, t.next_id)
+        same_table(fe.tracks_get(0), t)
+        with pytest.raises(_lib.MsckfError, match="rc=-3") as e:
+            fe.tracks_step(args, THRESHOLD, max_kp=8, inlier_error=INLIER_ERROR, n_hyp=N_HYP, **LK)
+        same_table(fe.tracks_get(0), t)
+        res = fe.tracks_step(args, THRESHOLD, inlier_error=INLIER_ERROR, n_hyp=N_HYP, **LK)
+        assert e.value.n_total.tolist() == [res[0].n_total] and res[0].n_total > 8
+        assert res[0].counters[0] == 260 and res[0].counters[3] > 0 and res[0].n + 60 <= 320
     finally:
         fe.close()
 
