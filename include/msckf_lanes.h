@@ -2,7 +2,8 @@
  * msckf_lanes.h -- the front-end's device calls for many stereo streams
  * (lanes) at once, on the same mfe_ctx_t (same library, conventions of
  * msckf_frontend.h).  Each call is, per set, exactly its single-stream
- * counterpart, bit for bit; this text states only what the set form adds:
+ * counterpart, bit for bit -- the single call is this call with one set, on
+ * the same kernels; this text states only what the set form adds:
  *
  *   mfe_upload_many        mfe_upload          (msckf_frontend.h)
  *   mfe_lk_sets            mfe_lk              (msckf_frontend.h)
@@ -36,8 +37,7 @@
  *    fixed (an image, a grid cell) and from a per-point set index, which the
  *    call derives from set_off, for point lists.  The slots' pyramid
  *    descriptors and the per-set arguments are read from device tables; the
- *    descriptor table is written once, by the context's first call of this
- *    header.
+ *    descriptor table is written once, by mfe_create.
  *
  * mfe_create accepts up to 96 slots (three per lane, 32 lanes).
  *
@@ -83,8 +83,8 @@
  * returns -3 with every n_total set and nothing else written.
  *
  * The score map, mask, row counts / offsets and raster keypoint list of
- * mfe_fast_grid exist once per set; they are allocated at the first call and
- * again when a call has more sets than any before (not by mfe_create).  The
+ * mfe_fast_grid exist once per set; mfe_create allocates them for one set and
+ * a call with more sets than any before allocates them again.  The
  * stages run as in mfe_fast_grid with the set in the grid, one launch per
  * stage; the same fixed-order reductions, no atomics.  The call makes no
  * read of the totals in between: as in mfe_fast_grid, the raster list and the

@@ -22,7 +22,7 @@
  * For each of the n cam0 points pt (pixels, fp64, as mfe_undistort takes them)
  * exactly what ImageProcessor.stereo_match composes from mfe_undistort,
  * mfe_distort, mfe_lk, mfe_lk and two more mfe_undistort calls; one wavefront
- * per point (k_stereo_match).  No fp contraction anywhere.
+ * per point (k_stereo_match_sets).  No fp contraction anywhere.
  *
  *  1. Initial guess, fp64: g = distort_cam1(undistort_cam0(pt, R_guess, new
  *     intrinsics [1 1 0 0])) -- the arithmetic of mfe_undistort followed by
@@ -74,7 +74,7 @@
  *          does with a negative start (image.py:317-360).  A NaN coordinate
  *          clears nothing.
  *  Detect  FAST 9/16, score, 3x3 non-max suppression and the mask exactly as
- *          mfe_fast (k_fast and k_fast_rows unchanged), the keypoints in
+ *          mfe_fast (the same k_fast_sets and k_fast_rows_sets), the keypoints in
  *          raster order; the row offsets come from a device scan.  *n_total =
  *          the keypoints that passed, before selection.
  *  Select  A keypoint's cell is (y / gh) grid_col + x / gw (integer division),

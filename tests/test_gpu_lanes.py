@@ -2,14 +2,23 @@
 mfe_stereo_match_sets, mfe_fast_grid_sets, mfe_undistort_sets) and
 MultiImageProcessor on the device.
 
-The reference of every comparison is the existing single-stream call on the
-same inputs (pinned to the oracle by tests/test_gpu_frontend.py and
-tests/test_gpu_pipeline.py), so every comparison is bit-exact, on every point.
+Every operator has one kernel, the set form, and a single-stream call is that
+kernel run with one set.  The single calls are pinned to the oracle and the
+reference by tests/test_gpu_frontend.py and tests/test_gpu_pipeline.py, which
+so exercise the set kernels directly; they are the anchor to the truth.  The
+comparisons here put many sets in one call against the same kernels with one
+set at a time, on the same inputs: that checks the per-set indexing (slots,
+per-point set index, per-set work areas and tables), and every comparison is
+bit-exact, on every point.
 
 Per-call cases: 150 x 110 images (no multiple of 16 or 64), six slots holding
 six different images; the set layouts of LAYOUTS -- 1, 2 and 11 sets, the sizes
 0, 1, 63, 64, 65 and 257, an empty set first, in the middle and last; in the
 11-set layout sets share a slot pair and use pairs reversed (PAIRS).
+
+The single calls on the shared state: they work in set 0 of the detection's
+work areas, which a set call with more sets reallocates and any detection
+leaves its mask in; their result codes through ctypes.
 
 End to end: three lanes (the two golden scenes and a third texture, one lane
 with RANSAC, one started late) publish, bit for bit, what a single
@@ -308,6 +317,90 @@ def test_undistort_sets_equal_undistort(n_sets):
     assert rejected > 0 if n_sets != 2 else True          # the fisheye rejection value, bit for bit
     for a, b in zip(got, fe.undistort_sets(sets)):
         assert a.tobytes() == b.tobytes()
+
+
+# ------------------------------------------ the single calls on shared state --
+def test_single_calls_survive_a_grow_of_the_work_area():
+    fe = fe_mod.Frontend(W, H, nslot=NSLOT, max_level=LK["max_level"], max_points=MAXP)
+    try:
+        for s, im in enumerate(grid_images()):
+            fe.upload(s, im)
+        occ = occupied(fe, 1, 65, 0)
+        single = lambda: fe.fast(1, 15) + fe.fast_grid(1, 15, occ, 4, 5, 5)
+        before = single()
+        assert len(before[0]) > 20 and before[5] > 20
+        sets = [(s, occupied(fe, s, n, i)) for i, (s, n) in enumerate(zip((0, 1, 5), OCC[3]))]
+        assert len(fe.fast_grid_sets(sets, 15, 4, 5, 5)) == 3      # one set -> three: the areas are allocated again
+        for a, b in zip(single(), before):
+            np.testing.assert_array_equal(a, b)
+    finally:
+        fe.close()
+
+
+def test_unmasked_fast_after_a_masked_detection():
+    fe, _ = frontend()
+    fe.upload_many(list(range(NSLOT)), np.stack(grid_images()))
+
+    def same(a, b):
+        np.testing.assert_array_equal(a[0], b[0])
+        np.testing.assert_array_equal(a[1], b[1])
+    r0 = fe.fast(0, 15)
+    assert fe.fast_grid(0, 15, occupied(fe, 0, 300, 1), 4, 5, 5)[3] < len(r0[0])      # the mask removed keypoints
+    same(fe.fast(0, 15), r0)                                  # mask = NULL is unmasked, whatever set 0's mask held
+    m = np.ones((H, W), np.uint8)
+    m[:, :75] = 0
+    keep = r0[0][:, 0] >= 75
+    assert 0 < keep.sum() < len(keep)
+    same(fe.fast(0, 15, mask=m), (r0[0][keep], r0[1][keep]))
+    same(fe.fast(0, 15), r0)
+
+
+def test_single_calls_result_codes():
+    fe, _ = frontend()
+    lib, h = fe.lib, fe.h
+    fp, dp, u8 = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+    d = lambda a: np.ascontiguousarray(a, float).ravel().ctypes.data_as(dp)
+    big = MAXP + 1
+    prev = np.random.default_rng(0).uniform(10, 100, (big, 2)).astype(np.float32)
+    nxt0 = prev + np.float32(0.5)
+
+    def lk(slot_next, n):
+        nxt, st = nxt0.copy(), np.full(big, 9, np.uint8)
+        rc = lib.mfe_lk(h, 0, slot_next, n, prev.ctypes.data_as(fp), nxt.ctypes.data_as(fp), st.ctypes.data_as(u8),
+                        15, 2, 30, 0.01)
+        return rc, bool((nxt == nxt0).all() and (st == 9).all())
+    rc, untouched = lk(1, 10)
+    assert rc == 0 and not untouched
+    assert lk(NSLOT, 10) == (-1, True)                       # a bad slot: next_pts and status as passed
+    assert lk(1, big) == (-1, True)                          # n above the context's max_points
+    assert lk(1, 0) == (0, True)
+
+    p = points(65, 7)
+    for kind in (1, 2):                                      # radtan, equidistant
+        K, model, k = camera(kind)[0]
+        def und(n, R, nK):
+            out = np.full((len(p), 2), -7.0)
+            rc = lib.mfe_undistort(h, n, d(p), out.ctypes.data_as(dp), d(K), model, d(k), R, nK)
+            return rc, out
+        (rc0, a), (rc1, b) = und(len(p), None, None), und(len(p), d(np.eye(3)), d([1.0, 1.0, 0.0, 0.0]))
+        assert rc0 == rc1 == 0 and a.tobytes() == b.tobytes() and (a != -7.0).all()
+        rc, out = und(0, None, None)
+        assert rc == 0 and (out == -7.0).all()
+        out = np.full((len(p), 2), -7.0)
+        assert lib.mfe_distort(h, 0, d(p), out.ctypes.data_as(dp), d(K), model, d(k)) == 0 and (out == -7.0).all()
+
+    cam0, cam1, R, E, thr = camera(1)
+
+    def stereo(n, model0):
+        c1, inl, rsn = np.full((len(p), 2), -7, np.float32), np.full(len(p), 9, np.uint8), np.full(len(p), 9, np.uint8)
+        rc = lib.mfe_stereo_match(h, 0, 1, n, d(p), d(cam0[0]), model0, d(cam0[2]), d(cam1[0]), cam1[1], d(cam1[2]),
+                                  d(R), d(E), 15, 2, 30, 0.01, thr, c1.ctypes.data_as(fp), inl.ctypes.data_as(u8),
+                                  rsn.ctypes.data_as(u8))
+        return rc, bool((c1 == -7).all() and (inl == 9).all() and (rsn == 9).all())
+    rc, untouched = stereo(len(p), cam0[1])
+    assert rc == 0 and not untouched
+    assert stereo(len(p), 7) == (-1, True)                   # an unknown model: the outputs untouched
+    assert stereo(0, cam0[1]) == (0, True)
 
 
 # ------------------------------------------------------------------- errors --

@@ -1,6 +1,7 @@
-"""mfe_stereo_match and mfe_fast_grid (include/msckf_pipeline.h; k_stereo_match,
-k_mask_clear, k_row_scan, k_grid_select) on small images: 150 x 110 (no
-multiple of 16 or 64, ragged last grid cells) and the 376 x 240 scenes of
+"""mfe_stereo_match and mfe_fast_grid (include/msckf_pipeline.h; k_stereo_match_sets,
+k_mask_clear_sets, k_row_scan_sets, k_grid_select_sets, each run with one set) on
+small images: 150 x 110 (no multiple of 16 or 64, ragged last grid cells) and the
+376 x 240 scenes of
 tests/golden/frontend_ref.npz.
 
 fast_grid against the reference tests/frontend_pipeline_ref.py, bit-exact on

@@ -86,6 +86,30 @@ def test_call_counts(monkeypatch):
     key = lambda ip: [(f.id, f.cam0_point, f.cam1_point, f.response) for c in ip.curr_features for f in c]
     assert key(on) == key(off) and len(key(on)) > 0
 
+    # one whole tracked frame (the second stareo_callback, RANSAC on), uploads included: the
+    # switch-off list is the one the plain methods made before the frame logic was written once
+    composed = ["undistort", "distort", "lk", "lk", "undistort", "undistort"]
+    want = {False: ["upload", "upload", "lk"] + composed + ["ransac", "fast"] + composed + ["undistort", "undistort"],
+            True: ["upload", "upload", "lk", "stereo_match", "ransac", "fast_grid", "stereo_match", "undistort",
+                   "undistort"]}
+    msgs = {}
+    for switch in (False, True):
+        ip = _one_frame_processor(monkeypatch, switch)
+        calls = ip.fe.calls
+        ip.config.ransac_enabled = True
+        ip.ransac_fn = lambda sets, *a: (calls.append("ransac"), [(np.ones(len(s[0]), bool), None) for s in sets])[1]
+        ip.fe.upload = lambda slot, image, up=ip.fe.upload: (calls.append("upload"), up(slot, image))[1]
+        f = fs.texture_fn(3, W=96, H=64)
+        for k in range(2):
+            img, im1 = fs.render(f, 96, 64, 1.0 * k, 0.0), fs.render(f, 96, 64, 1.0 * k - 4.0, 0.0)
+            del calls[:]
+            msgs[switch, k] = ip.stareo_callback(SimpleNamespace(
+                cam0_msg=SimpleNamespace(image=img, vio_timestamp__=0.05 * k),
+                cam1_msg=SimpleNamespace(image=im1, vio_timestamp__=0.05 * k)))
+        assert calls == want[switch], switch
+        assert ip.num_features["after_ransac"] == ip.num_features["before_tracking"] > 0
+    assert msgs[False, 1] == msgs[True, 1] and len(msgs[True, 1].vio_features) > 0
+
 
 def test_switch_is_off_by_default():
     assert fe_mod.FrontendConfig().device_pipeline is False

@@ -8,27 +8,29 @@
 // published OpenCV 4.x algorithms -- the same restatement as
 // oracle/frontend_oracle.py (test infrastructure), which the GPU tests check
 // them against:
-//   k_pyrdown   Gaussian pyramid level (pyrDown, 5x5 [1 4 6 4 1]^2, REFLECT_101)
-//   k_scharr    Scharr derivatives of a level (calcScharrDeriv)
-//   k_fast      FAST 9/16 segment test + corner score (fast.cpp, fast_score.cpp)
-//   k_fast_rows 3x3 non-max suppression + mask, raster-order compaction: one
-//               wave per image row, ballot / popcount, two passes around a host
-//               prefix sum of the row counts (deterministic order)
-//   k_lk        pyramidal Lucas-Kanade (LKTrackerInvoker), one wavefront per
+//   k_pyrdown_sets   Gaussian pyramid level (pyrDown, 5x5 [1 4 6 4 1]^2, REFLECT_101)
+//   k_scharr_sets    Scharr derivatives of a level (calcScharrDeriv)
+//   k_fast_sets      FAST 9/16 segment test + corner score (fast.cpp, fast_score.cpp)
+//   k_fast_rows_sets 3x3 non-max suppression + mask, raster-order compaction: one
+//               wave per image row, ballot / popcount, two passes around the
+//               prefix sum of the row counts, k_row_scan_sets (deterministic order)
+//   k_lk_sets   pyramidal Lucas-Kanade (LKTrackerInvoker), one wavefront per
 //               point: the 15 x 15 window over the 64 lanes, 14-bit fixed-point
 //               bilinear weights, window sums of the integer products reduced
 //               exactly (int64) across the wave
-//   k_undistort / k_distort   radtan and equidistant camera models, fp64
+//   k_undistort_sets / k_distort   radtan and equidistant camera models, fp64
 //   k_two_point_ransac   temporal outlier rejection (include/msckf_ransac.h): one
 //               workgroup per point set, one wave per hypothesis
-//   k_stereo_match   ImageProcessor.stereo_match in one launch
+//   k_stereo_match_sets   ImageProcessor.stereo_match in one launch
 //               (include/msckf_pipeline.h): one wavefront per point, the camera
-//               models and both LK runs from the functions k_undistort,
-//               k_distort and k_lk are made of
-//   k_mask_clear / k_row_scan / k_grid_select   masked detection with the
-//               per-cell selection (include/msckf_pipeline.h) around k_fast and
-//               k_fast_rows: device-built mask, device scan of the row counts,
-//               one workgroup per grid cell
+//               models and both LK runs from the functions k_undistort_sets,
+//               k_distort and k_lk_sets are made of
+//   k_mask_clear_sets / k_row_scan_sets / k_grid_select_sets   masked detection
+//               with the per-cell selection (include/msckf_pipeline.h) around
+//               k_fast_sets and k_fast_rows_sets: device-built mask, device scan
+//               of the row counts, one workgroup per grid cell
+// Each of these takes a list of sets (include/msckf_lanes.h); a single-image call
+// is the list of one.
 //   k_trk_*     the feature tracks kept on the device (include/msckf_tracks.h): a
 //               whole tracked frame of many streams chained on the device, around
 //               lk_point, stereo_point, k_two_point_ransac and the detection stages
@@ -94,11 +96,10 @@ __device__ __forceinline__ int refl101(int i, int n) {   // BORDER_REFLECT_101
 __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 
 // ---------------------------------------------------------------- pyramid --
-// The kernels below come in two forms around one body each: the single-image form
-// of msckf_frontend.h / msckf_pipeline.h with its arguments in the kernel arguments,
-// and the set form of msckf_lanes.h (k_*_sets), which takes the set index from the
-// grid or from a per-point index and reads the slots' Pyr descriptors and the
-// per-set arguments from device tables.
+// Every operator has one kernel, the set form of msckf_lanes.h (k_*_sets), around a
+// __device__ body: it takes the set index from the grid or from a per-point index
+// and reads the slots' Pyr descriptors and the per-set arguments from device tables.
+// The single-image calls of msckf_frontend.h / msckf_pipeline.h run it with one set.
 __device__ __forceinline__ void pyrdown_px(const uint8_t* __restrict__ src, int sw, int sh,
                                            uint8_t* __restrict__ dst, int dw, int dh, int x, int y) {
     if (x >= dw || y >= dh) return;
@@ -116,11 +117,6 @@ __device__ __forceinline__ void pyrdown_px(const uint8_t* __restrict__ src, int 
         s += k[i] * hsum;
     }
     dst[(size_t)y * dw + x] = (uint8_t)((s + 128) >> 8);
-}
-
-__global__ void __launch_bounds__(256) k_pyrdown(const uint8_t* __restrict__ src, int sw, int sh,
-                                                 uint8_t* __restrict__ dst, int dw, int dh) {
-    pyrdown_px(src, sw, sh, dst, dw, dh, blockIdx.x * 16 + (threadIdx.x & 15), blockIdx.y * 16 + (threadIdx.x >> 4));
 }
 
 // blockIdx.z = the image of the call; its slot's level - 1 -> level
@@ -143,11 +139,6 @@ __device__ __forceinline__ void scharr_px(const uint8_t* __restrict__ img, int w
     const int gy = 3 * (rp[xm] + rp[xp]) + 10 * rp[x] - (3 * (rm[xm] + rm[xp]) + 10 * rm[x]);
     ix[(size_t)y * w + x] = (int16_t)gx;
     iy[(size_t)y * w + x] = (int16_t)gy;
-}
-
-__global__ void __launch_bounds__(256) k_scharr(const uint8_t* __restrict__ img, int w, int h,
-                                                int16_t* __restrict__ ix, int16_t* __restrict__ iy) {
-    scharr_px(img, w, h, ix, iy, blockIdx.x * 16 + (threadIdx.x & 15), blockIdx.y * 16 + (threadIdx.x >> 4));
 }
 
 __global__ void __launch_bounds__(256) k_scharr_sets(const Pyr* __restrict__ tab, const int32_t* __restrict__ slots,
@@ -241,11 +232,6 @@ __device__ __forceinline__ void fast_px(const uint8_t* __restrict__ img, int w, 
     score[(size_t)y * w + x] = out;
 }
 
-__global__ void __launch_bounds__(256) k_fast(const uint8_t* __restrict__ img, int w, int h, int threshold,
-                                              uint16_t* __restrict__ score) {
-    fast_px(img, w, h, threshold, score, blockIdx.x * 16 + (threadIdx.x & 15), blockIdx.y * 16 + (threadIdx.x >> 4));
-}
-
 // blockIdx.z = the set: level 0 of its slot -> the set's score map
 __global__ void __launch_bounds__(256) k_fast_sets(const Pyr* __restrict__ tab, const int32_t* __restrict__ slots,
                                                    int threshold, uint16_t* __restrict__ score) {
@@ -290,14 +276,6 @@ __device__ __forceinline__ void fast_rows_row(const uint16_t* __restrict__ score
         count += __popcll(bal);
     }
     if (pass == 0 && lane == 0) row_count[y] = count;
-}
-
-__global__ void __launch_bounds__(256) k_fast_rows(const uint16_t* __restrict__ score, const uint8_t* __restrict__ mask,
-                                                   int w, int h, int pass, int* __restrict__ row_count,
-                                                   const int* __restrict__ row_off, int max_kp,
-                                                   float* __restrict__ xy, float* __restrict__ resp) {
-    fast_rows_row(score, mask, w, h, pass, row_count, row_off, max_kp, xy, resp, blockIdx.x * 4 + (threadIdx.x >> 6),
-                  threadIdx.x & 63);
 }
 
 // The per-set work areas of mfe_fast_grid_sets, set s at s times the single call's
@@ -363,7 +341,7 @@ constexpr int LK_SLOTS = 4;   // window pixels per lane: win <= 16 (win^2 <= 256
 // One point on one wavefront (every lane calls it with the same arguments):
 // (nx, ny) is nextPts[ptidx], the initial guess on entry and the tracked
 // position on exit, the same in every lane; returns the status.  Shared by
-// k_lk and k_stereo_match.
+// k_lk_sets, k_stereo_match_sets and the k_trk_* kernels.
 __device__ __forceinline__ bool lk_point(const Pyr& P, const Pyr& N, float ppx, float ppy, float& nx, float& ny,
                                          int win, int max_level, int max_iter, double eps, int lane) {
 #pragma clang fp contract(off)
@@ -463,20 +441,6 @@ __device__ __forceinline__ bool lk_point(const Pyr& P, const Pyr& N, float ppx, 
     return st;
 }
 
-__global__ void __launch_bounds__(64) k_lk(Pyr P, Pyr N, int n, const float* __restrict__ prev_pts,
-                                           float* __restrict__ next_pts, uint8_t* __restrict__ status, int win,
-                                           int max_level, int max_iter, double eps) {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= n) return;
-    float nx = next_pts[2 * i], ny = next_pts[2 * i + 1];
-    const bool st = lk_point(P, N, prev_pts[2 * i], prev_pts[2 * i + 1], nx, ny, win, max_level, max_iter, eps, lane);
-    if (lane == 0) {
-        next_pts[2 * i] = nx;
-        next_pts[2 * i + 1] = ny;
-        status[i] = st ? 1 : 0;
-    }
-}
-
 // mfe_lk_sets: the per-point set index is the same in every lane of the
 // wavefront, so the descriptors come through scalar loads
 struct LkSetsArgs {
@@ -513,7 +477,7 @@ struct CamModel {
 };
 
 // Pixel -> normalised, undistorted coordinates (before any rectification);
-// false = the fisheye solution was rejected.  Shared by k_undistort and
+// false = the fisheye solution was rejected.  Shared by k_undistort_sets and
 // k_two_point_ransac.
 __device__ __forceinline__ bool undistort_norm(const CamModel& c, double px, double py, double& xo, double& yo) {
 #pragma clang fp contract(off)
@@ -560,7 +524,7 @@ __device__ __forceinline__ bool undistort_norm(const CamModel& c, double px, dou
 
 // mfe_undistort of one point: undistort_norm, the rectification c.R and the new
 // intrinsics; a rejected fisheye solution goes out as (-1e6, -1e6), unrectified.
-// Shared by k_undistort and k_stereo_match.
+// Shared by k_undistort_sets and k_stereo_match_sets.
 __device__ __forceinline__ void undistort_rect(const CamModel& c, double px, double py, double& xo, double& yo) {
 #pragma clang fp contract(off)
     double x, y;
@@ -576,7 +540,7 @@ __device__ __forceinline__ void undistort_rect(const CamModel& c, double px, dou
     yo = c.nfy * Y / Wz + c.ncy;
 }
 
-// mfe_distort of one normalised point.  Shared by k_distort and k_stereo_match.
+// mfe_distort of one normalised point.  Shared by k_distort and k_stereo_match_sets.
 __device__ __forceinline__ void distort_pix(const CamModel& c, double x, double y, double& xo, double& yo) {
 #pragma clang fp contract(off)
     double xd, yd;
@@ -596,16 +560,6 @@ __device__ __forceinline__ void distort_pix(const CamModel& c, double x, double 
     }
     xo = c.fx * xd + c.cx;
     yo = c.fy * yd + c.cy;
-}
-
-__global__ void __launch_bounds__(256) k_undistort(CamModel c, int n, const double* __restrict__ in,
-                                                   double* __restrict__ out) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
-    double x, y;
-    undistort_rect(c, in[2 * t], in[2 * t + 1], x, y);
-    out[2 * t] = x;
-    out[2 * t + 1] = y;
 }
 
 // mfe_undistort_sets: point t with the model of its set
@@ -849,18 +803,8 @@ __global__ void __launch_bounds__(RS_THREADS) k_two_point_ransac(RansacArgs a) {
 // include/msckf_pipeline.h states the algorithm: ImageProcessor.stereo_match
 // as one kernel, one wavefront per point.  Every lane computes the same fp64
 // camera arithmetic; the two LK runs spread their windows over the lanes.
-struct StereoArgs {
-    CamModel cam0, cam1;   // cam0.R = R_guess; both with new intrinsics [1 1 0 0]
-    double E[9];
-    double eps, epi_thr;   // epi_thr = stereo_threshold * norm_pixel_unit
-    const double* pts;
-    float* cam1_pts;
-    uint8_t *inlier, *reason;
-    int n, win, max_level, max_iter;
-};
-
 // One point on one wavefront: steps 1-4 of the header; (c1x, c1y) is cam1_pts[i],
-// the return value reason[i].  Shared by k_stereo_match and k_stereo_match_sets.
+// the return value reason[i].  Shared by k_stereo_match_sets and k_trk_stereo*.
 __device__ __forceinline__ int stereo_point(const Pyr& P0, const Pyr& P1, const CamModel& cam0, const CamModel& cam1,
                                             const double* E, double epi_thr, double eps, int win, int max_level,
                                             int max_iter, double px, double py, int lane, float& c1x, float& c1y) {
@@ -897,22 +841,8 @@ __device__ __forceinline__ int stereo_point(const Pyr& P0, const Pyr& P1, const 
     return reason;
 }
 
-__global__ void __launch_bounds__(64) k_stereo_match(Pyr P0, Pyr P1, StereoArgs a) {
-    const int i = blockIdx.x, lane = threadIdx.x;
-    if (i >= a.n) return;
-    float c1x, c1y;
-    const int reason = stereo_point(P0, P1, a.cam0, a.cam1, a.E, a.epi_thr, a.eps, a.win, a.max_level, a.max_iter,
-                                    a.pts[2 * i], a.pts[2 * i + 1], lane, c1x, c1y);
-    if (lane == 0) {
-        a.cam1_pts[2 * i] = c1x;
-        a.cam1_pts[2 * i + 1] = c1y;
-        a.inlier[i] = reason == 0 ? 1 : 0;
-        a.reason[i] = (uint8_t)reason;
-    }
-}
-
 // mfe_stereo_match_sets: one table entry per set (cam0.R = R_guess, both cameras
-// with new intrinsics [1 1 0 0], as StereoArgs), read by every lane of the point's
+// with new intrinsics [1 1 0 0]), read by every lane of the point's
 // wavefront at the same address
 struct StereoSet {
     CamModel cam0, cam1;
@@ -947,7 +877,7 @@ __global__ void __launch_bounds__(64) k_stereo_match_sets(StereoSetsArgs a) {
 }
 
 // ---------------------------------------------------- grid-selected detection --
-// include/msckf_pipeline.h states the stages.  k_mask_clear: 7 threads per
+// include/msckf_pipeline.h states the stages.  k_mask_clear_sets: 7 threads per
 // occupied point, one per row of its 7 x 7 block (threads of overlapping blocks
 // store the same 0).
 __device__ __forceinline__ void mask_clear_row(float px, float py, int r, uint8_t* __restrict__ mask, int w, int h) {
@@ -956,14 +886,6 @@ __device__ __forceinline__ void mask_clear_row(float px, float py, int r, uint8_
     if (yy >= h) return;
     const int x1 = min(x + 3, w - 1);
     for (int xx = x - 3; xx <= x1; ++xx) mask[(size_t)yy * w + xx] = 0;
-}
-
-__global__ void __launch_bounds__(256) k_mask_clear(const float* __restrict__ occ, int n_occ,
-                                                    uint8_t* __restrict__ mask, int w, int h) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    const int p = t / 7, r = t - 7 * p;
-    if (p >= n_occ) return;
-    mask_clear_row(occ[2 * p], occ[2 * p + 1], r, mask, w, h);
 }
 
 // the occupied points of all sets, each in the mask of its set (occ_set[p])
@@ -993,12 +915,6 @@ __device__ __forceinline__ void row_scan_block(const int* __restrict__ cnt, int*
         base += cnt[r];
     }
     if (tid == 255) *total = base;
-}
-
-__global__ void __launch_bounds__(256) k_row_scan(const int* __restrict__ cnt, int* __restrict__ off, int h,
-                                                  int* __restrict__ total) {
-    __shared__ int s_part[256];
-    row_scan_block(cnt, off, h, total, s_part);
 }
 
 // blockIdx.x = the set
@@ -1068,12 +984,6 @@ __device__ __forceinline__ void grid_select_cell(const GridArgs& a, int cell, lo
         }
         prev = best;
     }
-}
-
-__global__ void __launch_bounds__(256) k_grid_select(GridArgs a) {
-    __shared__ long long s_key[4];
-    __shared__ int s_cnt[4];
-    grid_select_cell(a, blockIdx.x, s_key, s_cnt);
 }
 
 // blockIdx.y = the set; a holds set 0's pointers, the outputs [n_sets][cells k]
@@ -1460,25 +1370,20 @@ struct mfe_ctx {
     hipStream_t stream = nullptr;
     std::vector<Pyr> slots;
     std::vector<void*> allocs;
-    uint16_t* score = nullptr;
-    uint8_t* mask = nullptr;
-    int* rows = nullptr;   // [2][H]: counts, offsets
-    float* kp = nullptr;   // [max_kp][3]
-    int kp_cap = 0;
-    float* pts = nullptr;  // [2][max_points][2]
-    uint8_t* st = nullptr;
-    double* dpts = nullptr;   // [2][max_points][2]
-    // mfe_two_point_ransac, mfe_stereo_match, mfe_fast_grid: one device block (inputs |
-    // work | outputs) and one pinned host block (inputs | outputs), grown to the largest
-    // call seen
+    int kp_cap = 0;           // rows of a set's raster keypoint list
+    double* dpts = nullptr;   // mfe_distort: [2][max_points][2]
+    // every other call with points: one device block and one pinned host block of the same
+    // layout (inputs | work | outputs), grown to the largest call seen
     unsigned char* rs_dev = nullptr;
     unsigned char* rs_host = nullptr;
-    size_t rs_dev_cap = 0, rs_host_cap = 0;
-    // the set calls (msckf_lanes.h): the slots' Pyr descriptors on the device, written by the
-    // first set call, and the per-set work areas of mfe_fast_grid_sets for lanes_cap sets
+    size_t rs_cap = 0;
+    // what the kernels read their sets from: the slots' Pyr descriptors and the slot
+    // numbers 0 .. nslot - 1 on the device (d_slot + s is the slot list of the one image s),
+    // and the detection's work areas for work_cap sets (one from mfe_create on)
     Pyr* d_pyr = nullptr;
-    GridWork lanes{};
-    int lanes_cap = 0;
+    int32_t* d_slot = nullptr;
+    GridWork work{};
+    int work_cap = 0;
     // the track tables (msckf_tracks.h), one block of the context's allocations; the host's
     // record of each lane's current table and its row count
     TrkDev trk{};
@@ -1498,56 +1403,40 @@ int check_n(mfe_ctx* c, int n) {
     return 0;
 }
 
-int grow_scratch(mfe_ctx* c, size_t dev_bytes, size_t host_bytes) {
-    if (dev_bytes > c->rs_dev_cap) {   // nothing is in flight: every call ends with a synchronisation
-        if (c->rs_dev) (void)hipFree(c->rs_dev);
-        c->rs_dev = nullptr;
-        c->rs_dev_cap = 0;
-        MFE_HIP(hipMalloc((void**)&c->rs_dev, dev_bytes));
-        c->rs_dev_cap = dev_bytes;
-    }
-    if (host_bytes > c->rs_host_cap) {
-        if (c->rs_host) (void)hipHostFree(c->rs_host);
-        c->rs_host = nullptr;
-        c->rs_host_cap = 0;
-        MFE_HIP(hipHostMalloc((void**)&c->rs_host, host_bytes, hipHostMallocDefault));
-        c->rs_host_cap = host_bytes;
-    }
+int grow_scratch(mfe_ctx* c, size_t bytes) {
+    if (bytes <= c->rs_cap) return 0;   // nothing is in flight: every call ends with a synchronisation
+    if (c->rs_dev) (void)hipFree(c->rs_dev);
+    if (c->rs_host) (void)hipHostFree(c->rs_host);
+    c->rs_dev = c->rs_host = nullptr;
+    c->rs_cap = 0;
+    MFE_HIP(hipMalloc((void**)&c->rs_dev, bytes));
+    MFE_HIP(hipHostMalloc((void**)&c->rs_host, bytes, hipHostMallocDefault));
+    c->rs_cap = bytes;
     return 0;
 }
 
 void free_grid_work(mfe_ctx* c) {
-    if (c->lanes.score) (void)hipFree(c->lanes.score);
-    if (c->lanes.mask) (void)hipFree(c->lanes.mask);
-    if (c->lanes.rows) (void)hipFree(c->lanes.rows);
-    if (c->lanes.kp) (void)hipFree(c->lanes.kp);
-    c->lanes = GridWork{};
-    c->lanes_cap = 0;
+    if (c->work.score) (void)hipFree(c->work.score);
+    if (c->work.mask) (void)hipFree(c->work.mask);
+    if (c->work.rows) (void)hipFree(c->work.rows);
+    if (c->work.kp) (void)hipFree(c->work.kp);
+    c->work = GridWork{};
+    c->work_cap = 0;
 }
 
-// the work areas of mfe_fast_grid_sets for n_sets sets (nothing is in flight: every call
-// ends with a synchronisation)
+// the detection's work areas for n_sets sets; their contents do not outlive a call (nothing
+// is in flight: every call ends with a synchronisation)
 int grow_grid_work(mfe_ctx* c, int n_sets) {
-    if (n_sets <= c->lanes_cap) return 0;
+    if (n_sets <= c->work_cap) return 0;
     free_grid_work(c);
     const size_t S = (size_t)n_sets, px = (size_t)c->W * c->H;
-    GridWork& g = c->lanes;
+    GridWork& g = c->work;
     MFE_HIP(hipMalloc((void**)&g.score, S * px * 2));
     MFE_HIP(hipMalloc((void**)&g.mask, S * px));
     MFE_HIP(hipMalloc((void**)&g.rows, S * 2 * c->H * sizeof(int)));
     MFE_HIP(hipMalloc((void**)&g.kp, S * 3 * c->kp_cap * sizeof(float)));
     g.w = c->W; g.h = c->H; g.kp_cap = c->kp_cap;
-    c->lanes_cap = n_sets;
-    return 0;
-}
-
-// the first set call of a context writes the slots' descriptors to the device
-int ensure_pyr_table(mfe_ctx* c) {
-    if (c->d_pyr) return 0;
-    void* p;
-    if (int rc = dev_alloc(c, &p, c->slots.size() * sizeof(Pyr))) return rc;
-    MFE_HIP(hipMemcpy(p, c->slots.data(), c->slots.size() * sizeof(Pyr), hipMemcpyHostToDevice));
-    c->d_pyr = (Pyr*)p;
+    c->work_cap = n_sets;
     return 0;
 }
 
@@ -1649,20 +1538,19 @@ int mfe_create(int hip_device, int width, int height, int nslot, int max_level, 
             h = (h + 1) / 2;
         }
     }
-    void* p;
-    if (dev_alloc(c, &p, (size_t)width * height * 2)) return fail(-2);
-    c->score = (uint16_t*)p;
-    if (dev_alloc(c, &p, (size_t)width * height)) return fail(-2);
-    c->mask = (uint8_t*)p;
-    if (dev_alloc(c, &p, 2 * (size_t)height * sizeof(int))) return fail(-2);
-    c->rows = (int*)p;
+    std::vector<int32_t> ident(nslot);
+    for (int s = 0; s < nslot; ++s) ident[s] = s;
+    void *p, *q;
+    if (dev_alloc(c, &p, nslot * sizeof(Pyr)) || dev_alloc(c, &q, nslot * sizeof(int32_t)) ||
+        hipMemcpy(p, c->slots.data(), nslot * sizeof(Pyr), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(q, ident.data(), nslot * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        set_err("writing the slot tables failed");
+        return fail(-2);
+    }
+    c->d_pyr = (Pyr*)p;
+    c->d_slot = (int32_t*)q;
     c->kp_cap = 1 << 16;
-    if (dev_alloc(c, &p, (size_t)c->kp_cap * 3 * sizeof(float))) return fail(-2);
-    c->kp = (float*)p;
-    if (dev_alloc(c, &p, 4 * (size_t)max_points * sizeof(float))) return fail(-2);
-    c->pts = (float*)p;
-    if (dev_alloc(c, &p, (size_t)max_points)) return fail(-2);
-    c->st = (uint8_t*)p;
+    if (grow_grid_work(c, 1)) return fail(-2);
     if (dev_alloc(c, &p, 4 * (size_t)max_points * sizeof(double))) return fail(-2);
     c->dpts = (double*)p;
     *out = c;
@@ -1682,59 +1570,69 @@ int mfe_destroy(mfe_ctx_t* c) {
     return 0;
 }
 
+// the pyramids and Scharr derivatives of the n images in the slots dslots (device) names
+static void launch_pyramids(mfe_ctx_t* c, const int32_t* dslots, int n) {
+    for (int l = 0; l <= c->max_level; ++l) {
+        const Level& L = c->slots[0].lv[l];
+        const dim3 grid((L.w + 15) / 16, (L.h + 15) / 16, n);
+        if (l > 0) hipLaunchKernelGGL(k_pyrdown_sets, grid, dim3(256), 0, c->stream, (const Pyr*)c->d_pyr, dslots, l);
+        hipLaunchKernelGGL(k_scharr_sets, grid, dim3(256), 0, c->stream, (const Pyr*)c->d_pyr, dslots, l);
+    }
+}
+
+// The detection stages up to the raster keypoint lists of n_sets sets, in the work areas:
+// the masks are the caller's; totals [n_sets] on the device.
+static void launch_detect(mfe_ctx_t* c, const int32_t* dslots, int n_sets, int threshold, int max_kp, int* totals) {
+    const GridWork& g = c->work;
+    hipStream_t s = c->stream;
+    hipLaunchKernelGGL(k_fast_sets, dim3((g.w + 15) / 16, (g.h + 15) / 16, n_sets), dim3(256), 0, s,
+                       (const Pyr*)c->d_pyr, dslots, threshold < 0 ? 0 : (threshold > 255 ? 255 : threshold), g.score);
+    hipLaunchKernelGGL(k_fast_rows_sets, dim3((g.h + 3) / 4, n_sets), dim3(256), 0, s, g, 0, 0);
+    hipLaunchKernelGGL(k_row_scan_sets, dim3(n_sets), dim3(256), 0, s, g, totals);
+    hipLaunchKernelGGL(k_fast_rows_sets, dim3((g.h + 3) / 4, n_sets), dim3(256), 0, s, g, 1, max_kp);
+}
+
+// The single-image calls: their own checks, then the set call with one set.
 int mfe_upload(mfe_ctx_t* c, int slot, const uint8_t* image) {
     if (!c || !image) MFE_FAIL(-1, "null argument");
-    if (slot < 0 || slot >= c->nslot) MFE_FAIL(-1, "slot %d outside [0, %d)", slot, c->nslot);
+    const int32_t sl = slot;
+    if (check_slots(c, 1, &sl, "slot")) return -1;
     MFE_HIP(hipSetDevice(c->device));
-    Pyr& P = c->slots[slot];
-    hipStream_t s = c->stream;
-    MFE_HIP(hipMemcpyAsync(P.lv[0].img, image, (size_t)c->W * c->H, hipMemcpyHostToDevice, s));
-    for (int l = 0; l <= c->max_level; ++l) {
-        const Level& L = P.lv[l];
-        if (l > 0) {
-            const Level& U = P.lv[l - 1];
-            hipLaunchKernelGGL(k_pyrdown, dim3((L.w + 15) / 16, (L.h + 15) / 16), dim3(256), 0, s, U.img, U.w, U.h,
-                               L.img, L.w, L.h);
-        }
-        hipLaunchKernelGGL(k_scharr, dim3((L.w + 15) / 16, (L.h + 15) / 16), dim3(256), 0, s, L.img, L.w, L.h, L.ix,
-                           L.iy);
-    }
+    // straight into level 0 of the slot: one image needs no packing and no scatter
+    MFE_HIP(hipMemcpyAsync(c->slots[slot].lv[0].img, image, (size_t)c->W * c->H, hipMemcpyHostToDevice, c->stream));
+    launch_pyramids(c, c->d_slot + slot, 1);
     MFE_HIP(hipGetLastError());
-    MFE_HIP(hipStreamSynchronize(s));
+    MFE_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 
 int mfe_fast(mfe_ctx_t* c, int slot, int threshold, const uint8_t* mask, int max_kp, float* xy_out,
              float* response_out, int* n_out) {
     if (!c || !n_out) MFE_FAIL(-1, "null argument");
-    if (slot < 0 || slot >= c->nslot) MFE_FAIL(-1, "slot %d outside [0, %d)", slot, c->nslot);
+    const int32_t sl = slot;
+    if (check_slots(c, 1, &sl, "slot")) return -1;
     if (max_kp < 0 || (max_kp > 0 && (!xy_out || !response_out))) MFE_FAIL(-1, "bad keypoint output");
     MFE_HIP(hipSetDevice(c->device));
-    threshold = threshold < 0 ? 0 : (threshold > 255 ? 255 : threshold);
-    const Level& L = c->slots[slot].lv[0];
+    if (int rc = grow_scratch(c, 16)) return rc;
     hipStream_t s = c->stream;
-    const int W = L.w, H = L.h;
-    if (mask) MFE_HIP(hipMemcpyAsync(c->mask, mask, (size_t)W * H, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_fast, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, s, L.img, W, H, threshold, c->score);
-    hipLaunchKernelGGL(k_fast_rows, dim3((H + 3) / 4), dim3(256), 0, s, c->score, mask ? c->mask : nullptr, W, H, 0,
-                       c->rows, (const int*)nullptr, 0, (float*)nullptr, (float*)nullptr);
-    std::vector<int> cnt(H), off(H);
-    MFE_HIP(hipMemcpyAsync(cnt.data(), c->rows, H * sizeof(int), hipMemcpyDeviceToHost, s));
-    MFE_HIP(hipStreamSynchronize(s));
-    int tot = 0;
-    for (int y = 0; y < H; ++y) { off[y] = tot; tot += cnt[y]; }
-    *n_out = tot;
-    const int nw = std::min(std::min(tot, max_kp), c->kp_cap);
-    if (nw > 0) {
-        MFE_HIP(hipMemcpyAsync(c->rows + H, off.data(), H * sizeof(int), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_fast_rows, dim3((H + 3) / 4), dim3(256), 0, s, c->score, mask ? c->mask : nullptr, W, H, 1,
-                           c->rows, (const int*)(c->rows + H), nw, c->kp, c->kp + 2 * (size_t)c->kp_cap);
-        MFE_HIP(hipMemcpyAsync(xy_out, c->kp, 2 * (size_t)nw * sizeof(float), hipMemcpyDeviceToHost, s));
-        MFE_HIP(hipMemcpyAsync(response_out, c->kp + 2 * (size_t)c->kp_cap, (size_t)nw * sizeof(float),
-                               hipMemcpyDeviceToHost, s));
-    }
+    const GridWork& g = c->work;   // set 0
+    const size_t px = (size_t)g.w * g.h;
+    // the mask of set 0 holds what the last detection left: all ones unless the caller has one
+    if (mask) MFE_HIP(hipMemcpyAsync(g.mask, mask, px, hipMemcpyHostToDevice, s));
+    else MFE_HIP(hipMemsetAsync(g.mask, 1, px, s));
+    const int cap = std::min(max_kp, g.kp_cap);
+    launch_detect(c, c->d_slot + slot, 1, threshold, cap, (int*)c->rs_dev);
     MFE_HIP(hipGetLastError());
+    MFE_HIP(hipMemcpyAsync(c->rs_host, c->rs_dev, sizeof(int), hipMemcpyDeviceToHost, s));
     MFE_HIP(hipStreamSynchronize(s));
+    const int tot = *(const int*)c->rs_host, nw = std::min(tot, cap);
+    *n_out = tot;
+    if (nw > 0) {
+        MFE_HIP(hipMemcpyAsync(xy_out, g.kp, 2 * (size_t)nw * sizeof(float), hipMemcpyDeviceToHost, s));
+        MFE_HIP(hipMemcpyAsync(response_out, g.kp + 2 * (size_t)g.kp_cap, (size_t)nw * sizeof(float),
+                               hipMemcpyDeviceToHost, s));
+        MFE_HIP(hipStreamSynchronize(s));
+    }
     return 0;
 }
 
@@ -1743,55 +1641,42 @@ int mfe_lk(mfe_ctx_t* c, int slot_prev, int slot_next, int n, const float* prev_
     if (!c) MFE_FAIL(-1, "null context");
     if (check_n(c, n)) return -1;
     if (n == 0) return 0;
-    if (!prev_pts || !next_pts || !status) MFE_FAIL(-1, "null point array");
-    if (slot_prev < 0 || slot_prev >= c->nslot || slot_next < 0 || slot_next >= c->nslot) MFE_FAIL(-1, "bad slot");
-    if (win < 3 || win * win > 64 * LK_SLOTS) MFE_FAIL(-1, "window %d outside [3, 16]", win);
-    if (max_level < 0 || max_level > c->max_level) MFE_FAIL(-1, "max_level %d outside [0, %d]", max_level, c->max_level);
-    if (max_iter < 1) MFE_FAIL(-1, "max_iter must be positive");
-    MFE_HIP(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    float* dprev = c->pts;
-    float* dnext = c->pts + 2 * (size_t)c->max_points;
-    MFE_HIP(hipMemcpyAsync(dprev, prev_pts, 2 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-    MFE_HIP(hipMemcpyAsync(dnext, next_pts, 2 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_lk, dim3(n), dim3(64), 0, s, c->slots[slot_prev], c->slots[slot_next], n, dprev, dnext, c->st,
-                       win, max_level, max_iter, eps);
-    MFE_HIP(hipGetLastError());
-    MFE_HIP(hipMemcpyAsync(next_pts, dnext, 2 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
-    MFE_HIP(hipMemcpyAsync(status, c->st, (size_t)n, hipMemcpyDeviceToHost, s));
-    MFE_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-
-static int cam_call(mfe_ctx_t* c, int n, const double* in, double* out, const CamModel& m, bool undist) {
-    if (!c) MFE_FAIL(-1, "null context");
-    if (check_n(c, n)) return -1;
-    if (n == 0) return 0;
-    if (!in || !out) MFE_FAIL(-1, "null point array");
-    if (m.model != MFE_RADTAN && m.model != MFE_EQUIDISTANT) MFE_FAIL(-1, "unknown distortion model %d", m.model);
-    MFE_HIP(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    double* din = c->dpts;
-    double* dout = c->dpts + 2 * (size_t)c->max_points;
-    MFE_HIP(hipMemcpyAsync(din, in, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-    if (undist) hipLaunchKernelGGL(k_undistort, dim3((n + 255) / 256), dim3(256), 0, s, m, n, din, dout);
-    else hipLaunchKernelGGL(k_distort, dim3((n + 255) / 256), dim3(256), 0, s, m, n, din, dout);
-    MFE_HIP(hipGetLastError());
-    MFE_HIP(hipMemcpyAsync(out, dout, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    MFE_HIP(hipStreamSynchronize(s));
-    return 0;
+    const int32_t off[2] = {0, n}, sp = slot_prev, sn = slot_next;
+    return mfe_lk_sets(c, 1, off, &sp, &sn, prev_pts, next_pts, status, win, max_level, max_iter, eps);
 }
 
 int mfe_undistort(mfe_ctx_t* c, int n, const double* pts_in, double* pts_out, const double* intrinsics, int model,
                   const double* coeffs, const double* R, const double* new_intrinsics) {
+    if (!c) MFE_FAIL(-1, "null context");
     if (!intrinsics) MFE_FAIL(-1, "null intrinsics");
-    return cam_call(c, n, pts_in, pts_out, make_model(intrinsics, model, coeffs, R, new_intrinsics), true);
+    if (check_n(c, n)) return -1;
+    if (n == 0) return 0;
+    static const double zero[4] = {0, 0, 0, 0}, eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, unit[4] = {1, 1, 0, 0};
+    const int32_t off[2] = {0, n}, m = model;
+    return mfe_undistort_sets(c, 1, off, pts_in, pts_out, intrinsics, &m, coeffs ? coeffs : zero, R ? R : eye,
+                              new_intrinsics ? new_intrinsics : unit);
 }
 
 int mfe_distort(mfe_ctx_t* c, int n, const double* pts_in, double* pts_out, const double* intrinsics, int model,
                 const double* coeffs) {
+    if (!c) MFE_FAIL(-1, "null context");
     if (!intrinsics) MFE_FAIL(-1, "null intrinsics");
-    return cam_call(c, n, pts_in, pts_out, make_model(intrinsics, model, coeffs, nullptr, nullptr), false);
+    if (check_n(c, n)) return -1;
+    if (n == 0) return 0;
+    if (!pts_in || !pts_out) MFE_FAIL(-1, "null point array");
+    const int32_t m = model;
+    if (check_models(1, &m, "model")) return -1;
+    MFE_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    double* din = c->dpts;
+    double* dout = c->dpts + 2 * (size_t)c->max_points;
+    MFE_HIP(hipMemcpyAsync(din, pts_in, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_distort, dim3((n + 255) / 256), dim3(256), 0, s,
+                       make_model(intrinsics, model, coeffs, nullptr, nullptr), n, din, dout);
+    MFE_HIP(hipGetLastError());
+    MFE_HIP(hipMemcpyAsync(pts_out, dout, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFE_HIP(hipStreamSynchronize(s));
+    return 0;
 }
 
 int mfe_two_point_ransac(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const double* pts_prev,
@@ -1814,29 +1699,26 @@ int mfe_two_point_ransac(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const
     if (!pts_prev || !pts_curr || !R_p_c || !intrinsics || !model || !coeffs || !draws || !inlier_out || !info_out)
         MFE_FAIL(-1, "null argument");
     if (n_hyp < 1 || n_hyp > MFE_RANSAC_MAX_HYP) MFE_FAIL(-1, "n_hyp %d outside [1, %d]", n_hyp, MFE_RANSAC_MAX_HYP);
-    for (int s = 0; s < n_sets; ++s)
-        if (model[s] != MFE_RADTAN && model[s] != MFE_EQUIDISTANT)
-            MFE_FAIL(-1, "unknown distortion model %d (set %d)", model[s], s);
+    if (check_models(n_sets, model, "model")) return -1;
     MFE_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    // byte offsets; the fp64 sections first, so that every section is aligned to its element
-    const size_t H = (size_t)n_hyp;
-    const size_t o_prev = 0, o_curr = o_prev + 16 * T, o_R = o_curr + 16 * T, o_intr = o_R + 72 * S,
-                 o_coef = o_intr + 32 * S, o_off = o_coef + 32 * S, o_model = o_off + 4 * (S + 1),
-                 o_draw = o_model + 4 * S, in_bytes = (o_draw + 8 * S * H + 7) & ~(size_t)7;
-    const size_t o_work = in_bytes, o_info = o_work + 32 * T, o_inl = o_info + 8 * MFE_RANSAC_INFO_LEN * S,
-                 out_bytes = 8 * MFE_RANSAC_INFO_LEN * S + T, dev_bytes = o_inl + T;
-    if (int rc = grow_scratch(c, dev_bytes, in_bytes + out_bytes)) return rc;
-    unsigned char *hin = c->rs_host, *hout = c->rs_host + in_bytes, *d = c->rs_dev;
-    memcpy(hin + o_prev, pts_prev, 16 * T);
-    memcpy(hin + o_curr, pts_curr, 16 * T);
-    memcpy(hin + o_R, R_p_c, 72 * S);
-    memcpy(hin + o_intr, intrinsics, 32 * S);
-    memcpy(hin + o_coef, coeffs, 32 * S);
-    memcpy(hin + o_off, set_off, 4 * (S + 1));
-    memcpy(hin + o_model, model, 4 * S);
-    memcpy(hin + o_draw, draws, 8 * S * H);
-    MFE_HIP(hipMemcpyAsync(d, hin, in_bytes, hipMemcpyHostToDevice, st));
+    // inputs | work | info, inlier: what comes back
+    const size_t H = (size_t)n_hyp, info_bytes = 8 * MFE_RANSAC_INFO_LEN * S;
+    Block b;
+    const size_t o_prev = b.add(16 * T), o_curr = b.add(16 * T), o_R = b.add(72 * S), o_intr = b.add(32 * S),
+                 o_coef = b.add(32 * S), o_off = b.add(4 * (S + 1)), o_model = b.add(4 * S), o_draw = b.add(8 * S * H),
+                 in_bytes = b.size, o_work = b.add(32 * T), o_info = b.add(info_bytes), o_inl = b.add(T);
+    if (int rc = grow_scratch(c, b.size)) return rc;
+    unsigned char *h = c->rs_host, *d = c->rs_dev;
+    memcpy(h + o_prev, pts_prev, 16 * T);
+    memcpy(h + o_curr, pts_curr, 16 * T);
+    memcpy(h + o_R, R_p_c, 72 * S);
+    memcpy(h + o_intr, intrinsics, 32 * S);
+    memcpy(h + o_coef, coeffs, 32 * S);
+    memcpy(h + o_off, set_off, 4 * (S + 1));
+    memcpy(h + o_model, model, 4 * S);
+    memcpy(h + o_draw, draws, 8 * S * H);
+    MFE_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, st));
     RansacArgs a;
     a.set_off = (const int32_t*)(d + o_off);
     a.pts_prev = (const double*)(d + o_prev);
@@ -1853,10 +1735,10 @@ int mfe_two_point_ransac(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const
     a.n_hyp = n_hyp;
     hipLaunchKernelGGL(k_two_point_ransac, dim3(n_sets), dim3(RS_THREADS), 0, st, a);
     MFE_HIP(hipGetLastError());
-    MFE_HIP(hipMemcpyAsync(hout, d + o_info, out_bytes, hipMemcpyDeviceToHost, st));
+    MFE_HIP(hipMemcpyAsync(h + o_info, d + o_info, b.size - o_info, hipMemcpyDeviceToHost, st));
     MFE_HIP(hipStreamSynchronize(st));
-    memcpy(info_out, hout, 8 * MFE_RANSAC_INFO_LEN * S);
-    memcpy(inlier_out, hout + 8 * MFE_RANSAC_INFO_LEN * S, T);
+    memcpy(info_out, h + o_info, info_bytes);
+    memcpy(inlier_out, h + o_inl, T);
     return 0;
 }
 
@@ -1868,108 +1750,17 @@ int mfe_stereo_match(mfe_ctx_t* c, int slot_cam0, int slot_cam1, int n, const do
     if (!c) MFE_FAIL(-1, "null context");
     if (check_n(c, n)) return -1;
     if (n == 0) return 0;
-    if (!cam0_pts || !cam1_pts || !inlier || !reason) MFE_FAIL(-1, "null point array");
-    if (!intrinsics0 || !coeffs0 || !intrinsics1 || !coeffs1 || !R_guess || !E) MFE_FAIL(-1, "null camera argument");
-    if ((model0 != MFE_RADTAN && model0 != MFE_EQUIDISTANT) || (model1 != MFE_RADTAN && model1 != MFE_EQUIDISTANT))
-        MFE_FAIL(-1, "unknown distortion model %d / %d", model0, model1);
-    if (slot_cam0 < 0 || slot_cam0 >= c->nslot || slot_cam1 < 0 || slot_cam1 >= c->nslot) MFE_FAIL(-1, "bad slot");
-    if (win < 3 || win * win > 64 * LK_SLOTS) MFE_FAIL(-1, "window %d outside [3, 16]", win);
-    if (max_level < 0 || max_level > c->max_level) MFE_FAIL(-1, "max_level %d outside [0, %d]", max_level, c->max_level);
-    if (max_iter < 1) MFE_FAIL(-1, "max_iter must be positive");
-    MFE_HIP(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const size_t N = (size_t)n, in_bytes = 16 * N, o_c1 = in_bytes, o_inl = o_c1 + 8 * N, o_rsn = o_inl + N,
-                 out_bytes = 10 * N;
-    if (int rc = grow_scratch(c, in_bytes + out_bytes, in_bytes + out_bytes)) return rc;
-    unsigned char *hin = c->rs_host, *hout = c->rs_host + in_bytes, *d = c->rs_dev;
-    memcpy(hin, cam0_pts, in_bytes);
-    MFE_HIP(hipMemcpyAsync(d, hin, in_bytes, hipMemcpyHostToDevice, s));
-    StereoArgs a;
-    a.cam0 = make_model(intrinsics0, model0, coeffs0, R_guess, nullptr);
-    a.cam1 = make_model(intrinsics1, model1, coeffs1, nullptr, nullptr);
-    for (int i = 0; i < 9; ++i) a.E[i] = E[i];
-    a.eps = eps;
-    a.epi_thr = stereo_threshold * (4.0 / (intrinsics0[0] + intrinsics0[1] + intrinsics1[0] + intrinsics1[1]));
-    a.pts = (const double*)d;
-    a.cam1_pts = (float*)(d + o_c1);
-    a.inlier = d + o_inl;
-    a.reason = d + o_rsn;
-    a.n = n; a.win = win; a.max_level = max_level; a.max_iter = max_iter;
-    hipLaunchKernelGGL(k_stereo_match, dim3(n), dim3(64), 0, s, c->slots[slot_cam0], c->slots[slot_cam1], a);
-    MFE_HIP(hipGetLastError());
-    MFE_HIP(hipMemcpyAsync(hout, d + o_c1, out_bytes, hipMemcpyDeviceToHost, s));
-    MFE_HIP(hipStreamSynchronize(s));
-    memcpy(cam1_pts, hout, 8 * N);
-    memcpy(inlier, hout + 8 * N, N);
-    memcpy(reason, hout + 9 * N, N);
-    return 0;
+    const int32_t off[2] = {0, n}, s0 = slot_cam0, s1 = slot_cam1, m0 = model0, m1 = model1;
+    return mfe_stereo_match_sets(c, 1, off, &s0, &s1, cam0_pts, intrinsics0, &m0, coeffs0, intrinsics1, &m1, coeffs1,
+                                 R_guess, E, &stereo_threshold, win, max_level, max_iter, eps, cam1_pts, inlier, reason);
 }
 
 int mfe_fast_grid(mfe_ctx_t* c, int slot, int threshold, int n_occ, const float* occupied, int grid_row,
                   int grid_col, int k, int max_kp, float* xy_out, float* response_out, int32_t* cell_count,
                   int* n_total) {
-    if (!c || !xy_out || !response_out || !cell_count || !n_total) MFE_FAIL(-1, "null argument");
-    if (slot < 0 || slot >= c->nslot) MFE_FAIL(-1, "slot %d outside [0, %d)", slot, c->nslot);
-    if (check_n(c, n_occ)) return -1;
-    if (n_occ > 0 && !occupied) MFE_FAIL(-1, "null occupied points");
-    if (c->W < 16 || c->H < 16) MFE_FAIL(-1, "image %dx%d is smaller than 16x16", c->W, c->H);
-    if (k < 1 || k > MFE_GRID_MAX_K) MFE_FAIL(-1, "k = %d outside [1, %d]", k, MFE_GRID_MAX_K);
-    if (grid_row < 1 || grid_col < 1 || (long long)grid_row * grid_col > MFE_GRID_MAX_CELLS)
-        MFE_FAIL(-1, "grid %dx%d outside [1, %d] cells", grid_row, grid_col, MFE_GRID_MAX_CELLS);
-    if (max_kp < 1 || max_kp > c->kp_cap) MFE_FAIL(-1, "max_kp = %d outside [1, %d]", max_kp, c->kp_cap);
-    MFE_HIP(hipSetDevice(c->device));
-    threshold = threshold < 0 ? 0 : (threshold > 255 ? 255 : threshold);
-    const Level& L = c->slots[slot].lv[0];
-    hipStream_t s = c->stream;
-    const int W = L.w, H = L.h;
-    const size_t cells = (size_t)grid_row * grid_col, K = (size_t)k;
-    // device block: occupied | total, pad | cell_count | response | xy; the part after occupied comes back
-    const size_t in_bytes = (8 * (size_t)n_occ + 15) & ~(size_t)15, o_cnt = 8, o_resp = o_cnt + 4 * cells,
-                 o_xy = o_resp + 4 * cells * K, out_bytes = o_xy + 8 * cells * K;
-    if (int rc = grow_scratch(c, in_bytes + out_bytes, in_bytes + out_bytes)) return rc;
-    unsigned char *hin = c->rs_host, *hout = c->rs_host + in_bytes, *d = c->rs_dev, *dout = c->rs_dev + in_bytes;
-    MFE_HIP(hipMemsetAsync(c->mask, 1, (size_t)W * H, s));
-    if (n_occ > 0) {
-        memcpy(hin, occupied, 8 * (size_t)n_occ);
-        MFE_HIP(hipMemcpyAsync(d, hin, 8 * (size_t)n_occ, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_mask_clear, dim3((7 * n_occ + 255) / 256), dim3(256), 0, s, (const float*)d, n_occ,
-                           c->mask, W, H);
-    }
-    float* kxy = c->kp;
-    float* kresp = c->kp + 2 * (size_t)c->kp_cap;
-    hipLaunchKernelGGL(k_fast, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, s, L.img, W, H, threshold, c->score);
-    hipLaunchKernelGGL(k_fast_rows, dim3((H + 3) / 4), dim3(256), 0, s, c->score, c->mask, W, H, 0, c->rows,
-                       (const int*)nullptr, 0, (float*)nullptr, (float*)nullptr);
-    hipLaunchKernelGGL(k_row_scan, dim3(1), dim3(256), 0, s, (const int*)c->rows, c->rows + H, H, (int*)dout);
-    hipLaunchKernelGGL(k_fast_rows, dim3((H + 3) / 4), dim3(256), 0, s, c->score, c->mask, W, H, 1, c->rows,
-                       (const int*)(c->rows + H), max_kp, kxy, kresp);
-    GridArgs a;
-    a.xy = kxy; a.resp = kresp; a.total = (const int*)dout;
-    a.out_xy = (float*)(dout + o_xy); a.out_resp = (float*)(dout + o_resp); a.cell_count = (int*)(dout + o_cnt);
-    a.cap = max_kp; a.gh = (H + grid_row - 1) / grid_row; a.gw = (W + grid_col - 1) / grid_col;
-    a.grid_col = grid_col; a.k = k;
-    hipLaunchKernelGGL(k_grid_select, dim3((unsigned)cells), dim3(256), 0, s, a);
-    MFE_HIP(hipGetLastError());
-    MFE_HIP(hipMemcpyAsync(hout, dout, out_bytes, hipMemcpyDeviceToHost, s));
-    MFE_HIP(hipStreamSynchronize(s));
-    int tot;
-    memcpy(&tot, hout, sizeof(int));
-    *n_total = tot;
-    if (tot > max_kp) MFE_FAIL(-3, "%d keypoints exceed the capacity of %d", tot, max_kp);
-    const int32_t* cnt = (const int32_t*)(hout + o_cnt);
-    const float* resp = (const float*)(hout + o_resp);
-    const float* xy = (const float*)(hout + o_xy);
-    size_t w = 0;
-    for (size_t cell = 0; cell < cells; ++cell) {
-        cell_count[cell] = cnt[cell];
-        const size_t kept = std::min((size_t)cnt[cell], K);
-        for (size_t r = 0; r < kept; ++r, ++w) {
-            xy_out[2 * w] = xy[2 * (cell * K + r)];
-            xy_out[2 * w + 1] = xy[2 * (cell * K + r) + 1];
-            response_out[w] = resp[cell * K + r];
-        }
-    }
-    return 0;
+    const int32_t off[2] = {0, n_occ}, sl = slot;
+    return mfe_fast_grid_sets(c, 1, &sl, off, occupied, threshold, grid_row, grid_col, k, max_kp, xy_out,
+                              response_out, cell_count, n_total);
 }
 
 // ------------------------------------------------- set calls (msckf_lanes.h) --
@@ -1981,12 +1772,11 @@ int mfe_upload_many(mfe_ctx_t* c, int n, const int32_t* slots, const uint8_t* im
         for (int j = 0; j < i; ++j)
             if (slots[i] == slots[j]) MFE_FAIL(-1, "slot %d is named twice (images %d and %d)", slots[i], j, i);
     MFE_HIP(hipSetDevice(c->device));
-    if (int rc = ensure_pyr_table(c)) return rc;
     hipStream_t s = c->stream;
     const size_t px = (size_t)c->W * c->H;
     Block b;
     const size_t o_slots = b.add(4 * (size_t)n), o_img = b.add(px * n);
-    if (int rc = grow_scratch(c, b.size, b.size)) return rc;
+    if (int rc = grow_scratch(c, b.size)) return rc;
     unsigned char *hin = c->rs_host, *d = c->rs_dev;
     memcpy(hin + o_slots, slots, 4 * (size_t)n);
     memcpy(hin + o_img, images, px * n);
@@ -1996,12 +1786,7 @@ int mfe_upload_many(mfe_ctx_t* c, int n, const int32_t* slots, const uint8_t* im
     const size_t items = vec ? px / 16 : px;
     hipLaunchKernelGGL(k_image_scatter_sets, dim3((unsigned)((items + 255) / 256), 1, n), dim3(256), 0, s,
                        (const Pyr*)c->d_pyr, dslots, (const uint8_t*)(d + o_img), px, vec);
-    for (int l = 0; l <= c->max_level; ++l) {
-        const Level& L = c->slots[0].lv[l];
-        const dim3 grid((L.w + 15) / 16, (L.h + 15) / 16, n);
-        if (l > 0) hipLaunchKernelGGL(k_pyrdown_sets, grid, dim3(256), 0, s, (const Pyr*)c->d_pyr, dslots, l);
-        hipLaunchKernelGGL(k_scharr_sets, grid, dim3(256), 0, s, (const Pyr*)c->d_pyr, dslots, l);
-    }
+    launch_pyramids(c, dslots, n);
     MFE_HIP(hipGetLastError());
     MFE_HIP(hipStreamSynchronize(s));
     return 0;
@@ -2020,13 +1805,12 @@ int mfe_lk_sets(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const int32_t*
     if (T == 0) return 0;
     if (!prev_pts || !next_pts || !status) MFE_FAIL(-1, "null point array");
     MFE_HIP(hipSetDevice(c->device));
-    if (int rc = ensure_pyr_table(c)) return rc;
     hipStream_t s = c->stream;
     // prev | pt_set | slots | next | status: next ends what goes in and starts what comes back
     Block b;
     const size_t o_prev = b.add(8 * T), o_set = b.add(4 * T), o_slots = b.add(8 * S), o_next = b.add(8 * T),
                  in_bytes = b.size, o_st = b.add(T), out_bytes = b.size - o_next;
-    if (int rc = grow_scratch(c, b.size, b.size)) return rc;
+    if (int rc = grow_scratch(c, b.size)) return rc;
     unsigned char *h = c->rs_host, *d = c->rs_dev;
     memcpy(h + o_prev, prev_pts, 8 * T);
     fill_pt_set((int32_t*)(h + o_set), n_sets, set_off);
@@ -2073,12 +1857,11 @@ int mfe_stereo_match_sets(mfe_ctx_t* c, int n_sets, const int32_t* set_off, cons
     if (T == 0) return 0;
     if (!cam0_pts || !cam1_pts || !inlier || !reason) MFE_FAIL(-1, "null point array");
     MFE_HIP(hipSetDevice(c->device));
-    if (int rc = ensure_pyr_table(c)) return rc;
     hipStream_t s = c->stream;
     Block b;
     const size_t o_pts = b.add(16 * T), o_tab = b.add(sizeof(StereoSet) * S), o_set = b.add(4 * T), in_bytes = b.size,
                  o_c1 = b.add(8 * T), o_inl = b.add(T), o_rsn = b.add(T), out_bytes = b.size - o_c1;
-    if (int rc = grow_scratch(c, b.size, b.size)) return rc;
+    if (int rc = grow_scratch(c, b.size)) return rc;
     unsigned char *h = c->rs_host, *d = c->rs_dev;
     memcpy(h + o_pts, cam0_pts, 16 * T);
     StereoSet* tab = (StereoSet*)(h + o_tab);
@@ -2129,9 +1912,7 @@ int mfe_fast_grid_sets(mfe_ctx_t* c, int n_sets, const int32_t* slots, const int
         MFE_FAIL(-1, "grid %dx%d outside [1, %d] cells", grid_row, grid_col, MFE_GRID_MAX_CELLS);
     if (max_kp < 1 || max_kp > c->kp_cap) MFE_FAIL(-1, "max_kp = %d outside [1, %d]", max_kp, c->kp_cap);
     MFE_HIP(hipSetDevice(c->device));
-    if (int rc = ensure_pyr_table(c)) return rc;
     if (int rc = grow_grid_work(c, n_sets)) return rc;
-    threshold = threshold < 0 ? 0 : (threshold > 255 ? 255 : threshold);
     hipStream_t s = c->stream;
     const int W = c->W, H = c->H;
     const size_t cells = (size_t)grid_row * grid_col, K = (size_t)k;
@@ -2139,23 +1920,18 @@ int mfe_fast_grid_sets(mfe_ctx_t* c, int n_sets, const int32_t* slots, const int
     const size_t o_occ = b.add(8 * T), o_oset = b.add(4 * T), o_slots = b.add(4 * S), in_bytes = b.size,
                  o_tot = b.add(4 * S), o_cnt = b.add(4 * S * cells), o_resp = b.add(4 * S * cells * K),
                  o_xy = b.add(8 * S * cells * K), out_bytes = b.size - o_tot;
-    if (int rc = grow_scratch(c, b.size, b.size)) return rc;
+    if (int rc = grow_scratch(c, b.size)) return rc;
     unsigned char *h = c->rs_host, *d = c->rs_dev;
     if (T > 0) memcpy(h + o_occ, occupied, 8 * T);
     fill_pt_set((int32_t*)(h + o_oset), n_sets, occ_off);
     memcpy(h + o_slots, slots, 4 * S);
     MFE_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
-    const GridWork& g = c->lanes;
-    const int32_t* dslots = (const int32_t*)(d + o_slots);
+    const GridWork& g = c->work;
     MFE_HIP(hipMemsetAsync(g.mask, 1, S * W * H, s));
     if (T > 0)
         hipLaunchKernelGGL(k_mask_clear_sets, dim3((unsigned)((7 * T + 255) / 256)), dim3(256), 0, s,
                            (const float*)(d + o_occ), (const int32_t*)(d + o_oset), (int)T, g.mask, W, H);
-    hipLaunchKernelGGL(k_fast_sets, dim3((W + 15) / 16, (H + 15) / 16, n_sets), dim3(256), 0, s, (const Pyr*)c->d_pyr,
-                       dslots, threshold, g.score);
-    hipLaunchKernelGGL(k_fast_rows_sets, dim3((H + 3) / 4, n_sets), dim3(256), 0, s, g, 0, 0);
-    hipLaunchKernelGGL(k_row_scan_sets, dim3(n_sets), dim3(256), 0, s, g, (int*)(d + o_tot));
-    hipLaunchKernelGGL(k_fast_rows_sets, dim3((H + 3) / 4, n_sets), dim3(256), 0, s, g, 1, max_kp);
+    launch_detect(c, (const int32_t*)(d + o_slots), n_sets, threshold, max_kp, (int*)(d + o_tot));
     GridArgs a;
     a.xy = g.kp; a.resp = g.kp + 2 * (size_t)g.kp_cap; a.total = (const int*)(d + o_tot);
     a.out_xy = (float*)(d + o_xy); a.out_resp = (float*)(d + o_resp); a.cell_count = (int*)(d + o_cnt);
@@ -2207,7 +1983,7 @@ int mfe_undistort_sets(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const d
     Block b;
     const size_t o_pts = b.add(16 * T), o_tab = b.add(sizeof(CamModel) * S), o_set = b.add(4 * T), in_bytes = b.size,
                  o_out = b.add(16 * T);
-    if (int rc = grow_scratch(c, b.size, b.size)) return rc;
+    if (int rc = grow_scratch(c, b.size)) return rc;
     unsigned char *h = c->rs_host, *d = c->rs_dev;
     memcpy(h + o_pts, pts_in, 16 * T);
     CamModel* tab = (CamModel*)(h + o_tab);
@@ -2367,9 +2143,7 @@ int mfe_tracks_step(mfe_ctx_t* c, int n_lanes, const int32_t* lanes, const int32
     if (c->W < 16 || c->H < 16) MFE_FAIL(-1, "image %dx%d is smaller than 16x16", c->W, c->H);
     if (max_kp < 1 || max_kp > c->kp_cap) MFE_FAIL(-1, "max_kp = %d outside [1, %d]", max_kp, c->kp_cap);
     MFE_HIP(hipSetDevice(c->device));
-    if (int rc = ensure_pyr_table(c)) return rc;
     if (int rc = grow_grid_work(c, n_lanes)) return rc;
-    threshold = threshold < 0 ? 0 : (threshold > 255 ? 255 : threshold);
     hipStream_t s = c->stream;
     const int W = c->W, H = c->H;
     const size_t NL = (size_t)n_lanes, NR = (size_t)n_rs, C = (size_t)d.cap, HY = (size_t)(n_rs ? n_hyp : 0);
@@ -2379,7 +2153,7 @@ int mfe_tracks_step(mfe_ctx_t* c, int n_lanes, const int32_t* lanes, const int32
                  o_rsm = b.add(4 * 2 * NR), o_draw = b.add(8 * 2 * NR * HY), in_bytes = b.size,
                  o_n = b.add(4 * NL), o_ctr = b.add(16 * NL), o_tot = b.add(4 * NL), o_next = b.add(8 * NL),
                  o_ids = b.add(8 * NL * C), o_uv = b.add(32 * NL * C), out_bytes = b.size - o_n;
-    if (int rc = grow_scratch(c, b.size, b.size)) return rc;
+    if (int rc = grow_scratch(c, b.size)) return rc;
     unsigned char *h = c->rs_host, *dv = c->rs_dev;
     TrkLane* tl = (TrkLane*)(h + o_lanes);
     int32_t* rsl = (int32_t*)(h + o_rsl);
@@ -2444,15 +2218,10 @@ int mfe_tracks_step(mfe_ctx_t* c, int n_lanes, const int32_t* lanes, const int32
     hipLaunchKernelGGL(k_trk_rs_flag, per256, dim3(256), 0, s, d, dl);
     hipLaunchKernelGGL(k_trk_compact, dim3(n_lanes), dim3(TRK_THREADS), 0, s, d, dl, 2);
     // step 6: the stages of mfe_fast_grid_sets
-    const GridWork& g = c->lanes;
-    const int32_t* dslots = (const int32_t*)(dv + o_slots);
+    const GridWork& g = c->work;
     MFE_HIP(hipMemsetAsync(g.mask, 1, NL * W * H, s));
     hipLaunchKernelGGL(k_trk_mask_clear, dim3((7 * d.cap + 255) / 256, n_lanes), dim3(256), 0, s, d, g.mask, W, H);
-    hipLaunchKernelGGL(k_fast_sets, dim3((W + 15) / 16, (H + 15) / 16, n_lanes), dim3(256), 0, s, tab, dslots,
-                       threshold, g.score);
-    hipLaunchKernelGGL(k_fast_rows_sets, dim3((H + 3) / 4, n_lanes), dim3(256), 0, s, g, 0, 0);
-    hipLaunchKernelGGL(k_row_scan_sets, dim3(n_lanes), dim3(256), 0, s, g, o.n_total);
-    hipLaunchKernelGGL(k_fast_rows_sets, dim3((H + 3) / 4, n_lanes), dim3(256), 0, s, g, 1, max_kp);
+    launch_detect(c, (const int32_t*)(dv + o_slots), n_lanes, threshold, max_kp, o.n_total);
     GridArgs ga;
     ga.xy = g.kp; ga.resp = g.kp + 2 * (size_t)g.kp_cap; ga.total = o.n_total;
     ga.out_xy = d.g_xy; ga.out_resp = d.g_resp; ga.cell_count = d.g_cnt;

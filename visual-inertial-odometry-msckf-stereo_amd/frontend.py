@@ -7,14 +7,14 @@ published message -- and every image operator runs in the HIP kernels of
 ``csrc/msckf_frontend.hip`` behind ``include/msckf_frontend.h``:
 
   reference (cv2)                              here
-  FastFeatureDetector.detect (image.py:175,333) mfe_fast   (k_fast, k_fast_rows)
-  calcOpticalFlowPyrLK (image.py:254,581,585)   mfe_lk     (k_lk; pyramids + Scharr
+  FastFeatureDetector.detect (image.py:175,333) mfe_fast   (k_fast_sets, k_fast_rows_sets)
+  calcOpticalFlowPyrLK (image.py:254,581,585)   mfe_lk     (k_lk_sets; pyramids + Scharr
                                                             built by mfe_upload)
   undistortPoints / fisheye (image.py:640-674)  mfe_undistort
   projectPoints / fisheye (image.py:676-702)    mfe_distort
   RANSAC stub (image.py:292-293)                mfe_two_point_ransac (k_two_point_ransac,
                                                 include/msckf_ransac.h), opt-in
-  stereo_match (image.py:554-638)               mfe_stereo_match (k_stereo_match,
+  stereo_match (image.py:554-638)               mfe_stereo_match (k_stereo_match_sets,
                                                 include/msckf_pipeline.h), opt-in
   mask + detect + sieve (image.py:317-360)      mfe_fast_grid (include/msckf_pipeline.h), opt-in
   one stream per ImageProcessor                 MultiImageProcessor: S streams on one context,
@@ -642,22 +642,7 @@ class ImageProcessor:
 
     # ---- callbacks (image.py:95-147) ----
     def stareo_callback(self, stereo_msg):
-        if self.config.device_pipeline:
-            return self._drive(self._frame_steps(stereo_msg))
-        self.cam0_curr_img_msg = stereo_msg.cam0_msg
-        self.cam1_curr_img_msg = stereo_msg.cam1_msg
-        self.create_image_pyramids()
-        if self.is_first_img:
-            self.initialize_first_frame()
-            self.is_first_img = False
-        else:
-            self.track_features()
-            self.add_new_features()
-            self.prune_features()
-        try:
-            return self.publish()
-        finally:
-            self._end_frame()
+        return self._drive(self._frame_steps(stereo_msg))
 
     stereo_callback = stareo_callback
 
@@ -674,18 +659,11 @@ class ImageProcessor:
     def create_image_pyramids(self):
         """image.py:149-164 -- here the device builds the pyramids (and the
         Scharr derivatives LK needs) once per image."""
-        if self.config.device_pipeline:
-            return self._drive(self._upload_steps())
-        self.fe.upload(self._slot_c0, self.cam0_curr_img_msg.image)
-        self.fe.upload(self._slot_c1, self.cam1_curr_img_msg.image)
+        return self._drive(self._upload_steps())
 
     # ---- detection / tracking (image.py:166-404) ----
     def _grid_code(self, pt, gh, gw):
         return int(pt[1] / gh) * self.config.grid_col + int(pt[0] / gw)
-
-    def _collect_new(self, cam0_points, responses):
-        cam1_points, inliers = self.stereo_match(cam0_points)
-        self._assign_new(cam0_points, responses, cam1_points, inliers)
 
     def _assign_new(self, cam0_points, responses, cam1_points, inliers):
         gh, gw = self.get_grid_size(self.cam0_curr_img_msg.image)
@@ -707,103 +685,30 @@ class ImageProcessor:
 
     def initialize_first_frame(self):
         """image.py:166-217."""
-        if self.config.device_pipeline:
-            return self._drive(self._first_frame_steps())
-        xy, resp = self.fe.fast(self._slot_c0, self.config.fast_threshold)
-        self._collect_new([tuple(p) for p in xy], list(resp))
+        return self._drive(self._first_frame_steps())
 
     def track_features(self):
         """image.py:219-313."""
-        if self.config.device_pipeline:
-            return self._drive(self._track_steps())
-        img = self.cam0_curr_img_msg.image
-        gh, gw = self.get_grid_size(img)
-        cam0_R_p_c, cam1_R_p_c = self.integrate_imu_data()
-        if self.config.ransac_enabled:   # once per tracked frame, whatever the frame holds: a replay repeats
-            draws = self.ransac_rng.integers(0, 1 << 32, size=(2, self.ransac_n_hyp, 2), dtype=np.uint32)
-        prev_ids, prev_lifetime, prev_cam0_points, prev_cam1_points = [], [], [], []
-        for f in chain.from_iterable(self.prev_features):
-            prev_ids.append(f.id)
-            prev_lifetime.append(f.lifetime)
-            prev_cam0_points.append(f.cam0_point)
-            prev_cam1_points.append(f.cam1_point)
-        prev_cam0_points = np.array(prev_cam0_points, dtype=np.float32).reshape(-1, 2)
-        self.num_features["before_tracking"] = len(prev_cam0_points)
-        if len(prev_cam0_points) == 0:
-            return
-        curr_cam0_points = self.predict_feature_tracking(prev_cam0_points, cam0_R_p_c, self.cam0_intrinsics)
-        curr_cam0_points, track_inliers = self.fe.lk(self._slot_prev, self._slot_c0, prev_cam0_points,
-                                                     curr_cam0_points, **self.lk_kw)
-        track_inliers = track_inliers.astype(bool)
-        for i, p in enumerate(curr_cam0_points):
-            if not track_inliers[i]:
-                continue
-            if p[0] < 0 or p[0] > img.shape[1] - 1 or p[1] < 0 or p[1] > img.shape[0] - 1:
-                track_inliers[i] = False
-        prev_tracked_ids = _select(prev_ids, track_inliers)
-        prev_tracked_lifetime = _select(prev_lifetime, track_inliers)
-        curr_tracked_cam0_points = _select(curr_cam0_points, track_inliers)
-        self.num_features["after_tracking"] = len(curr_tracked_cam0_points)
-        curr_cam1_points, match_inliers = self.stereo_match(curr_tracked_cam0_points)
-        prev_matched_ids = _select(prev_tracked_ids, match_inliers)
-        prev_matched_lifetime = _select(prev_tracked_lifetime, match_inliers)
-        curr_matched_cam0_points = _select(curr_tracked_cam0_points, match_inliers)
-        curr_matched_cam1_points = _select(curr_cam1_points, match_inliers)
-        self.num_features["after_matching"] = len(curr_matched_cam0_points)
-        ransac_inliers = None
-        if self.config.ransac_enabled:
-            ransac_inliers = self.two_point_ransac(
-                _select(_select(prev_cam0_points, track_inliers), match_inliers), curr_matched_cam0_points,
-                _select(_select(prev_cam1_points, track_inliers), match_inliers), curr_matched_cam1_points,
-                cam0_R_p_c, cam1_R_p_c, draws)
-        after_ransac = 0
-        for i in range(len(curr_matched_cam0_points)):   # RANSAC stub: all inliers (image.py:292-293)
-            if ransac_inliers is not None and not ransac_inliers[i]:
-                continue
-            f = FeatureMetaData()
-            f.id = prev_matched_ids[i]
-            f.lifetime = prev_matched_lifetime[i] + 1
-            f.cam0_point = curr_matched_cam0_points[i]
-            f.cam1_point = curr_matched_cam1_points[i]
-            self.curr_features[self._grid_code(curr_matched_cam0_points[i], gh, gw)].append(f)
-            after_ransac += 1
-        self.num_features["after_ransac"] = after_ransac
+        return self._drive(self._track_steps())
 
     def two_point_ransac(self, prev_cam0, curr_cam0, prev_cam1, curr_cam1, cam0_R_p_c, cam1_R_p_c, draws):
         """The step the reference stubs (image.py:292-293), as in msckf_vio:
         the two-point RANSAC of cam0 prev -> curr and of cam1 prev -> curr, both
         in one device call; a feature stays only if it is an inlier of both."""
-        sets = self._ransac_sets(prev_cam0, curr_cam0, prev_cam1, curr_cam1, cam0_R_p_c, cam1_R_p_c)
-        fn = self.ransac_fn if self.ransac_fn is not None else self.fe.two_point_ransac
-        (in0, _), (in1, _) = fn(sets, self.config.ransac_threshold, self.ransac_n_hyp, draws)
-        return np.logical_and(in0, in1)
+        return self._drive(self._ransac_steps(prev_cam0, curr_cam0, prev_cam1, curr_cam1, cam0_R_p_c, cam1_R_p_c,
+                                              draws))
 
-    def _ransac_sets(self, prev_cam0, curr_cam0, prev_cam1, curr_cam1, cam0_R_p_c, cam1_R_p_c):
-        return [(prev_cam0, curr_cam0, cam0_R_p_c, self.cam0_intrinsics, _model(self.cam0_distortion_model),
+    def _ransac_steps(self, prev_cam0, curr_cam0, prev_cam1, curr_cam1, cam0_R_p_c, cam1_R_p_c, draws):
+        sets = [(prev_cam0, curr_cam0, cam0_R_p_c, self.cam0_intrinsics, _model(self.cam0_distortion_model),
                  self.cam0_distortion_coeffs),
                 (prev_cam1, curr_cam1, cam1_R_p_c, self.cam1_intrinsics, _model(self.cam1_distortion_model),
                  self.cam1_distortion_coeffs)]
+        (in0, _), (in1, _) = yield ("ransac", sets, self.config.ransac_threshold, self.ransac_n_hyp, draws)
+        return np.logical_and(in0, in1)
 
     def add_new_features(self):
         """image.py:317-390."""
-        if self.config.device_pipeline:
-            return self._drive(self._add_new_steps())
-        img = self.cam0_curr_img_msg.image
-        gh, gw = self.get_grid_size(img)
-        mask = np.ones(img.shape[:2], dtype=np.uint8)
-        for f in chain.from_iterable(self.curr_features):
-            x, y = map(int, f.cam0_point)
-            mask[y - 3:y + 4, x - 3:x + 4] = 0   # the reference's slice, negative starts included
-        xy, resp = self.fe.fast(self._slot_c0, self.config.fast_threshold, mask=mask)
-        sieve = [[] for _ in range(self.config.grid_num)]
-        for p, r in zip(xy, resp):
-            sieve[self._grid_code(p, gh, gw)].append((tuple(p), r))
-        picked = []
-        for feats in sieve:
-            if len(feats) > self.config.grid_max_feature_num:
-                feats = sorted(feats, key=lambda x: x[1], reverse=True)[:self.config.grid_max_feature_num]
-            picked.extend(feats)
-        self._collect_new([p for p, _ in picked], [r for _, r in picked])
+        return self._drive(self._add_new_steps())
 
     def prune_features(self):
         """image.py:392-404."""
@@ -815,17 +720,7 @@ class ImageProcessor:
 
     def publish(self):
         """image.py:406-438."""
-        if self.config.device_pipeline:
-            return self._drive(self._publish_steps())
-        ids, c0, c1 = [], [], []
-        for f in chain.from_iterable(self.curr_features):
-            ids.append(f.id)
-            c0.append(f.cam0_point)
-            c1.append(f.cam1_point)
-        u0 = self.undistort_points(c0, self.cam0_intrinsics, self.cam0_distortion_model, self.cam0_distortion_coeffs)
-        u1 = self.undistort_points(c1, self.cam1_intrinsics, self.cam1_distortion_model, self.cam1_distortion_coeffs)
-        feats = [FeatureMeasurement(ids[i], u0[i][0], u0[i][1], u1[i][0], u1[i][1]) for i in range(len(ids))]
-        return FeatureMsg(self.cam0_curr_img_msg.vio_timestamp__, feats)
+        return self._drive(self._publish_steps())
 
     # ---- geometry helpers (image.py:440-702) ----
     def integrate_imu_data(self):
@@ -858,22 +753,42 @@ class ImageProcessor:
         """image.py:521-552."""
         if len(input_pts) == 0:
             return np.zeros((0, 2), np.float32)
-        K = np.array([[intrinsics[0], 0.0, intrinsics[2]], [0.0, intrinsics[1], intrinsics[3]], [0.0, 0.0, 1.0]])
-        Hm = K @ R_p_c @ np.linalg.inv(K)
+        Hm = self._homography(R_p_c, intrinsics)
         p = np.concatenate([np.asarray(input_pts, float).reshape(-1, 2), np.ones((len(input_pts), 1))], 1)
         q = p @ Hm.T
         return (q[:, :2] / q[:, 2:3]).astype(np.float32)
+
+    @staticmethod
+    def _homography(R_p_c, intrinsics):
+        """K R K^-1 of predict_feature_tracking (image.py:535-541)."""
+        K = np.array([[intrinsics[0], 0.0, intrinsics[2]], [0.0, intrinsics[1], intrinsics[3]], [0.0, 0.0, 1.0]])
+        return K @ R_p_c @ np.linalg.inv(K)
+
+    def _stereo_extrinsics(self):
+        """(R_cam0_cam1, E) of stereo_match (image.py:561, 611-614)."""
+        R_cam0_cam1 = self.R_cam1_imu.T @ self.R_cam0_imu
+        t_cam0_cam1 = self.R_cam1_imu.T @ (self.t_cam0_imu - self.t_cam1_imu)
+        return R_cam0_cam1, _skew(t_cam0_cam1) @ R_cam0_cam1
 
     def stereo_match(self, cam0_points):
         """image.py:554-638: project into cam1 through the extrinsics, LK
         cam0 -> cam1 and back, and the vertical-disparity, round-trip and
         epipolar tests."""
+        return self._drive(self._match_steps(cam0_points))
+
+    def _match_steps(self, cam0_points):
+        """The stereo match of the tracked and of the new features: one request
+        with config.device_pipeline, otherwise composed on the spot from six
+        single calls (no request: the generator ends without yielding)."""
         if self.config.device_pipeline:
-            return self._drive(self._stereo_match_steps(cam0_points))
+            return (yield from self._stereo_match_steps(cam0_points))
+        return self._stereo_match_composed(cam0_points)
+
+    def _stereo_match_composed(self, cam0_points):
         cam0_points = np.asarray(cam0_points, float).reshape(-1, 2)
         if len(cam0_points) == 0:
             return [], []
-        R_cam0_cam1 = self.R_cam1_imu.T @ self.R_cam0_imu
+        R_cam0_cam1, E = self._stereo_extrinsics()
         und = self.undistort_points(cam0_points, self.cam0_intrinsics, self.cam0_distortion_model,
                                     self.cam0_distortion_coeffs, R_cam0_cam1)
         cam1_points = self.distort_points(und, self.cam1_intrinsics, self.cam1_distortion_model,
@@ -891,8 +806,6 @@ class ImageProcessor:
                 continue
             if p[0] < 0 or p[0] > img1.shape[1] - 1 or p[1] < 0 or p[1] > img1.shape[0] - 1:
                 inliers[i] = False
-        t_cam0_cam1 = self.R_cam1_imu.T @ (self.t_cam0_imu - self.t_cam1_imu)
-        E = _skew(t_cam0_cam1) @ R_cam0_cam1
         u0 = self.undistort_points(c0, self.cam0_intrinsics, self.cam0_distortion_model, self.cam0_distortion_coeffs)
         u1 = self.undistort_points(c1, self.cam1_intrinsics, self.cam1_distortion_model, self.cam1_distortion_coeffs)
         norm_pixel_unit = 4.0 / (self.cam0_intrinsics[0] + self.cam0_intrinsics[1] +
@@ -908,14 +821,17 @@ class ImageProcessor:
                 inliers[i] = False
         return [tuple(p) for p in c1], list(inliers)
 
-    # ---- the device pipeline as a generator of device requests ----
-    # With config.device_pipeline the frame logic is written once, as generators that
-    # yield a request wherever a device call is due and receive its result (as
-    # MSCKF._frame_steps does for the filter).  The public methods above drive them with
-    # the single calls (_serve); MultiImageProcessor drives many lanes' _frame_steps and
-    # serves each kind for all waiting lanes with one set call.  Requests:
+    # ---- the frame as generators of device requests ----
+    # The frame logic is written once, as generators that yield a request wherever a
+    # device call is due and receive its result (as MSCKF._frame_steps does for the
+    # filter).  The public methods above drive them with the single calls (_serve);
+    # MultiImageProcessor drives many lanes' _frame_steps and serves each kind for all
+    # waiting lanes with one set call.  config.device_pipeline is consulted in two places:
+    # _match_steps (one stereo_match request, or six single calls composed on the spot)
+    # and _add_new_steps (a fast_grid request, or a fast request and the host sieve).
+    # Requests:
     #   ("upload", [(slot, image), ...])                                     -> None
-    #   ("fast", slot, threshold)                                            -> Frontend.fast
+    #   ("fast", slot, threshold[, mask])                                    -> Frontend.fast
     #   ("lk", slot_prev, slot_next, prev_pts, next_pts)                     -> Frontend.lk
     #   ("stereo_match", slot0, slot1, pts, cam0, cam1, R_guess, E, thr)     -> Frontend.stereo_match
     #   ("ransac", sets, inlier_error, n_hyp, draws)                         -> Frontend.two_point_ransac
@@ -978,11 +894,11 @@ class ImageProcessor:
         yield from self._collect_new_steps([tuple(p) for p in xy], list(resp))
 
     def _collect_new_steps(self, cam0_points, responses):
-        cam1_points, inliers = yield from self._stereo_match_steps(cam0_points)
+        cam1_points, inliers = yield from self._match_steps(cam0_points)
         self._assign_new(cam0_points, responses, cam1_points, inliers)
 
     def _track_steps(self):
-        """track_features, statement for statement, around its three requests."""
+        """track_features (image.py:219-313) around its requests."""
         img = self.cam0_curr_img_msg.image
         gh, gw = self.get_grid_size(img)
         cam0_R_p_c, cam1_R_p_c = self.integrate_imu_data()
@@ -1011,7 +927,7 @@ class ImageProcessor:
         prev_tracked_lifetime = _select(prev_lifetime, track_inliers)
         curr_tracked_cam0_points = _select(curr_cam0_points, track_inliers)
         self.num_features["after_tracking"] = len(curr_tracked_cam0_points)
-        curr_cam1_points, match_inliers = yield from self._stereo_match_steps(curr_tracked_cam0_points)
+        curr_cam1_points, match_inliers = yield from self._match_steps(curr_tracked_cam0_points)
         prev_matched_ids = _select(prev_tracked_ids, match_inliers)
         prev_matched_lifetime = _select(prev_tracked_lifetime, match_inliers)
         curr_matched_cam0_points = _select(curr_tracked_cam0_points, match_inliers)
@@ -1019,13 +935,12 @@ class ImageProcessor:
         self.num_features["after_matching"] = len(curr_matched_cam0_points)
         ransac_inliers = None
         if self.config.ransac_enabled:
-            (in0, _), (in1, _) = yield ("ransac", self._ransac_sets(
+            ransac_inliers = yield from self._ransac_steps(
                 _select(_select(prev_cam0_points, track_inliers), match_inliers), curr_matched_cam0_points,
                 _select(_select(prev_cam1_points, track_inliers), match_inliers), curr_matched_cam1_points,
-                cam0_R_p_c, cam1_R_p_c), self.config.ransac_threshold, self.ransac_n_hyp, draws)
-            ransac_inliers = np.logical_and(in0, in1)
+                cam0_R_p_c, cam1_R_p_c, draws)
         after_ransac = 0
-        for i in range(len(curr_matched_cam0_points)):
+        for i in range(len(curr_matched_cam0_points)):   # RANSAC stub: all inliers (image.py:292-293)
             if ransac_inliers is not None and not ransac_inliers[i]:
                 continue
             f = FeatureMetaData()
@@ -1037,22 +952,23 @@ class ImageProcessor:
             after_ransac += 1
         self.num_features["after_ransac"] = after_ransac
 
+    def _stereo_args(self):
+        """(cam0, cam1, R_guess, E, stereo_threshold) of mfe_stereo_match and
+        mfe_tracks_step.  The equidistant quirk of undistort_points (no
+        rectification) is kept by passing the identity as the rotation of the
+        initial guess."""
+        R_cam0_cam1, E = self._stereo_extrinsics()
+        model0 = _model(self.cam0_distortion_model)
+        return ((self.cam0_intrinsics, model0, self.cam0_distortion_coeffs),
+                (self.cam1_intrinsics, _model(self.cam1_distortion_model), self.cam1_distortion_coeffs),
+                np.identity(3) if model0 == EQUIDISTANT else R_cam0_cam1, E, self.config.stereo_threshold)
+
     def _stereo_match_steps(self, cam0_points):
-        """stereo_match as the one call mfe_stereo_match.  The equidistant
-        quirk of undistort_points (no rectification) is kept by passing the
-        identity as the rotation of the initial guess."""
+        """stereo_match as the one call mfe_stereo_match."""
         cam0_points = np.asarray(cam0_points, float).reshape(-1, 2)
         if len(cam0_points) == 0:
             return [], []
-        R_cam0_cam1 = self.R_cam1_imu.T @ self.R_cam0_imu
-        t_cam0_cam1 = self.R_cam1_imu.T @ (self.t_cam0_imu - self.t_cam1_imu)
-        E = _skew(t_cam0_cam1) @ R_cam0_cam1
-        model0 = _model(self.cam0_distortion_model)
-        c1, inliers, _ = yield (
-            "stereo_match", self._slot_c0, self._slot_c1, cam0_points,
-            (self.cam0_intrinsics, model0, self.cam0_distortion_coeffs),
-            (self.cam1_intrinsics, _model(self.cam1_distortion_model), self.cam1_distortion_coeffs),
-            np.identity(3) if model0 == EQUIDISTANT else R_cam0_cam1, E, self.config.stereo_threshold)
+        c1, inliers, _ = yield ("stereo_match", self._slot_c0, self._slot_c1, cam0_points, *self._stereo_args())
         return [tuple(p) for p in c1], list(inliers.astype(bool))
 
     def _tracks_lane(self, lane):
@@ -1064,28 +980,38 @@ class ImageProcessor:
         ransac = None
         if self.config.ransac_enabled:   # once per tracked frame, as in _track_steps
             ransac = (R0, R1, self.ransac_rng.integers(0, 1 << 32, size=(2, self.ransac_n_hyp, 2), dtype=np.uint32))
-        k = self.cam0_intrinsics
-        K = np.array([[k[0], 0.0, k[2]], [0.0, k[1], k[3]], [0.0, 0.0, 1.0]])
-        Hm = K @ R0 @ np.linalg.inv(K)
-        R_cam0_cam1 = self.R_cam1_imu.T @ self.R_cam0_imu
-        t_cam0_cam1 = self.R_cam1_imu.T @ (self.t_cam0_imu - self.t_cam1_imu)
-        model0 = _model(self.cam0_distortion_model)
-        return TracksLane(lane, self._slot_prev, self._slot_c0, self._slot_c1, Hm,
-                          (self.cam0_intrinsics, model0, self.cam0_distortion_coeffs),
-                          (self.cam1_intrinsics, _model(self.cam1_distortion_model), self.cam1_distortion_coeffs),
-                          np.identity(3) if model0 == EQUIDISTANT else R_cam0_cam1, _skew(t_cam0_cam1) @ R_cam0_cam1,
-                          self.config.stereo_threshold, ransac)
+        return TracksLane(lane, self._slot_prev, self._slot_c0, self._slot_c1,
+                          self._homography(R0, self.cam0_intrinsics), *self._stereo_args(), ransac)
 
     def _add_new_steps(self):
-        """add_new_features with the mask, the detection and the per-cell sieve
-        as the one call mfe_fast_grid.  A cell comes back response-descending
-        with raster ties where the sieve leaves a cell of at most
-        grid_max_feature_num in raster order; _assign_new sorts every cell by
-        response with a stable sort, so the features and their ids are the same."""
-        occ = np.array([f.cam0_point for f in chain.from_iterable(self.curr_features)], np.float32).reshape(-1, 2)
-        xy, resp, _, _ = yield ("fast_grid", self._slot_c0, self.config.fast_threshold, occ, self.config.grid_row,
-                                self.config.grid_col, self.config.grid_max_feature_num)
-        yield from self._collect_new_steps([tuple(p) for p in xy], list(resp))
+        """add_new_features (image.py:317-390).  With config.device_pipeline the
+        mask, the detection and the per-cell sieve are the one call
+        mfe_fast_grid: a cell comes back response-descending with raster ties
+        where the host sieve leaves a cell of at most grid_max_feature_num in
+        raster order; _assign_new sorts every cell by response with a stable
+        sort, so the features and their ids are the same."""
+        cfg = self.config
+        if cfg.device_pipeline:
+            occ = np.array([f.cam0_point for f in chain.from_iterable(self.curr_features)], np.float32).reshape(-1, 2)
+            xy, resp, _, _ = yield ("fast_grid", self._slot_c0, cfg.fast_threshold, occ, cfg.grid_row, cfg.grid_col,
+                                    cfg.grid_max_feature_num)
+            return (yield from self._collect_new_steps([tuple(p) for p in xy], list(resp)))
+        img = self.cam0_curr_img_msg.image
+        gh, gw = self.get_grid_size(img)
+        mask = np.ones(img.shape[:2], dtype=np.uint8)
+        for f in chain.from_iterable(self.curr_features):
+            x, y = map(int, f.cam0_point)
+            mask[y - 3:y + 4, x - 3:x + 4] = 0   # the reference's slice, negative starts included
+        xy, resp = yield ("fast", self._slot_c0, cfg.fast_threshold, mask)
+        sieve = [[] for _ in range(cfg.grid_num)]
+        for p, r in zip(xy, resp):
+            sieve[self._grid_code(p, gh, gw)].append((tuple(p), r))
+        picked = []
+        for feats in sieve:
+            if len(feats) > cfg.grid_max_feature_num:
+                feats = sorted(feats, key=lambda x: x[1], reverse=True)[:cfg.grid_max_feature_num]
+            picked.extend(feats)
+        yield from self._collect_new_steps([p for p, _ in picked], [r for _, r in picked])
 
     def _publish_steps(self):
         """publish: both cameras' points undistorted by one request."""
