@@ -7,13 +7,15 @@ frames/s of both, the batched launch counts, and ATE vs ground truth.  The
 replayed messages (the front-end's output) are built before both timed
 regions.
 
-    python tools/bench_sequences.py [--seqs 11] [--frames 200] [--fp32] [--device-map]
+    python tools/bench_sequences.py [--seqs 11] [--frames 200] [--fp32] [--device-map [--device-keyframes]]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         tools/bench_sequences.py --seqs 11      # sequences dealt round-robin over N GPUs
 
 --device-map keeps the lanes' feature maps on the device (msckf_map.h) and
-feeds the frames as array messages (msckf.FeatureArrays); --profile prints a
-cProfile split of the batched replay to stderr.
+feeds the frames as array messages (msckf.FeatureArrays); --device-keyframes
+(with --device-map) chooses a prune frame's cam states on the device
+(msckf_keyframes.h); --profile prints a cProfile split of the batched replay to
+stderr.
 
 On N GPUs every rank replays its share of the sequences (replicas.shard) on
 its own device; the replicas' host TCP hub (msckf_amd.replicas, no RCCL:
@@ -45,15 +47,18 @@ def main():
     ap.add_argument("--fp32", action="store_true")
     ap.add_argument("--no-single", action="store_true")
     ap.add_argument("--device-map", action="store_true")
+    ap.add_argument("--device-keyframes", action="store_true")
     ap.add_argument("--profile", action="store_true")
     a = ap.parse_args()
+    if a.device_keyframes and not a.device_map:
+        ap.error("--device-keyframes needs --device-map")
     dtype = np.float32 if a.fp32 else np.float64
     grp = replicas.init()
     mine = replicas.shard(list(range(a.seqs)), grp.rank, grp.world)
     streams = [FeatureStream.from_synthetic(synth.make_sequence(a.frames, 100 + i)) for i in mine]
     n_frames = sum(s.n_frames for s in streams)
     multi = MultiMSCKF(len(streams), dtype=dtype, device=grp.local_rank,
-                       device_map=a.device_map) if streams else None
+                       device_map=a.device_map, device_keyframes=a.device_keyframes) if streams else None
     # the messages are the front-end's output: built before either timed
     # region (as the bench's ATE leg does), fresh objects for each run
     msgs = [s.messages(arrays=a.device_map) for s in streams]
@@ -77,7 +82,8 @@ def main():
     out = {"config": "SURVEY config 4 shape: %d synthetic stereo+IMU sequences x %d frames, %s, %d GPU(s)"
                      % (a.seqs, a.frames, "fp32" if a.fp32 else "fp64", grp.world),
            "batched_frames_per_s": round(total_frames / el_b, 1), "batched_s": round(el_b, 2),
-           "device_map": bool(a.device_map), "batched_launches_rank0": launches,
+           "device_map": bool(a.device_map), "device_keyframes": bool(a.device_keyframes),
+           "batched_launches_rank0": launches,
            "ate_vs_gt_m_rank0": [round(ate(t, s.gt), 5) for t, s in zip(trajs, streams)]}
     if not a.no_single and grp.world == 1:
         evs = [s.events() for s in streams]
@@ -86,7 +92,7 @@ def main():
                     zip(ev, np.cumsum([k for k, _ in ev]) - 1)] for s, ev in zip(streams, evs)]
         t0 = time.perf_counter()
         for s, ev in zip(streams, evs):
-            flt = msckf_amd.MSCKF(dtype=dtype, device_map=a.device_map)
+            flt = msckf_amd.MSCKF(dtype=dtype, device_map=a.device_map, device_keyframes=a.device_keyframes)
             replay(flt, s, events=ev)
             flt.close()
         el_s = time.perf_counter() - t0

@@ -163,6 +163,15 @@ MAP_SIGS = {
 }
 MAP_EXPORTED = tuple(MAP_SIGS)
 
+# the keyframe choice on the device, fused into the prune select (include/msckf_keyframes.h), same library and
+# context; the reference's thresholds (msckf.py:711): rotation [rad], translation [m], tracking rate
+KEYFRAME_ROT_THR, KEYFRAME_TRANS_THR, KEYFRAME_RATE_THR = 0.2618, 0.4, 0.5
+KEYFRAME_SIGS = {
+    "msckf_keyframe_select": (C.c_int, [_P, C.c_int, _I, _D, C.c_double, C.c_double, C.c_double, _I, _I, _I64, _I,
+                                        _U8, _D, _D, _U8, _I]),
+}
+KEYFRAME_EXPORTED = tuple(KEYFRAME_SIGS)
+
 # multi-GPU replica transport, RCCL (include/msckf_replicas.h), same library
 REPLICA_SIGS = {
     "msckf_rccl_unique_id": (C.c_int, [_U8]),
@@ -191,7 +200,7 @@ def load_library(path: str = LIB_PATH):
         for name, (res, args) in (list(_SIGS.items()) + list(FRONTEND_SIGS.items()) +
                                   list(FRONTEND_RANSAC_SIGS.items()) + list(FRONTEND_PIPELINE_SIGS.items()) +
                                   list(FRONTEND_LANES_SIGS.items()) + list(FRONTEND_TRACKS_SIGS.items()) +
-                                  list(MAP_SIGS.items()) +
+                                  list(MAP_SIGS.items()) + list(KEYFRAME_SIGS.items()) +
                                   list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res
@@ -549,6 +558,36 @@ class Context:
                 self.h, k, _ptr(filters, C.c_int32), _ptr(slot_off, C.c_int32), _ptr(slots, C.c_int32),
                 _ptr(ninv, C.c_int32), _ptr(did, C.c_int64), _ptr(dinfo, C.c_int32)))
         return [(did[w, :ninv[w]].copy(), dinfo[w, :ninv[w]].copy()) for w in range(k)]
+
+    def keyframe_select(self, filters, rates, rot_thr=KEYFRAME_ROT_THR, trans_thr=KEYFRAME_TRANS_THR,
+                        rate_thr=KEYFRAME_RATE_THR):
+        """msckf_keyframe_select: the two cam slots of each listed filter chosen
+        on the device from its cam states and ``rates`` (its tracking rate), and
+        the prune select with them, one synchronisation.  Per listed filter
+        (slots [2] ascending, involved ids, info [n][4] as map_prune_select).
+        An outstanding deferred batch (Pending) is read back in the same copy."""
+        filters = _i32(filters)
+        k = len(filters)
+        rates = _f64(rates, (k,))
+        slots, ninv = np.zeros((k, 2), np.int32), np.zeros(k, np.int32)
+        did, dinfo = self._map_desc(k)
+        pend = self._pending if self._pending is not None and self._pending.res is None else None
+        if pend is not None:
+            nf = self._nf
+            acc, gam, p, v = np.zeros(nf, np.uint8), np.zeros(nf), np.zeros((nf, 3)), np.zeros(nf, np.uint8)
+            rows = np.zeros(self.B, np.int32)
+        else:
+            acc = gam = p = v = rows = None
+        with self.lock:
+            self._check(self.lib.msckf_keyframe_select(
+                self.h, k, _ptr(filters, C.c_int32), _ptr(rates, C.c_double), float(rot_thr), float(trans_thr),
+                float(rate_thr), _ptr(slots, C.c_int32), _ptr(ninv, C.c_int32), _ptr(did, C.c_int64),
+                _ptr(dinfo, C.c_int32), _ptr(acc, C.c_uint8), _ptr(gam, C.c_double), _ptr(p, C.c_double),
+                _ptr(v, C.c_uint8), _ptr(rows, C.c_int32)))
+        if pend is not None:
+            pend.res = (acc.astype(bool), gam, p, v.astype(bool), rows)
+            self._pending = None
+        return [(slots[w].copy(), did[w, :ninv[w]].copy(), dinfo[w, :ninv[w]].copy()) for w in range(k)]
 
     def map_load(self, mode, filters, feat_off, rows, counts, p_w=None):
         """msckf_map_load; the batch holds the features in ascending filter

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/msckf_hip.h"
+#include "../../include/msckf_keyframes.h"
 #include "../../include/msckf_map.h"
 #include "msckf_common.h"
 #include "msckf_launch.h"
@@ -1656,6 +1657,7 @@ int msckf_debug_kalman(msckf_ctx_t* c) {
 
 }  // extern "C"
 
-// definitions, not declarations: the host side of include/msckf_map.h, kept in a file of its own but part of
-// this translation unit because it uses the context, the staging helpers and the loader plan above
+// definitions, not declarations: the host side of include/msckf_map.h and include/msckf_keyframes.h, kept in
+// a file of its own but part of this translation unit because it uses the context, the staging helpers and the
+// loader plan above
 #include "msckf_map_api.inc"

@@ -1,6 +1,7 @@
 // msckf_map.hip -- the filter's feature map kept on the device
 // (include/msckf_map.h is the specification, tests/feature_map_ref.py its
-// numpy restatement).  One workgroup of 256 threads (four wavefronts) per named
+// numpy restatement), and the keyframe choice fused into the prune select
+// (include/msckf_keyframes.h, tests/keyframe_ref.py).  One workgroup of 256 threads (four wavefronts) per named
 // filter; a call reads a filter's current table and writes its other one.
 //
 // Rules (those of the front-end's k_trk_* kernels): fixed-stride [filter][cap]
@@ -10,6 +11,7 @@
 // data-dependent ordering -- a repeat gives the same bits.
 #include <hip/hip_runtime.h>
 
+#include "msckf_common.h"
 #include "msckf_map_dev.h"
 
 namespace msckf {
@@ -181,15 +183,16 @@ k_map_add_lost(MapDev m, const int* __restrict__ hdr, const int64_t* __restrict_
     }
 }
 
-// msckf_map_prune_select: no row moves.
-__global__ void __launch_bounds__(MAP_BLOCK)
-k_map_prune_select(MapDev m, const int* __restrict__ hdr, const unsigned long long* __restrict__ rm,
-                   int* __restrict__ out, int64_t* __restrict__ desc_id, int* __restrict__ desc_info) {
-    __shared__ int s_wcnt[MAP_WAVES];
-    const int w = blockIdx.x, tid = threadIdx.x, cap = m.cap, N4 = m.Nmax * 4;
-    const int* h = hdr + w * MAP_HDR;
+// The body of a prune select, shared by msckf_map_prune_select and
+// msckf_keyframe_select: the rows of the table read into the other one with the
+// single involved observations dropped, the involved rows into the descriptor;
+// (r0, r1) = the removed slots.  No row moves.  Every thread of the workgroup
+// calls it; returns the number of involved rows.
+__device__ inline int select_body(const MapDev& m, const int* __restrict__ h, int w, unsigned long long r0,
+                                  unsigned long long r1, int* s_wcnt, int64_t* __restrict__ desc_id,
+                                  int* __restrict__ desc_info) {
+    const int tid = threadIdx.x, cap = m.cap, N4 = m.Nmax * 4;
     const int f = h[0], n = h[1], cur = h[2], ds = h[6];
-    const unsigned long long r0 = rm[2 * w], r1 = rm[2 * w + 1];
     const MapTab src = m.t[cur], dstt = m.t[cur ^ 1];
     const size_t fb = (size_t)f * cap;
     int ninv = 0;
@@ -235,11 +238,115 @@ k_map_prune_select(MapDev m, const int* __restrict__ hdr, const unsigned long lo
         }
         if (bit_of(k0, k1, slot)) dstt.z[(fb + i) * N4 + kk] = src.z[(fb + i) * N4 + kk];
     }
-    if (tid == 0) {
+    return ninv;
+}
+
+// msckf_map_prune_select
+__global__ void __launch_bounds__(MAP_BLOCK)
+k_map_prune_select(MapDev m, const int* __restrict__ hdr, const unsigned long long* __restrict__ rm,
+                   int* __restrict__ out, int64_t* __restrict__ desc_id, int* __restrict__ desc_info) {
+    __shared__ int s_wcnt[MAP_WAVES];
+    const int w = blockIdx.x;
+    const int* h = hdr + w * MAP_HDR;
+    const int ninv = select_body(m, h, w, rm[2 * w], rm[2 * w + 1], s_wcnt, desc_id, desc_info);
+    if (threadIdx.x == 0) {
         out[w * MAP_OUT + 0] = ninv;
-        out[w * MAP_OUT + 1] = n;
+        out[w * MAP_OUT + 1] = h[1];
         out[w * MAP_OUT + 2] = 0;
         out[w * MAP_OUT + 3] = 0;
+    }
+}
+
+// to_rotation of q / |q| (geometry.py; JPL [x y z w]), row-major
+__device__ inline void kf_rotation(const double* q, double* R) {
+    const double nq = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double x = q[0] / nq, y = q[1] / nq, z = q[2] / nq, w = q[3] / nq;
+    const double d = 2.0 * w * w - 1.0;
+    R[0] = d + 2.0 * x * x;
+    R[1] = 2.0 * w * z + 2.0 * x * y;
+    R[2] = -2.0 * w * y + 2.0 * x * z;
+    R[3] = -2.0 * w * z + 2.0 * y * x;
+    R[4] = d + 2.0 * y * y;
+    R[5] = 2.0 * w * x + 2.0 * y * z;
+    R[6] = 2.0 * w * y + 2.0 * z * x;
+    R[7] = -2.0 * w * x + 2.0 * z * y;
+    R[8] = d + 2.0 * z * z;
+}
+
+// The rotation angle between cam records c and key: 2 acos of the last component
+// of to_quaternion(R_c R_key^T), the four branches of geometry.to_quaternion.
+__device__ inline double kf_angle(const double* Rc, const double* Rk) {
+    double M[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            M[i * 3 + j] = Rc[i * 3] * Rk[j * 3] + Rc[i * 3 + 1] * Rk[j * 3 + 1] + Rc[i * 3 + 2] * Rk[j * 3 + 2];
+    double u0, u1, u2, u3;
+    if (M[8] < 0.0) {
+        if (M[0] > M[4]) {
+            u0 = 1.0 + M[0] - M[4] - M[8], u1 = M[1] + M[3], u2 = M[6] + M[2], u3 = M[5] - M[7];
+        } else {
+            u0 = M[1] + M[3], u1 = 1.0 - M[0] + M[4] - M[8], u2 = M[7] + M[5], u3 = M[6] - M[2];
+        }
+    } else if (M[0] < -M[4]) {
+        u0 = M[2] + M[6], u1 = M[7] + M[5], u2 = 1.0 - M[0] - M[4] + M[8], u3 = M[1] - M[3];
+    } else {
+        u0 = M[5] - M[7], u1 = M[6] - M[2], u2 = M[1] - M[3], u3 = 1.0 + M[0] + M[4] + M[8];
+    }
+    return 2.0 * acos(u3 / sqrt(u0 * u0 + u1 * u1 + u2 * u2 + u3 * u3));
+}
+
+// msckf_keyframe_select: lane 0 chooses the two cam slots (include/msckf_keyframes.h)
+// from the filter's cam records, the workgroup then runs the select body with them.
+template <typename T>
+__global__ void __launch_bounds__(MAP_BLOCK)
+k_map_keyframe_select(MapDev m, const int* __restrict__ hdr, const double* __restrict__ rate, double rot_thr,
+                      double trans_thr, double rate_thr, const T* __restrict__ cams, int* __restrict__ out,
+                      int64_t* __restrict__ desc_id, int* __restrict__ desc_info) {
+    __shared__ int s_wcnt[MAP_WAVES];
+    __shared__ unsigned long long s_rm[2];
+    __shared__ int s_slot[2];
+    const int w = blockIdx.x;
+    const int* h = hdr + w * MAP_HDR;
+    if (threadIdx.x == 0) {
+        const int nc = h[3];   // 4 <= nc <= Nmax, checked on the host
+        const T* rec = cams + (size_t)h[0] * m.Nmax * CAM_STRIDE;
+        const T* kr = rec + (size_t)(nc - 4) * CAM_STRIDE;
+        double q[4], Rk[9], Rc[9];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) q[c] = (double)kr[c];
+        kf_rotation(q, Rk);
+        const double kp0 = (double)kr[4], kp1 = (double)kr[5], kp2 = (double)kr[6];
+        const bool rate_ok = rate[w] > rate_thr;
+        int first = 0, slot[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const T* cr = rec + (size_t)(nc - 3 + j) * CAM_STRIDE;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) q[c] = (double)cr[c];
+            kf_rotation(q, Rc);
+            const double d0 = (double)cr[4] - kp0, d1 = (double)cr[5] - kp1, d2 = (double)cr[6] - kp2;
+            const double dist = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+            const double ang = kf_angle(Rc, Rk);
+            slot[j] = (ang < rot_thr && dist < trans_thr && rate_ok) ? nc - 3 + j : first++;
+        }
+        const int a = min(slot[0], slot[1]), b = max(slot[0], slot[1]);   // distinct: first <= 1 < nc - 3 + j
+        unsigned long long r0 = 0, r1 = 0;
+        if (a < 64) r0 |= 1ull << a; else r1 |= 1ull << (a - 64);
+        if (b < 64) r0 |= 1ull << b; else r1 |= 1ull << (b - 64);
+        s_rm[0] = r0;
+        s_rm[1] = r1;
+        s_slot[0] = a;
+        s_slot[1] = b;
+    }
+    __syncthreads();
+    const int ninv = select_body(m, h, w, s_rm[0], s_rm[1], s_wcnt, desc_id, desc_info);
+    if (threadIdx.x == 0) {
+        out[w * MAP_OUT + 0] = ninv;
+        out[w * MAP_OUT + 1] = h[1];
+        out[w * MAP_OUT + 2] = s_slot[0];
+        out[w * MAP_OUT + 3] = s_slot[1];
     }
 }
 
@@ -355,6 +462,18 @@ void launch_map_prune_select(hipStream_t s, const MapDev& m, int nfilt, const in
                              int* out, int64_t* desc_id, int* desc_info) {
     hipLaunchKernelGGL(k_map_prune_select, dim3(nfilt), dim3(MAP_BLOCK), 0, s, m, hdr, rm, out, desc_id, desc_info);
 }
+
+template <typename T>
+void launch_map_keyframe_select(hipStream_t s, const MapDev& m, int nfilt, const int* hdr, const double* rate,
+                                double rot_thr, double trans_thr, double rate_thr, const T* cams, int* out,
+                                int64_t* desc_id, int* desc_info) {
+    hipLaunchKernelGGL(k_map_keyframe_select<T>, dim3(nfilt), dim3(MAP_BLOCK), 0, s, m, hdr, rate, rot_thr, trans_thr,
+                       rate_thr, cams, out, desc_id, desc_info);
+}
+template void launch_map_keyframe_select<float>(hipStream_t, const MapDev&, int, const int*, const double*, double,
+                                                double, double, const float*, int*, int64_t*, int*);
+template void launch_map_keyframe_select<double>(hipStream_t, const MapDev&, int, const int*, const double*, double,
+                                                 double, double, const double*, int*, int64_t*, int*);
 
 void launch_map_prune_commit(hipStream_t s, const MapDev& m, int nfilt, const int* hdr, const unsigned long long* rm,
                              const int* ent_row, const int* ent_valid, const double* ent_pw) {

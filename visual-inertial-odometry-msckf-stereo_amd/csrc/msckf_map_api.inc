@@ -1,4 +1,4 @@
-// msckf_map_api.inc -- host side of include/msckf_map.h: argument checks, the
+// msckf_map_api.inc -- host side of include/msckf_map.h and include/msckf_keyframes.h: argument checks, the
 // host's record of every table (row count, which of the two sets is current),
 // one input block and one H2D copy per call, the launches of msckf_map.hip.
 // Included by msckf_api.hip, which owns the context and the batch loader's plan.
@@ -110,6 +110,66 @@ int do_map_load(msckf_ctx* c, int mode, int nfilt, const int32_t* filters, const
                          reinterpret_cast<T*>(c->obs_z), reinterpret_cast<T*>(c->chi2), c->valid,
                          reinterpret_cast<T*>(c->p_w));
     HIPC(hipGetLastError());
+    return 0;
+}
+
+// msckf_keyframe_select after its argument checks (include/msckf_keyframes.h): the launch, then ONE copy
+// back for the slots, the counts, the descriptors and -- if asked -- the loaded batch's results.
+template <typename T>
+int do_keyframe_select(msckf_ctx* c, int nfilt, const int32_t* filters, const double* rate, double rot_thr,
+                       double trans_thr, double rate_thr, int32_t* cam_slots_out, int32_t* n_inv_out,
+                       int64_t* desc_id_out, int32_t* desc_info_out, uint8_t* accepted_out, double* gamma_out,
+                       double* p_w_out, uint8_t* valid_out, int32_t* rows_out) {
+    auto& mp = c->map;
+    int ds = 1;
+    for (int w = 0; w < nfilt; ++w) ds = std::max(ds, mp.n[filters[w]]);
+    for (int w = 0; w < nfilt; ++w) mp.lost_ok[filters[w]] = 0;   // the launch overwrites the lost table
+    std::vector<int> hdr((size_t)nfilt * MAP_HDR, 0);
+    for (int w = 0; w < nfilt; ++w) {
+        const int f = filters[w];
+        int* h = &hdr[(size_t)w * MAP_HDR];
+        h[0] = f, h[1] = mp.n[f], h[2] = mp.cur[f], h[3] = c->h_ncams[f], h[6] = ds;
+    }
+    MapBlock blk;
+    const size_t o_hdr = blk.add(hdr.data(), hdr.size() * sizeof(int));
+    const size_t o_rate = blk.add(rate, (size_t)nfilt * sizeof(double));
+    if (int r = map_send(c, mp.in, blk)) return r;
+    const MapOut mo(nfilt, ds);
+    HIPC(mp.out.ensure(mo.total + 16));
+    launch_map_keyframe_select<T>(c->stream, mp.dev, nfilt, reinterpret_cast<const int*>(mp.in.p + o_hdr),
+                                  reinterpret_cast<const double*>(mp.in.p + o_rate), rot_thr, trans_thr, rate_thr,
+                                  reinterpret_cast<const T*>(c->cams.p), reinterpret_cast<int*>(mp.out.p),
+                                  reinterpret_cast<int64_t*>(mp.out.p + mo.o_id),
+                                  reinterpret_cast<int*>(mp.out.p + mo.o_info));
+    HIPC(hipGetLastError());
+    const bool res = accepted_out || gamma_out || p_w_out || valid_out || rows_out;
+    DownList d;
+    const size_t o_out = d.add(mp.out.p, mo.total);
+    ResultsRead rr;
+    if (res) rr = add_results<T>(c, d);
+    HIPSYNC(c, d.run(c));
+    if (res)   // an error of the batch: nothing was selected (no table becomes current)
+        if (int r = unpack_results<T>(c, d, rr, accepted_out, gamma_out, p_w_out, valid_out, rows_out)) return r;
+    const unsigned char* p = d.at(c, o_out);
+    const int* out = reinterpret_cast<const int*>(p);
+    for (int w = 0; w < nfilt; ++w) {
+        const int a = out[w * MAP_OUT + 2], b = out[w * MAP_OUT + 3];
+        if (a < 0 || a >= b || b >= c->h_ncams[filters[w]])
+            FAIL(-2, "filter %d: the device chose the cam slots %d, %d of %d", filters[w], a, b, c->h_ncams[filters[w]]);
+    }
+    for (int w = 0; w < nfilt; ++w) {
+        const int f = filters[w], ni = out[w * MAP_OUT + 0], a = out[w * MAP_OUT + 2], b = out[w * MAP_OUT + 3];
+        cam_slots_out[2 * w] = a;
+        cam_slots_out[2 * w + 1] = b;
+        n_inv_out[w] = ni;
+        map_copy_desc(c, p, mo, ds, w, ni, desc_id_out, desc_info_out);
+        mp.cur[f] ^= 1;
+        mp.lost_ok[f] = 0;
+        mp.sel_ok[f] = 1;
+        mp.rm[2 * f] = mp.rm[2 * f + 1] = 0ull;
+        mp.rm[2 * f + (a >> 6)] |= 1ull << (a & 63);
+        mp.rm[2 * f + (b >> 6)] |= 1ull << (b & 63);
+    }
     return 0;
 }
 
@@ -359,6 +419,25 @@ int msckf_map_prune_select(msckf_ctx_t* c, int nfilt, const int32_t* filters, co
         mp.rm[2 * f + 1] = rm[2 * w + 1];
     }
     return 0;
+}
+
+int msckf_keyframe_select(msckf_ctx_t* c, int nfilt, const int32_t* filters, const double* tracking_rate,
+                          double rot_thr, double trans_thr, double rate_thr, int32_t* cam_slots_out,
+                          int32_t* n_inv_out, int64_t* desc_id_out, int32_t* desc_info_out, uint8_t* accepted_out,
+                          double* gamma_out, double* p_w_out, uint8_t* valid_out, int32_t* rows_out) {
+    if (int r = map_check(c)) return r;
+    if (int r = check_list(c, nfilt, filters)) return r;
+    if (nfilt <= 0) return 1;
+    if (!tracking_rate || !cam_slots_out || !n_inv_out || !desc_id_out || !desc_info_out) FAIL(-1, "null argument");
+    for (int w = 0; w < nfilt; ++w)
+        if (c->h_ncams[filters[w]] < 4)
+            FAIL(-1, "filter %d has %d cam states: the keyframe choice needs 4", filters[w], c->h_ncams[filters[w]]);
+    c->last_async = "msckf_keyframe_select";
+    HIPC(hipSetDevice(c->device));
+    JOIN_LANES(c);
+    return DISPATCH(c, do_keyframe_select, c, nfilt, filters, tracking_rate, rot_thr, trans_thr, rate_thr,
+                    cam_slots_out, n_inv_out, desc_id_out, desc_info_out, accepted_out, gamma_out, p_w_out, valid_out,
+                    rows_out);
 }
 
 int msckf_map_load(msckf_ctx_t* c, int mode, int nfilt, const int32_t* filters, const int32_t* feat_off,

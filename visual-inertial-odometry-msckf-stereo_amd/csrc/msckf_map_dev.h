@@ -34,6 +34,13 @@ void launch_map_add_lost(hipStream_t, const MapDev&, int nfilt, const int* hdr, 
 // hdr: [filter, n, table read, -, -, -, descriptor stride, -]; rm: the removed slots as a mask, two words per named filter
 void launch_map_prune_select(hipStream_t, const MapDev&, int nfilt, const int* hdr, const unsigned long long* rm,
                              int* out, int64_t* desc_id, int* desc_info);
+// msckf_keyframe_select (include/msckf_keyframes.h): the select with the two slots chosen in the kernel from the
+// filter's cam records (cams: the context's [B][Nmax][CAM_STRIDE]); out[2], out[3] = the slots, ascending
+// hdr: [filter, n, table read, cam states, -, -, descriptor stride, -]; rate: tracking rate per named filter
+template <typename T>
+void launch_map_keyframe_select(hipStream_t, const MapDev&, int nfilt, const int* hdr, const double* rate,
+                                double rot_thr, double trans_thr, double rate_thr, const T* cams, int* out,
+                                int64_t* desc_id, int* desc_info);
 // hdr: [filter, n, table read, -, entry first, entry end, -, -]; entries: row, valid flag, position
 void launch_map_prune_commit(hipStream_t, const MapDev&, int nfilt, const int* hdr, const unsigned long long* rm,
                              const int* ent_row, const int* ent_valid, const double* ent_pw);

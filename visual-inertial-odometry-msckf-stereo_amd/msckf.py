@@ -15,7 +15,9 @@ nullspace projection, gating, stacking, compression of the stacked rows
 no CPU fallback.  With ``device_map=True`` the feature map is device state as
 well (include/msckf_map.h): adding observations, the lost-feature and prune
 selections and the packing of an update's observations are device calls, the
-host keeps the decisions' descriptors (ids, track lengths) for its logs.
+host keeps the decisions' descriptors (ids, track lengths) for its logs; with
+``device_keyframes=True`` the keyframe selection is part of the prune select's
+device call too (include/msckf_keyframes.h).
 
 Every device interaction of a frame is expressed as a request yielded by a
 step generator (``_frame_steps``); ``feature_callback`` serves the requests
@@ -100,16 +102,23 @@ class MSCKF:
     ROW_CAP = 1500   # msckf.py:678
 
     def __init__(self, config=None, dtype=np.float64, device=0, cam_capacity=None, ctx=None, slot=0,
-                 device_map=False, map_capacity=1024):
+                 device_map=False, map_capacity=1024, device_keyframes=False):
         """``device_map``: keep the feature map in the context's tables
         (msckf_map.h) instead of ``map_server``'s dicts; ``map_capacity``: rows
-        per filter.  A shared ``ctx`` must already have its tables."""
+        per filter.  A shared ``ctx`` must already have its tables.
+        ``device_keyframes`` (with ``device_map``): a prune frame's cam states
+        are chosen on the device, in the prune select's call
+        (msckf_keyframes.h), instead of from a read of the cam poses."""
         if config is None:
             config = FilterConfig()
         elif not isinstance(config, FilterConfig):
             config = FilterConfig.from_reference(config)
         self.config = config
         self.device_map = bool(device_map)
+        self.device_keyframes = bool(device_keyframes)
+        if self.device_keyframes and not self.device_map:
+            raise ValueError("device_keyframes=True needs device_map=True: the choice is part of the map's prune "
+                             "select")
         if self.device_map and config.optimization.translation_threshold >= 0:
             raise ValueError("device_map=True needs optimization.translation_threshold < 0 (it is %r): check_motion "
                              "reads the cam poses on the host" % (config.optimization.translation_threshold,))
@@ -214,6 +223,8 @@ class MSCKF:
             return ctx.map_add_lost([f], [0, len(req[1])], req[1], req[2])[0]
         if kind == "map_prune_select":
             return ctx.map_prune_select([f], [0, len(req[1])], req[1])[0]
+        if kind == "map_keyframe_select":   # (kind, tracking rate)
+            return ctx.keyframe_select([f], [req[1]])[0]
         if kind == "map_triangulate":
             ctx.map_load(_lib.MAP_LOAD_PRUNE_TRI, [f], [0, len(req[1])], req[1], req[2])
             ctx.batch_triangulate()
@@ -232,7 +243,8 @@ class MSCKF:
     def _settle(self):
         """Applies the deferred update results (gate / shape logs, new
         positions) in request order.  Called at the frame's synchronisation
-        points -- after a ``states`` read, when the device has drained anyway."""
+        points -- after a ``states`` read or a ``map_keyframe_select``, when the
+        device has drained anyway."""
         d, self._deferred = self._deferred, []
         for pend, fn in d:
             fn(*pend.get())
@@ -572,11 +584,17 @@ class MSCKF:
         """msckf.py:730-818 on the device table."""
         if len(self.cam_ids) < self.config.max_cam_state_size:
             return
-        _, cams_arr = yield ("states",)
-        self._settle()
-        rm = self._find_redundant_cam_states(cams_arr)
-        slots = np.array([self.cam_ids.index(c) for c in rm], np.int32)
-        inv_ids, info = yield ("map_prune_select", slots)
+        if self.device_keyframes:   # the choice, the select and the deferred results in one call
+            slots, inv_ids, info = yield ("map_keyframe_select", self.tracking_rate)
+            self._settle()          # the device has drained
+            slots = np.asarray(slots, np.int32)
+            rm = [self.cam_ids[s] for s in slots]
+        else:
+            _, cams_arr = yield ("states",)
+            self._settle()
+            rm = self._find_redundant_cam_states(cams_arr)
+            slots = np.array([self.cam_ids.index(c) for c in rm], np.int32)
+            inv_ids, info = yield ("map_prune_select", slots)
         init = info[:, 2].astype(bool)
         tri = np.flatnonzero(~init)
         pw = np.full((len(inv_ids), 3), np.nan)

@@ -17,6 +17,10 @@ with ONE batched launch:
                  keyframe selection; the deferred update results ride along)
   prune       -> msckf_prune_batch
   cov_diag    -> msckf_get_cov_diag_batch (online reset)
+  map_*       -> the msckf_map_* call of the name (device_map=True), and
+                 map_keyframe_select -> msckf_keyframe_select
+                 (device_keyframes=True: the keyframe selection and the prune
+                 select in one call, the deferred update results riding along)
 
 Lanes whose frames diverge (one triangulates, another is already at its
 update) wait at the earliest pipeline stage first, so requests of the same
@@ -38,6 +42,7 @@ from .trajectory import Trajectory
 # pipeline order: a lane waiting at an earlier stage is served first
 _ORDER = {"set_state": 0, "propagate": 1, "augment": 2, "map_add_lost": 2.5, "triangulate": 3,
           "map_triangulate": 3, "update": 4, "map_update": 4, "states": 5, "map_prune_select": 5.3,
+          "map_keyframe_select": 5.3,
           "map_prune_commit": 5.6, "prune": 6, "cov_diag": 7, "map_clear": 8}
 
 
@@ -45,14 +50,18 @@ class MultiMSCKF:
     """``n`` filters (one per sequence) on one device context."""
 
     def __init__(self, n, config=None, dtype=np.float64, device=0, cam_capacity=None, lane_configs=None,
-                 device_map=False, map_capacity=1024):
+                 device_map=False, map_capacity=1024, device_keyframes=False):
         """``device_map`` / ``map_capacity``: every lane keeps its feature map
-        in the context's tables (msckf_map.h), as ``MSCKF(device_map=True)``.
+        in the context's tables (msckf_map.h), as ``MSCKF(device_map=True)``;
+        ``device_keyframes``: the lanes' prune frames choose their cam states
+        on the device (msckf_keyframes.h), one call for all waiting lanes.
         ``lane_configs`` (optional, one per lane): per-sequence host-side
         settings (check_motion's translation threshold, online_reset's
         position std threshold, window size).  The device context is shared,
         so every lane must agree on what the device computes with (noise,
         extrinsics, LM parameters: the C-ABI msckf_config_t)."""
+        if device_keyframes and not device_map:
+            raise ValueError("device_keyframes=True needs device_map=True")
         config = config or FilterConfig()
         if not isinstance(config, FilterConfig):
             config = FilterConfig.from_reference(config)
@@ -74,7 +83,9 @@ class MultiMSCKF:
                     self.ctx.close()
                     raise ValueError("lane %d: device_map=True needs optimization.translation_threshold < 0" % i)
             self.ctx.map_create(map_capacity)
-        self.lanes = [MSCKF(cfgs[i], ctx=self.ctx, slot=i, device_map=self.device_map) for i in range(n)]
+        self.device_keyframes = bool(device_keyframes)
+        self.lanes = [MSCKF(cfgs[i], ctx=self.ctx, slot=i, device_map=self.device_map,
+                            device_keyframes=self.device_keyframes) for i in range(n)]
         self.launches = defaultdict(int)       # batched device calls per request kind
 
     def __len__(self):
@@ -164,6 +175,8 @@ class MultiMSCKF:
                                     np.concatenate([np.asarray(r[2], float).reshape(-1, 4) for r in reqs]))
         if kind == "map_prune_select":
             return ctx.map_prune_select(slots, offs([r[1] for r in reqs]), cat([r[1] for r in reqs], np.int32))
+        if kind == "map_keyframe_select":   # the deferred batch, if any, rides along as with "states"
+            return ctx.keyframe_select(slots, [r[1] for r in reqs])
         if kind == "map_triangulate":
             self._ranges = ctx.map_load(_lib.MAP_LOAD_PRUNE_TRI, slots, offs([r[1] for r in reqs]),
                                         cat([r[1] for r in reqs], np.int32), cat([r[2] for r in reqs], np.int32))
