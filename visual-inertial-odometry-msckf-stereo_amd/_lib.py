@@ -172,6 +172,18 @@ KEYFRAME_SIGS = {
 }
 KEYFRAME_EXPORTED = tuple(KEYFRAME_SIGS)
 
+# the frame's message handed from the front-end's tracks to the filter's map on the device
+# (include/msckf_handoff.h), same library, both contexts
+HANDOFF_SIGS = {
+    "mfe_tracks_msg_put": (C.c_int, [_P, C.c_int, C.c_int, _I64, _D]),
+    "mfe_tracks_msg_get": (C.c_int, [_P, C.c_int, _I, _I, _I64, _D]),
+    "mfe_tracks_step_msg": (C.c_int, [_P, C.c_int, _I, _I, _I, _I, _D, _D, _I, _D, _D, _I, _D, _D, _D, _D, _I, _D, _D,
+                                      _U32, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double,
+                                      C.c_int, _I, _I, _I, _I64]),
+    "msckf_map_add_lost_tracks": (C.c_int, [_P, _P, C.c_int, _I, _I, _I, _I, _I, _I64, _I]),
+}
+HANDOFF_EXPORTED = tuple(HANDOFF_SIGS)
+
 # multi-GPU replica transport, RCCL (include/msckf_replicas.h), same library
 REPLICA_SIGS = {
     "msckf_rccl_unique_id": (C.c_int, [_U8]),
@@ -200,7 +212,7 @@ def load_library(path: str = LIB_PATH):
         for name, (res, args) in (list(_SIGS.items()) + list(FRONTEND_SIGS.items()) +
                                   list(FRONTEND_RANSAC_SIGS.items()) + list(FRONTEND_PIPELINE_SIGS.items()) +
                                   list(FRONTEND_LANES_SIGS.items()) + list(FRONTEND_TRACKS_SIGS.items()) +
-                                  list(MAP_SIGS.items()) + list(KEYFRAME_SIGS.items()) +
+                                  list(MAP_SIGS.items()) + list(KEYFRAME_SIGS.items()) + list(HANDOFF_SIGS.items()) +
                                   list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res
@@ -544,6 +556,24 @@ class Context:
                 self.h, k, _ptr(filters, C.c_int32), _ptr(msg_off, C.c_int32), _ptr(ids, C.c_int64),
                 _ptr(z, C.c_double), _ptr(tracked, C.c_int32), _ptr(nbef, C.c_int32), _ptr(ncand, C.c_int32),
                 _ptr(did, C.c_int64), _ptr(dinfo, C.c_int32)))
+        return [(int(tracked[w]), int(nbef[w]), did[w, :ncand[w]].copy(), dinfo[w, :ncand[w]].copy())
+                for w in range(k)]
+
+    def map_add_lost_tracks(self, filters, fe, lanes):
+        """msckf_map_add_lost_tracks (msckf_handoff.h): listed filter w takes
+        the message of lane ``lanes[w]`` of the front-end context ``fe`` (a
+        ``frontend.Frontend``), read on the device.  Returns what
+        ``map_add_lost`` returns."""
+        filters, lanes = _i32(filters), _i32(lanes)
+        k = len(filters)
+        if len(lanes) != k:
+            raise ValueError("%d lanes for %d filters" % (len(lanes), k))
+        tracked, nbef, ncand = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+        did, dinfo = self._map_desc(k)
+        with self.lock:
+            self._check(self.lib.msckf_map_add_lost_tracks(
+                self.h, fe.h, k, _ptr(filters, C.c_int32), _ptr(lanes, C.c_int32), _ptr(tracked, C.c_int32),
+                _ptr(nbef, C.c_int32), _ptr(ncand, C.c_int32), _ptr(did, C.c_int64), _ptr(dinfo, C.c_int32)))
         return [(int(tracked[w]), int(nbef[w]), did[w, :ncand[w]].copy(), dinfo[w, :ncand[w]].copy())
                 for w in range(k)]
 

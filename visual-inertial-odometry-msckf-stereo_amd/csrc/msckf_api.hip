@@ -11,10 +11,12 @@
 #include <string>
 #include <vector>
 
+#include "../../include/msckf_handoff.h"
 #include "../../include/msckf_hip.h"
 #include "../../include/msckf_keyframes.h"
 #include "../../include/msckf_map.h"
 #include "msckf_common.h"
+#include "msckf_handoff_dev.h"
 #include "msckf_launch.h"
 #include "msckf_map_dev.h"
 #include "msckf_subbatch.h"

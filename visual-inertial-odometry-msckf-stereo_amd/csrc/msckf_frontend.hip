@@ -33,7 +33,9 @@
 // is the list of one.
 //   k_trk_*     the feature tracks kept on the device (include/msckf_tracks.h): a
 //               whole tracked frame of many streams chained on the device, around
-//               lk_point, stereo_point, k_two_point_ransac and the detection stages
+//               lk_point, stereo_point, k_two_point_ransac and the detection stages;
+//               k_trk_assemble and k_trk_uv write the published ids / uv into the
+//               call's block or into the lanes' message tables (include/msckf_handoff.h)
 // Images are 8-bit, small (752 x 480 for EuRoC) and read through the cache:
 // these kernels are latency-class work, not HBM-bound.
 #include <hip/hip_runtime.h>
@@ -49,7 +51,9 @@
 #include "../../include/msckf_lanes.h"
 #include "../../include/msckf_pipeline.h"
 #include "../../include/msckf_ransac.h"
+#include "../../include/msckf_handoff.h"
 #include "../../include/msckf_tracks.h"
+#include "msckf_handoff_dev.h"
 
 namespace {
 
@@ -1058,6 +1062,7 @@ struct TrkOut {
     long long* next_id; // [l]
     long long* ids;     // [l][cap]
     double* uv;         // [l][cap][4]
+    int by_lane;        // ids / uv are the message tables (msckf_handoff.h): [TrkLane::lane][cap], not [l][cap]
 };
 
 __device__ __forceinline__ int trk_cell(const TrkDev& d, float x, float y) {
@@ -1274,6 +1279,7 @@ __global__ void __launch_bounds__(TRK_THREADS) k_trk_assemble(TrkDev d, const Tr
     const TrkLane& L = lanes[l];
     const size_t base = (size_t)l * d.cap, tcur = ((size_t)L.cur * d.n_lanes + L.lane) * d.cap;
     const size_t tnxt = ((size_t)(L.cur ^ 1) * d.n_lanes + L.lane) * d.cap;
+    const size_t obase = (size_t)(o.by_lane ? L.lane : l) * d.cap;
     const int n_sv = d.cnt[2 * d.n_lanes + l];
     const int* sv = d.idx + ((size_t)2 * d.n_lanes + l) * d.cap;
     int ns = 0;
@@ -1346,7 +1352,7 @@ __global__ void __launch_bounds__(TRK_THREADS) k_trk_assemble(TrkDev d, const Tr
         d.life[tnxt + out] = life;
         d.cam0[2 * (tnxt + out)] = a0; d.cam0[2 * (tnxt + out) + 1] = a1;
         d.cam1[2 * (tnxt + out)] = b0; d.cam1[2 * (tnxt + out) + 1] = b1;
-        o.ids[base + out] = id;
+        o.ids[obase + out] = id;
     }
 }
 
@@ -1357,7 +1363,7 @@ __global__ void __launch_bounds__(256) k_trk_uv(TrkDev d, const TrkLane* __restr
     const size_t t = (size_t)(L.cur ^ 1) * d.n_lanes + L.lane;
     if (r >= min(d.hdr[t].n, d.cap)) return;
     const size_t row = t * d.cap + r;
-    double* uv = o.uv + 4 * ((size_t)l * d.cap + r);
+    double* uv = o.uv + 4 * ((size_t)(o.by_lane ? L.lane : l) * d.cap + r);
     undistort_rect(L.pub0, (double)d.cam0[2 * row], (double)d.cam0[2 * row + 1], uv[0], uv[1]);
     undistort_rect(L.st.cam1, (double)d.cam1[2 * row], (double)d.cam1[2 * row + 1], uv[2], uv[3]);
 }
@@ -1388,7 +1394,26 @@ struct mfe_ctx {
     // record of each lane's current table and its row count
     TrkDev trk{};
     std::vector<int> trk_cur, trk_n;
+    // the lanes' messages (msckf_handoff.h), in the same block: ids [lane][cap], uv [lane][cap][4]; the
+    // row count and the valid flag are the host's record
+    long long* msg_ids = nullptr;
+    double* msg_uv = nullptr;
+    std::vector<int> msg_n;
+    std::vector<unsigned char> msg_valid;
 };
+
+// msckf_handoff_dev.h: the message tables as msckf_map_add_lost_tracks reads them
+bool msckf::mfe_track_messages(const mfe_ctx* c, msckf::TrackMsgView& v) {
+    if (!c || !c->trk.ids) return false;
+    v.device = c->device;
+    v.n_lanes = c->trk.n_lanes;
+    v.cap = c->trk.cap;
+    v.ids = reinterpret_cast<const int64_t*>(c->msg_ids);
+    v.uv = c->msg_uv;
+    v.n = c->msg_n.data();
+    v.valid = c->msg_valid.data();
+    return true;
+}
 
 namespace {
 
@@ -2026,7 +2051,7 @@ int mfe_tracks_create(mfe_ctx_t* c, int n_lanes, int cap, int grid_row, int grid
                  o_cinl = b.add(NL * CK), o_noff = b.add(4 * NL * cells), o_ooff = b.add(4 * NL * cells),
                  o_rsoff = b.add(4 * (2 * NL + 1)), o_rsprev = b.add(16 * 2 * NL * C), o_rscurr = b.add(16 * 2 * NL * C),
                  o_rswork = b.add(32 * 2 * NL * C), o_rsinfo = b.add(8 * MFE_RANSAC_INFO_LEN * 2 * NL),
-                 o_rsinl = b.add(2 * NL * C);
+                 o_rsinl = b.add(2 * NL * C), o_mids = b.add(8 * NL * C), o_muv = b.add(32 * NL * C);
     void* p;
     if (int rc = dev_alloc(c, &p, b.size)) return rc;
     MFE_HIP(hipMemset(p, 0, b.size));   // every lane empty, next_id = 0
@@ -2046,6 +2071,10 @@ int mfe_tracks_create(mfe_ctx_t* c, int n_lanes, int cap, int grid_row, int grid
     d.gh = (c->H + grid_row - 1) / grid_row; d.gw = (c->W + grid_col - 1) / grid_col;
     c->trk_cur.assign(n_lanes, 0);
     c->trk_n.assign(n_lanes, 0);
+    c->msg_ids = (long long*)(m + o_mids);
+    c->msg_uv = (double*)(m + o_muv);
+    c->msg_n.assign(n_lanes, 0);
+    c->msg_valid.assign(n_lanes, 0);
     return 0;
 }
 
@@ -2064,6 +2093,7 @@ int mfe_tracks_put(mfe_ctx_t* c, int lane, int n, const int64_t* ids, const int3
         MFE_FAIL(-1, "n = %d outside [0, %lld] (cap %d less grid_min per cell)", n,
                  (long long)d.cap - (long long)d.cells * d.grid_min, d.cap);
     if (n > 0 && (!ids || !lifetimes || !cam0 || !cam1)) MFE_FAIL(-1, "null table array");
+    c->msg_valid[lane] = 0;   // the lane's message described the table this call replaces
     MFE_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t t = (size_t)c->trk_cur[lane] * d.n_lanes + lane, row = t * d.cap, N = (size_t)n;
@@ -2106,20 +2136,25 @@ int mfe_tracks_get(mfe_ctx_t* c, int lane, int32_t* n, int64_t* ids, int32_t* li
     return 0;
 }
 
-int mfe_tracks_step(mfe_ctx_t* c, int n_lanes, const int32_t* lanes, const int32_t* slot_prev, const int32_t* slot_c0,
-                    const int32_t* slot_c1, const double* Hpred, const double* intrinsics0, const int32_t* model0,
-                    const double* coeffs0, const double* intrinsics1, const int32_t* model1, const double* coeffs1,
-                    const double* R_guess, const double* E, const double* stereo_threshold, const int32_t* ransac,
-                    const double* R0, const double* R1, const uint32_t* draws, int win, int max_level, int max_iter,
-                    double eps, int threshold, int max_kp, double inlier_error, int n_hyp, int32_t* n_out,
-                    int64_t* ids_out, double* uv_out, int32_t* counters, int32_t* n_total, int64_t* next_id_out) {
+// The one tracking body of mfe_tracks_step and mfe_tracks_step_msg (to_msg: ids and uv go to the
+// named lanes' message tables instead of the call's block and ids_out / uv_out, which are not read).
+static int tracks_step_body(mfe_ctx_t* c, bool to_msg, int n_lanes, const int32_t* lanes, const int32_t* slot_prev,
+                            const int32_t* slot_c0, const int32_t* slot_c1, const double* Hpred,
+                            const double* intrinsics0, const int32_t* model0, const double* coeffs0,
+                            const double* intrinsics1, const int32_t* model1, const double* coeffs1,
+                            const double* R_guess, const double* E, const double* stereo_threshold,
+                            const int32_t* ransac, const double* R0, const double* R1, const uint32_t* draws, int win,
+                            int max_level, int max_iter, double eps, int threshold, int max_kp, double inlier_error,
+                            int n_hyp, int32_t* n_out, int64_t* ids_out, double* uv_out, int32_t* counters,
+                            int32_t* n_total, int64_t* next_id_out) {
     if (!c) MFE_FAIL(-1, "null context");
     if (!c->trk.ids) MFE_FAIL(-1, "the context has no track tables (mfe_tracks_create)");
     TrkDev d = c->trk;
     if (n_lanes < 0 || n_lanes > d.n_lanes) MFE_FAIL(-1, "n_lanes = %d outside [0, %d]", n_lanes, d.n_lanes);
     if (n_lanes == 0) return 0;
     if (!lanes || !Hpred || !ransac) MFE_FAIL(-1, "null lane argument");
-    if (!n_out || !ids_out || !uv_out || !counters || !n_total || !next_id_out) MFE_FAIL(-1, "null output");
+    if (!n_out || !counters || !n_total || !next_id_out || (!to_msg && (!ids_out || !uv_out)))
+        MFE_FAIL(-1, "null output");
     int n_rs = 0;
     for (int l = 0; l < n_lanes; ++l) {
         if (lanes[l] < 0 || lanes[l] >= d.n_lanes) MFE_FAIL(-1, "lanes[%d] = %d outside [0, %d)", l, lanes[l], d.n_lanes);
@@ -2142,6 +2177,8 @@ int mfe_tracks_step(mfe_ctx_t* c, int n_lanes, const int32_t* lanes, const int32
     }
     if (c->W < 16 || c->H < 16) MFE_FAIL(-1, "image %dx%d is smaller than 16x16", c->W, c->H);
     if (max_kp < 1 || max_kp > c->kp_cap) MFE_FAIL(-1, "max_kp = %d outside [1, %d]", max_kp, c->kp_cap);
+    // a lane's message describes its current table, which this call replaces (msckf_handoff.h)
+    for (int l = 0; l < n_lanes; ++l) c->msg_valid[lanes[l]] = 0;
     MFE_HIP(hipSetDevice(c->device));
     if (int rc = grow_grid_work(c, n_lanes)) return rc;
     hipStream_t s = c->stream;
@@ -2152,7 +2189,8 @@ int mfe_tracks_step(mfe_ctx_t* c, int n_lanes, const int32_t* lanes, const int32
                  o_rsR = b.add(72 * 2 * NR), o_rsK = b.add(32 * 2 * NR), o_rsk = b.add(32 * 2 * NR),
                  o_rsm = b.add(4 * 2 * NR), o_draw = b.add(8 * 2 * NR * HY), in_bytes = b.size,
                  o_n = b.add(4 * NL), o_ctr = b.add(16 * NL), o_tot = b.add(4 * NL), o_next = b.add(8 * NL),
-                 o_ids = b.add(8 * NL * C), o_uv = b.add(32 * NL * C), out_bytes = b.size - o_n;
+                 head_bytes = b.size - o_n, o_ids = b.add(to_msg ? 0 : 8 * NL * C),
+                 o_uv = b.add(to_msg ? 0 : 32 * NL * C), out_bytes = to_msg ? head_bytes : b.size - o_n;
     if (int rc = grow_scratch(c, b.size)) return rc;
     unsigned char *h = c->rs_host, *dv = c->rs_dev;
     TrkLane* tl = (TrkLane*)(h + o_lanes);
@@ -2194,7 +2232,10 @@ int mfe_tracks_step(mfe_ctx_t* c, int n_lanes, const int32_t* lanes, const int32
     const Pyr* tab = c->d_pyr;
     TrkOut o;
     o.n = (int*)(dv + o_n); o.counters = (int*)(dv + o_ctr); o.n_total = (int*)(dv + o_tot);
-    o.next_id = (long long*)(dv + o_next); o.ids = (long long*)(dv + o_ids); o.uv = (double*)(dv + o_uv);
+    o.next_id = (long long*)(dv + o_next);
+    o.ids = to_msg ? c->msg_ids : (long long*)(dv + o_ids);
+    o.uv = to_msg ? c->msg_uv : (double*)(dv + o_uv);
+    o.by_lane = to_msg ? 1 : 0;
     const dim3 rows(d.cap, n_lanes), per256((d.cap + 255) / 256, n_lanes);
     // steps 1-3
     hipLaunchKernelGGL(k_trk_lk, rows, dim3(64), 0, s, d, dl, tab, win, max_level, max_iter, eps);
@@ -2253,11 +2294,86 @@ int mfe_tracks_step(mfe_ctx_t* c, int n_lanes, const int32_t* lanes, const int32
         n_out[i] = hn[i];
         next_id_out[i] = ((const int64_t*)(h + o_next))[i];
         memcpy(counters + 4 * i, h + o_ctr + 16 * i, 16);
-        memcpy(ids_out + i * C, h + o_ids + 8 * i * C, 8 * N);
-        memcpy(uv_out + 4 * i * C, h + o_uv + 32 * i * C, 32 * N);
+        if (to_msg) {
+            c->msg_n[lanes[i]] = hn[i];
+            c->msg_valid[lanes[i]] = 1;
+        } else {
+            memcpy(ids_out + i * C, h + o_ids + 8 * i * C, 8 * N);
+            memcpy(uv_out + 4 * i * C, h + o_uv + 32 * i * C, 32 * N);
+        }
         c->trk_cur[lanes[i]] ^= 1;
         c->trk_n[lanes[i]] = hn[i];
     }
+    return 0;
+}
+
+int mfe_tracks_step(mfe_ctx_t* c, int n_lanes, const int32_t* lanes, const int32_t* slot_prev, const int32_t* slot_c0,
+                    const int32_t* slot_c1, const double* Hpred, const double* intrinsics0, const int32_t* model0,
+                    const double* coeffs0, const double* intrinsics1, const int32_t* model1, const double* coeffs1,
+                    const double* R_guess, const double* E, const double* stereo_threshold, const int32_t* ransac,
+                    const double* R0, const double* R1, const uint32_t* draws, int win, int max_level, int max_iter,
+                    double eps, int threshold, int max_kp, double inlier_error, int n_hyp, int32_t* n_out,
+                    int64_t* ids_out, double* uv_out, int32_t* counters, int32_t* n_total, int64_t* next_id_out) {
+    return tracks_step_body(c, false, n_lanes, lanes, slot_prev, slot_c0, slot_c1, Hpred, intrinsics0, model0, coeffs0,
+                            intrinsics1, model1, coeffs1, R_guess, E, stereo_threshold, ransac, R0, R1, draws, win,
+                            max_level, max_iter, eps, threshold, max_kp, inlier_error, n_hyp, n_out, ids_out, uv_out,
+                            counters, n_total, next_id_out);
+}
+
+// ------------------------------------------ the lanes' messages (msckf_handoff.h) --
+int mfe_tracks_step_msg(mfe_ctx_t* c, int n_lanes, const int32_t* lanes, const int32_t* slot_prev,
+                        const int32_t* slot_c0, const int32_t* slot_c1, const double* Hpred,
+                        const double* intrinsics0, const int32_t* model0, const double* coeffs0,
+                        const double* intrinsics1, const int32_t* model1, const double* coeffs1, const double* R_guess,
+                        const double* E, const double* stereo_threshold, const int32_t* ransac, const double* R0,
+                        const double* R1, const uint32_t* draws, int win, int max_level, int max_iter, double eps,
+                        int threshold, int max_kp, double inlier_error, int n_hyp, int32_t* n_out, int32_t* counters,
+                        int32_t* n_total, int64_t* next_id_out) {
+    return tracks_step_body(c, true, n_lanes, lanes, slot_prev, slot_c0, slot_c1, Hpred, intrinsics0, model0, coeffs0,
+                            intrinsics1, model1, coeffs1, R_guess, E, stereo_threshold, ransac, R0, R1, draws, win,
+                            max_level, max_iter, eps, threshold, max_kp, inlier_error, n_hyp, n_out, nullptr, nullptr,
+                            counters, n_total, next_id_out);
+}
+
+int mfe_tracks_msg_put(mfe_ctx_t* c, int lane, int n, const int64_t* ids, const double* uv) {
+    if (check_trk_lane(c, lane)) return -1;
+    const TrkDev& d = c->trk;
+    if (n < 0 || n > d.cap) MFE_FAIL(-1, "n = %d outside [0, %d]", n, d.cap);
+    if (n > 0 && (!ids || !uv)) MFE_FAIL(-1, "null message array");
+    {
+        std::vector<int64_t> srt(ids, ids + n);
+        std::sort(srt.begin(), srt.end());
+        if (std::adjacent_find(srt.begin(), srt.end()) != srt.end())
+            MFE_FAIL(-1, "lane %d: an id is repeated within the message", lane);
+    }
+    c->msg_valid[lane] = 0;
+    MFE_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t row = (size_t)lane * d.cap;
+    if (n > 0) {
+        MFE_HIP(hipMemcpyAsync(c->msg_ids + row, ids, 8 * (size_t)n, hipMemcpyHostToDevice, s));
+        MFE_HIP(hipMemcpyAsync(c->msg_uv + 4 * row, uv, 32 * (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    MFE_HIP(hipStreamSynchronize(s));
+    c->msg_n[lane] = n;
+    c->msg_valid[lane] = 1;
+    return 0;
+}
+
+int mfe_tracks_msg_get(mfe_ctx_t* c, int lane, int32_t* valid, int32_t* n, int64_t* ids, double* uv) {
+    if (check_trk_lane(c, lane)) return -1;
+    if (!valid || !n) MFE_FAIL(-1, "null output");
+    *valid = c->msg_valid[lane] ? 1 : 0;
+    *n = *valid ? c->msg_n[lane] : 0;
+    if (*n == 0) return 0;
+    if (!ids || !uv) MFE_FAIL(-1, "null output");
+    const TrkDev& d = c->trk;
+    MFE_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t row = (size_t)lane * d.cap, N = (size_t)*n;
+    MFE_HIP(hipMemcpyAsync(ids, c->msg_ids + row, 8 * N, hipMemcpyDeviceToHost, s));
+    MFE_HIP(hipMemcpyAsync(uv, c->msg_uv + 4 * row, 32 * N, hipMemcpyDeviceToHost, s));
+    MFE_HIP(hipStreamSynchronize(s));
     return 0;
 }
 

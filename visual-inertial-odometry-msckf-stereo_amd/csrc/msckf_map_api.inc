@@ -64,6 +64,62 @@ void map_copy_desc(const msckf_ctx* c, const unsigned char* p, const MapOut& mo,
                 (size_t)cnt * MAP_INFO * sizeof(int));
 }
 
+// msckf_map_add_lost and msckf_map_add_lost_tracks after their checks.  Filter w's message is rows
+// [m0[w], m1[w]) of the message arrays: the host's ids / z (ntot rows, sent in the call's block), or -- with
+// dev_ids / dev_z -- arrays that lie on the device already, and the block is the header alone.
+int map_add_lost_run(msckf_ctx* c, int nfilt, const int32_t* filters, const int* m0, const int* m1, int ntot,
+                     const int64_t* ids, const double* z, const int64_t* dev_ids, const double* dev_z,
+                     int32_t* tracked_out, int32_t* n_before_out, int32_t* n_cand_out, int64_t* desc_id_out,
+                     int32_t* desc_info_out) {
+    auto& mp = c->map;
+    int ds = 1;
+    for (int w = 0; w < nfilt; ++w) ds = std::max(ds, mp.n[filters[w]]);
+    HIPC(hipSetDevice(c->device));
+    JOIN_LANES(c);
+    // the launch writes every named filter's other set, which is its lost table of the frame before:
+    // that table is gone whether or not the call succeeds
+    for (int w = 0; w < nfilt; ++w) mp.lost_ok[filters[w]] = 0;
+    std::vector<int> hdr((size_t)nfilt * MAP_HDR, 0);
+    for (int w = 0; w < nfilt; ++w) {
+        const int f = filters[w];
+        int* h = &hdr[(size_t)w * MAP_HDR];
+        h[0] = f, h[1] = mp.n[f], h[2] = mp.cur[f], h[3] = c->h_ncams[f] - 1, h[4] = m0[w], h[5] = m1[w];
+        h[6] = ds;
+    }
+    MapBlock blk;
+    const size_t o_hdr = blk.add(hdr.data(), hdr.size() * sizeof(int));
+    size_t o_ids = 0, o_z = 0;
+    if (!dev_ids) o_ids = blk.add(ids, (size_t)ntot * 8), o_z = blk.add(z, (size_t)ntot * 32);
+    if (int r = map_send(c, mp.in, blk)) return r;
+    const MapOut mo(nfilt, ds);
+    HIPC(mp.out.ensure(mo.total + 16));
+    launch_map_add_lost(c->stream, mp.dev, nfilt, reinterpret_cast<const int*>(mp.in.p + o_hdr),
+                        dev_ids ? dev_ids : reinterpret_cast<const int64_t*>(mp.in.p + o_ids),
+                        dev_ids ? dev_z : reinterpret_cast<const double*>(mp.in.p + o_z),
+                        reinterpret_cast<int*>(mp.out.p), reinterpret_cast<int64_t*>(mp.out.p + mo.o_id),
+                        reinterpret_cast<int*>(mp.out.p + mo.o_info));
+    HIPC(hipGetLastError());
+    std::vector<int> out;
+    const unsigned char* res = map_read_select(c, nfilt, mo, out);
+    if (!res) return -2;
+    for (int w = 0; w < nfilt; ++w)
+        if (out[w * MAP_OUT + 3])
+            FAIL(-3, "filter %d: %d rows exceed the map capacity %d", filters[w], out[w * MAP_OUT + 1], mp.cap);
+    for (int w = 0; w < nfilt; ++w) {
+        const int f = filters[w], nc = out[w * MAP_OUT + 2];
+        tracked_out[w] = out[w * MAP_OUT + 0];
+        n_before_out[w] = mp.n[f];
+        mp.nprev[f] = mp.n[f];
+        n_cand_out[w] = nc;
+        map_copy_desc(c, res, mo, ds, w, nc, desc_id_out, desc_info_out);
+        mp.n[f] = out[w * MAP_OUT + 1];
+        mp.cur[f] ^= 1;
+        mp.lost_ok[f] = 1;
+        mp.sel_ok[f] = 0;
+    }
+    return 0;
+}
+
 template <typename T>
 int do_map_load(msckf_ctx* c, int mode, int nfilt, const int32_t* filters, const int32_t* feat_off,
                 const int32_t* rows, const int32_t* counts, const double* p_w) {
@@ -303,8 +359,6 @@ int msckf_map_add_lost(msckf_ctx_t* c, int nfilt, const int32_t* filters, const 
     if (!msg_off || !tracked_out || !n_before_out || !n_cand_out || !desc_id_out || !desc_info_out)
         FAIL(-1, "null argument");
     if (msg_off[0] != 0) FAIL(-1, "msg_off[0] must be 0");
-    auto& mp = c->map;
-    int ds = 1;
     for (int w = 0; w < nfilt; ++w) {
         const int f = filters[w];
         if (msg_off[w + 1] < msg_off[w]) FAIL(-1, "msg_off not monotone");
@@ -313,53 +367,41 @@ int msckf_map_add_lost(msckf_ctx_t* c, int nfilt, const int32_t* filters, const 
         std::sort(s.begin(), s.end());
         if (std::adjacent_find(s.begin(), s.end()) != s.end())
             FAIL(-1, "filter %d: an id is repeated within the message", f);
-        ds = std::max(ds, mp.n[f]);
     }
     const int ntot = msg_off[nfilt];
     if (ntot && (!ids || !z)) FAIL(-1, "null argument");
     c->last_async = "msckf_map_add_lost";
-    HIPC(hipSetDevice(c->device));
-    JOIN_LANES(c);
-    // the launch writes every named filter's other set, which is its lost table of the frame before:
-    // that table is gone whether or not the call succeeds
-    for (int w = 0; w < nfilt; ++w) mp.lost_ok[filters[w]] = 0;
-    std::vector<int> hdr((size_t)nfilt * MAP_HDR, 0);
+    return map_add_lost_run(c, nfilt, filters, msg_off, msg_off + 1, ntot, ids, z, nullptr, nullptr, tracked_out,
+                            n_before_out, n_cand_out, desc_id_out, desc_info_out);
+}
+
+int msckf_map_add_lost_tracks(msckf_ctx_t* c, mfe_ctx_t* fe, int nfilt, const int32_t* filters, const int32_t* lanes,
+                              int32_t* tracked_out, int32_t* n_before_out, int32_t* n_cand_out, int64_t* desc_id_out,
+                              int32_t* desc_info_out) {
+    if (int r = map_check(c)) return r;
+    if (int r = check_list(c, nfilt, filters)) return r;
+    TrackMsgView v;
+    if (!mfe_track_messages(fe, v)) FAIL(-1, "the front-end context has no track tables (mfe_tracks_create)");
+    if (v.device != c->device)
+        FAIL(-1, "the front-end context is on device %d, the filter context on device %d", v.device, c->device);
+    if (nfilt <= 0) return 1;
+    if (!lanes || !tracked_out || !n_before_out || !n_cand_out || !desc_id_out || !desc_info_out)
+        FAIL(-1, "null argument");
+    std::vector<int> m0(nfilt), m1(nfilt);
     for (int w = 0; w < nfilt; ++w) {
-        const int f = filters[w];
-        int* h = &hdr[(size_t)w * MAP_HDR];
-        h[0] = f, h[1] = mp.n[f], h[2] = mp.cur[f], h[3] = c->h_ncams[f] - 1, h[4] = msg_off[w], h[5] = msg_off[w + 1];
-        h[6] = ds;
+        const int f = filters[w], l = lanes[w];
+        if (l < 0 || l >= v.n_lanes) FAIL(-1, "lanes[%d] = %d outside [0, %d)", w, l, v.n_lanes);
+        for (int j = 0; j < w; ++j)
+            if (lanes[j] == l) FAIL(-1, "lane %d is named twice (entries %d and %d)", l, j, w);
+        if (!v.valid[l]) FAIL(-1, "lane %d has no valid message", l);
+        if (v.n[l] < 0 || v.n[l] > v.cap) FAIL(-1, "lane %d: a message of %d rows (cap %d)", l, v.n[l], v.cap);
+        if (c->h_ncams[f] < 1) FAIL(-1, "filter %d has no cam state to observe from", f);
+        m0[w] = l * v.cap;   // n_lanes cap <= MFE_MAX_SLOTS / 3 * MFE_RANSAC_MAX_SET_POINTS: an int holds it
+        m1[w] = m0[w] + v.n[l];
     }
-    MapBlock blk;
-    const size_t o_hdr = blk.add(hdr.data(), hdr.size() * sizeof(int));
-    const size_t o_ids = blk.add(ids, (size_t)ntot * 8), o_z = blk.add(z, (size_t)ntot * 32);
-    if (int r = map_send(c, mp.in, blk)) return r;
-    const MapOut mo(nfilt, ds);
-    HIPC(mp.out.ensure(mo.total + 16));
-    launch_map_add_lost(c->stream, mp.dev, nfilt, reinterpret_cast<const int*>(mp.in.p + o_hdr),
-                        reinterpret_cast<const int64_t*>(mp.in.p + o_ids),
-                        reinterpret_cast<const double*>(mp.in.p + o_z), reinterpret_cast<int*>(mp.out.p),
-                        reinterpret_cast<int64_t*>(mp.out.p + mo.o_id), reinterpret_cast<int*>(mp.out.p + mo.o_info));
-    HIPC(hipGetLastError());
-    std::vector<int> out;
-    const unsigned char* res = map_read_select(c, nfilt, mo, out);
-    if (!res) return -2;
-    for (int w = 0; w < nfilt; ++w)
-        if (out[w * MAP_OUT + 3])
-            FAIL(-3, "filter %d: %d rows exceed the map capacity %d", filters[w], out[w * MAP_OUT + 1], mp.cap);
-    for (int w = 0; w < nfilt; ++w) {
-        const int f = filters[w], nc = out[w * MAP_OUT + 2];
-        tracked_out[w] = out[w * MAP_OUT + 0];
-        n_before_out[w] = mp.n[f];
-        mp.nprev[f] = mp.n[f];
-        n_cand_out[w] = nc;
-        map_copy_desc(c, res, mo, ds, w, nc, desc_id_out, desc_info_out);
-        mp.n[f] = out[w * MAP_OUT + 1];
-        mp.cur[f] ^= 1;
-        mp.lost_ok[f] = 1;
-        mp.sel_ok[f] = 0;
-    }
-    return 0;
+    c->last_async = "msckf_map_add_lost_tracks";
+    return map_add_lost_run(c, nfilt, filters, m0.data(), m1.data(), 0, nullptr, nullptr, v.ids, v.uv, tracked_out,
+                            n_before_out, n_cand_out, desc_id_out, desc_info_out);
 }
 
 int msckf_map_prune_select(msckf_ctx_t* c, int nfilt, const int32_t* filters, const int32_t* slot_off,

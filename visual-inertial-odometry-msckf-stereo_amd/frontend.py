@@ -56,7 +56,7 @@ import numpy as np
 
 from . import _lib
 from .config import _default_T_imu_cam0
-from .msckf import FeatureArrays, message_arrays
+from .msckf import FeatureArrays, TrackMessage, message_arrays
 
 RADTAN, EQUIDISTANT = 0, 1
 _I32P = C.POINTER(C.c_int32)
@@ -519,12 +519,34 @@ class Frontend:
         k = n.value
         return ids[:k].copy(), life[:k].copy(), c0[:k].copy(), c1[:k].copy(), nxt.value
 
+    def tracks_msg_put(self, lane, ids, uv):
+        """mfe_tracks_msg_put (msckf_handoff.h): the lane's message, ids int64
+        [n] and uv float64 [n][4], written from the host."""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 4)
+        if len(ids) != len(uv):
+            raise ValueError("a message of %d ids and %d coordinate rows" % (len(ids), len(uv)))
+        self._check(self.lib.mfe_tracks_msg_put(self.h, int(lane), len(ids), ids.ctypes.data_as(_I64P),
+                                                uv.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def tracks_msg_get(self, lane):
+        """mfe_tracks_msg_get: (valid, ids int64 [n], uv float64 [n][4]) of
+        the lane's message; empty arrays without a valid one."""
+        cap = self.tracks_cap
+        ids, uv = np.zeros(cap, np.int64), np.zeros((cap, 4))
+        valid, n = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.mfe_tracks_msg_get(self.h, int(lane), C.byref(valid), C.byref(n),
+                                                ids.ctypes.data_as(_I64P), uv.ctypes.data_as(C.POINTER(C.c_double))))
+        return bool(valid.value), ids[:n.value].copy(), uv[:n.value].copy()
+
     def tracks_step(self, lanes, threshold, max_kp=1 << 16, inlier_error=0.0, n_hyp=0, win=15, max_level=3,
-                    max_iter=30, eps=0.01):
+                    max_iter=30, eps=0.01, to_message=False):
         """mfe_tracks_step: one tracked frame for each ``TracksLane`` of
         ``lanes``.  Returns one ``TracksResult`` per lane.  If a lane's
         detection exceeds ``max_kp`` the MsckfError raised carries every
-        lane's ``n_total`` and no table has changed."""
+        lane's ``n_total`` and no table has changed.  ``to_message``:
+        mfe_tracks_step_msg (msckf_handoff.h) -- ids and uv stay on the device
+        as the lanes' messages, and the results carry None in their place."""
         S, cap = len(lanes), self.tracks_cap
         i32 = lambda get: np.array([int(get(a)) for a in lanes], np.int32)
         row = lambda get, w: np.ascontiguousarray(
@@ -548,26 +570,34 @@ class Frontend:
                     raise ValueError("draws of shape %s, expected %s" % (dr.shape, draws.shape[1:]))
                 draws[i] = dr
         n = np.zeros(S, np.int32)
-        ids = np.zeros((S, cap), np.int64)
-        uv = np.zeros((S, cap, 4))
         ctr = np.zeros((S, _lib.TRACKS_COUNTERS), np.int32)
         tot = np.zeros(S, np.int32)
         nxt = np.zeros(S, np.int64)
         dp = C.POINTER(C.c_double)
-        rc = self.lib.mfe_tracks_step(
+        if to_message:
+            outs = ()
+            fn = self.lib.mfe_tracks_step_msg
+        else:
+            ids = np.zeros((S, cap), np.int64)
+            uv = np.zeros((S, cap, 4))
+            outs = (ids.ctypes.data_as(_I64P), uv.ctypes.data_as(dp))
+            fn = self.lib.mfe_tracks_step
+        rc = fn(
             self.h, S, ln.ctypes.data_as(_I32P), sp.ctypes.data_as(_I32P), s0.ctypes.data_as(_I32P),
             s1.ctypes.data_as(_I32P), Hp.ctypes.data_as(dp), K0.ctypes.data_as(dp), m0.ctypes.data_as(_I32P),
             k0.ctypes.data_as(dp), K1.ctypes.data_as(dp), m1.ctypes.data_as(_I32P), k1.ctypes.data_as(dp),
             Rg.ctypes.data_as(dp), E.ctypes.data_as(dp), thr.ctypes.data_as(dp), flag.ctypes.data_as(_I32P),
             R0.ctypes.data_as(dp), R1.ctypes.data_as(dp), draws.ctypes.data_as(C.POINTER(C.c_uint32)), int(win),
             int(max_level), int(max_iter), float(eps), int(threshold), int(max_kp), float(inlier_error), n_hyp,
-            n.ctypes.data_as(_I32P), ids.ctypes.data_as(_I64P), uv.ctypes.data_as(dp), ctr.ctypes.data_as(_I32P),
-            tot.ctypes.data_as(_I32P), nxt.ctypes.data_as(_I64P))
+            n.ctypes.data_as(_I32P), *outs, ctr.ctypes.data_as(_I32P), tot.ctypes.data_as(_I32P),
+            nxt.ctypes.data_as(_I64P))
         if rc == -3:
             err = _lib.MsckfError("mfe: %s (rc=%d)" % (self.lib.mfe_last_error().decode(), rc))
             err.n_total = tot.copy()
             raise err
         self._check(rc)
+        if to_message:
+            return [TracksResult(int(n[i]), None, None, ctr[i].copy(), int(tot[i]), int(nxt[i])) for i in range(S)]
         return [TracksResult(int(n[i]), ids[i, :n[i]].copy(), uv[i, :n[i]].copy(), ctr[i].copy(), int(tot[i]),
                              int(nxt[i])) for i in range(S)]
 
@@ -1155,14 +1185,19 @@ class MultiImageProcessor:
     def imu_callback(self, i, msg):
         self.lanes[i].imu_callback(msg)
 
-    def stereo_callbacks(self, msgs, arrays=False):
+    def stereo_callbacks(self, msgs, arrays=False, handoff=False):
         """``msgs``: {lane index: stereo_msg}.  Returns {lane index:
         FeatureMsg}, as the lanes' own stareo_callback would.  ``arrays``:
         array messages (msckf.FeatureArrays) instead -- with the tracks on the
         device straight from the step's ids / uv, no tuple per feature;
-        otherwise converted once."""
+        otherwise converted once.  ``handoff`` (needs ``device_tracks``): the
+        messages stay on the device (msckf_handoff.h) and every lane returns
+        a ``msckf.TrackMessage`` naming its place; a first-frame lane
+        publishes on the host as always and writes its message from there."""
+        if handoff and not self.device_tracks:
+            raise ValueError("handoff=True needs device_tracks: the message is handed over from the device tables")
         if self.device_tracks:
-            return self._tracks_callbacks(msgs, arrays)
+            return self._tracks_callbacks(msgs, arrays, handoff)
         gens, out = {}, {}
         for i, m in msgs.items():
             gens[i] = self.lanes[i]._frame_steps(m)
@@ -1192,41 +1227,46 @@ class MultiImageProcessor:
         cam0, cam1, next_id), rows in publish order."""
         return self.fe.tracks_get(i)
 
-    def _tracks_callbacks(self, msgs, arrays=False):
+    def _tracks_callbacks(self, msgs, arrays=False, handoff=False):
         """stereo_callbacks with the tracks on the device: one upload for all
-        lanes, the first-frame lanes on their generators (then tracks_put), and
-        ONE tracks_step for all tracking lanes."""
+        lanes, the first-frame lanes on their generators (then tracks_put, and
+        with ``handoff`` tracks_msg_put), and ONE tracks_step for all tracking
+        lanes (with ``handoff`` in its to_message form)."""
         lanes, out = self.lanes, {}
         for i, m in msgs.items():
             lanes[i].cam0_curr_img_msg, lanes[i].cam1_curr_img_msg = m.cam0_msg, m.cam1_msg
         self._serve("upload", [next(lanes[i]._upload_steps()) for i in msgs])
         first = [i for i in msgs if lanes[i].is_first_img]
         if first:
-            self._pump({i: self._first_frame_tracks_steps(i) for i in first}, out)
+            self._pump({i: self._first_frame_tracks_steps(i, handoff) for i in first}, out)
         tracking = [i for i in msgs if i not in first]
         if tracking:
             self.launches["tracks_step"] += 1
             inlier_error, n_hyp = self._tracks_ransac
+            kw = dict(self.lk_kw, to_message=True) if handoff else self.lk_kw   # the default call stays as it was
             res = self.fe.tracks_step([lanes[i]._tracks_lane(i) for i in tracking], lanes[0].config.fast_threshold,
-                                      inlier_error=inlier_error, n_hyp=n_hyp, **self.lk_kw)
+                                      inlier_error=inlier_error, n_hyp=n_hyp, **kw)
             for i, r in zip(tracking, res):
                 ip = lanes[i]
                 ip.num_features.update(zip(TRACKS_COUNTER_NAMES, (int(v) for v in r.counters)))
                 ip.next_feature_id = r.next_id
-                if arrays:
+                if handoff:
+                    out[i] = TrackMessage(ip.cam0_curr_img_msg.vio_timestamp__, self.fe, i, r.n)
+                elif arrays:
                     out[i] = FeatureArrays(ip.cam0_curr_img_msg.vio_timestamp__, np.asarray(r.ids, np.int64),
                                            np.asarray(r.uv, np.float64).reshape(-1, 4))
                 else:
                     out[i] = FeatureMsg(ip.cam0_curr_img_msg.vio_timestamp__,
                                         [FeatureMeasurement(k, *u) for k, u in zip(r.ids.tolist(), r.uv.tolist())])
                 ip._end_frame()
-        if arrays:   # the first-frame lanes' messages come from the existing path
+        if arrays and not handoff:   # the first-frame lanes' messages come from the existing path
             out = {i: _as_arrays(m) for i, m in out.items()}
         return out
 
-    def _first_frame_tracks_steps(self, i):
+    def _first_frame_tracks_steps(self, i, handoff=False):
         """A lane's first frame (the images are uploaded) on the existing path;
-        its features then enter the lane's device table."""
+        its features then enter the lane's device table -- and with
+        ``handoff`` what it published becomes the lane's message."""
         ip = self.lanes[i]
         yield from ip._first_frame_steps()
         ip.is_first_img = False
@@ -1236,6 +1276,11 @@ class MultiImageProcessor:
             self.launches["tracks_put"] += 1
             self.fe.tracks_put(i, [f.id for f in feats], [f.lifetime for f in feats], [f.cam0_point for f in feats],
                                [f.cam1_point for f in feats], ip.next_feature_id)
+            if handoff:
+                arr = _as_arrays(msg)
+                self.launches["tracks_msg_put"] += 1
+                self.fe.tracks_msg_put(i, arr.ids, arr.uv)
+                return TrackMessage(arr.timestamp, self.fe, i, len(arr.ids))
             return msg
         finally:
             ip._end_frame()

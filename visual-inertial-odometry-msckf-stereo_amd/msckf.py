@@ -15,7 +15,9 @@ nullspace projection, gating, stacking, compression of the stacked rows
 no CPU fallback.  With ``device_map=True`` the feature map is device state as
 well (include/msckf_map.h): adding observations, the lost-feature and prune
 selections and the packing of an update's observations are device calls, the
-host keeps the decisions' descriptors (ids, track lengths) for its logs; with
+host keeps the decisions' descriptors (ids, track lengths) for its logs, and a
+frame's message may be a ``TrackMessage`` that names where the front-end left
+it on the device (include/msckf_handoff.h); with
 ``device_keyframes=True`` the keyframe selection is part of the prune select's
 device call too (include/msckf_keyframes.h).
 
@@ -46,6 +48,9 @@ VioResult = namedtuple("vio_result", ["timestamp", "pose", "velocity", "cam0_pos
 # A feature message as arrays: ids int64 [n], uv float64 [n][4] (u0 v0 u1 v1).
 # Accepted wherever the reference's feature_msg tuple is.
 FeatureArrays = namedtuple("FeatureArrays", ["timestamp", "ids", "uv"])
+# A feature message that stayed on the device (include/msckf_handoff.h): the n-row message of lane
+# ``lane`` of the front-end context ``frontend`` (a frontend.Frontend).  Accepted with device_map=True only.
+TrackMessage = namedtuple("TrackMessage", ["timestamp", "frontend", "lane", "n"])
 
 
 def message_arrays(feature_msg):
@@ -221,6 +226,8 @@ class MSCKF:
             return ctx.set_state(f, req[1], req[2], req[3])
         if kind == "map_add_lost":
             return ctx.map_add_lost([f], [0, len(req[1])], req[1], req[2])[0]
+        if kind == "map_add_lost_tracks":   # (kind, front-end context, lane)
+            return ctx.map_add_lost_tracks([f], req[1], [req[2]])[0]
         if kind == "map_prune_select":
             return ctx.map_prune_select([f], [0, len(req[1])], req[1])[0]
         if kind == "map_keyframe_select":   # (kind, tracking rate)
@@ -291,6 +298,9 @@ class MSCKF:
     def _frame_steps(self, feature_msg):
         """The body of feature_callback as a request generator; returns the
         vio_result (or None before gravity initialisation)."""
+        if isinstance(feature_msg, TrackMessage) and not self.device_map:
+            raise TypeError("a TrackMessage names a message on the device, which only the device feature map reads: "
+                            "it needs MSCKF(device_map=True)")
         if not self.is_gravity_set:
             return None
         if self.is_first_img:
@@ -569,8 +579,11 @@ class MSCKF:
 
     def _map_add_and_remove_lost(self, feature_msg):
         """msckf.py:409-427 and 616-689 on the device table."""
-        ids, uv = message_arrays(feature_msg)
-        tracked, cur, cand_ids, info = yield ("map_add_lost", ids, uv)
+        if isinstance(feature_msg, TrackMessage):   # the message lies on the device (msckf_handoff.h)
+            tracked, cur, cand_ids, info = yield ("map_add_lost_tracks", feature_msg.frontend, feature_msg.lane)
+        else:
+            ids, uv = message_arrays(feature_msg)
+            tracked, cur, cand_ids, info = yield ("map_add_lost", ids, uv)
         self.tracking_rate = tracked / (cur + 1e-5)
         if not len(cand_ids):
             return

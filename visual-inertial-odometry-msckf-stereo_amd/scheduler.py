@@ -17,7 +17,9 @@ with ONE batched launch:
                  keyframe selection; the deferred update results ride along)
   prune       -> msckf_prune_batch
   cov_diag    -> msckf_get_cov_diag_batch (online reset)
-  map_*       -> the msckf_map_* call of the name (device_map=True), and
+  map_*       -> the msckf_map_* call of the name (device_map=True;
+                 map_add_lost_tracks: the lanes' messages read on the device
+                 where the front-end left them, msckf_handoff.h), and
                  map_keyframe_select -> msckf_keyframe_select
                  (device_keyframes=True: the keyframe selection and the prune
                  select in one call, the deferred update results riding along)
@@ -37,10 +39,11 @@ from . import _lib
 from .config import FilterConfig
 from .frontend import MultiImageProcessor  # noqa: F401  (the image-side counterpart, same interface)
 from .msckf import MSCKF
+from .vio import MultiStereoVIO, StereoVIO  # noqa: F401  (both ends in one class)
 from .trajectory import Trajectory
 
 # pipeline order: a lane waiting at an earlier stage is served first
-_ORDER = {"set_state": 0, "propagate": 1, "augment": 2, "map_add_lost": 2.5, "triangulate": 3,
+_ORDER = {"set_state": 0, "propagate": 1, "augment": 2, "map_add_lost": 2.5, "map_add_lost_tracks": 2.5, "triangulate": 3,
           "map_triangulate": 3, "update": 4, "map_update": 4, "states": 5, "map_prune_select": 5.3,
           "map_keyframe_select": 5.3,
           "map_prune_commit": 5.6, "prune": 6, "cov_diag": 7, "map_clear": 8}
@@ -115,6 +118,8 @@ class MultiMSCKF:
             elif kind in ("cov_diag", "states"):
                 key = pending[group[0]][1:3]
                 group = [i for i in group if pending[i][1:3] == key]
+            elif kind == "map_add_lost_tracks":   # one front-end context per call
+                group = [i for i in group if pending[i][1] is pending[group[0]][1]]
             results = self._serve(kind, group, [pending[i] for i in group])
             for i, res in zip(group, results):
                 del pending[i]
@@ -173,6 +178,8 @@ class MultiMSCKF:
         if kind == "map_add_lost":
             return ctx.map_add_lost(slots, offs([r[1] for r in reqs]), cat([r[1] for r in reqs], np.int64),
                                     np.concatenate([np.asarray(r[2], float).reshape(-1, 4) for r in reqs]))
+        if kind == "map_add_lost_tracks":
+            return ctx.map_add_lost_tracks(slots, reqs[0][1], [r[2] for r in reqs])
         if kind == "map_prune_select":
             return ctx.map_prune_select(slots, offs([r[1] for r in reqs]), cat([r[1] for r in reqs], np.int32))
         if kind == "map_keyframe_select":   # the deferred batch, if any, rides along as with "states"
