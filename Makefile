@@ -10,7 +10,7 @@ OBJS     := $(SRC)/msckf_kernels.o $(SRC)/msckf_kalman.o $(SRC)/msckf_gate_mfma.
             $(SRC)/msckf_rccl.o $(SRC)/msckf_map.o
 HDRS     := $(SRC)/msckf_common.h $(SRC)/msckf_launch.h $(SRC)/msckf_gate_routes.h $(SRC)/msckf_subbatch.h $(SRC)/msckf_rchol.h include/msckf_hip.h include/msckf_frontend.h \
             include/msckf_replicas.h include/msckf_ransac.h include/msckf_pipeline.h include/msckf_lanes.h \
-            include/msckf_tracks.h include/msckf_map.h include/msckf_keyframes.h include/msckf_handoff.h $(SRC)/msckf_map_dev.h $(SRC)/msckf_map_api.inc \
+            include/msckf_tracks.h include/msckf_map.h include/msckf_keyframes.h include/msckf_handoff.h include/msckf_equalize.h $(SRC)/msckf_map_dev.h $(SRC)/msckf_map_api.inc \
             $(SRC)/msckf_handoff_dev.h
 
 all: $(LIB)

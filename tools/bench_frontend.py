@@ -29,7 +29,15 @@ one call per tracked frame of all lanes).  Its messages must be identical too;
 (b) and (c) alternate, two runs each, and the JSON line gains (c)'s
 lane-frames/s, its device calls per step and a cProfile split of its host time.
 
+--equalize {none,hist,clahe} sets FrontendConfig.equalize (include/msckf_equalize.h:
+the images equalised on the device at upload) for the single stream and for the
+lanes; --contrast C is the texture's contrast (default 110; 6 gives grey values
+120..136, in which the fixed FAST threshold finds nothing without equalisation).
+The JSON line names both.  --lanes S [--device-tracks] --stream-only runs the
+MultiImageProcessor once and nothing else: the process to put under a kernel trace.
+
     python tools/bench_frontend.py [--frames 60] [--device-pipeline] [--lanes S [--device-tracks]]
+                                   [--equalize none] [--contrast 110]
 """
 import argparse
 import cProfile
@@ -105,13 +113,13 @@ def stereo_leg(ip, c0, c1, pts, reps=30):
     return round(float(np.median(ms)), 3)
 
 
-def lane_streams(S, n, W, H):
+def lane_streams(S, n, W, H, contrast=110.0):
     """S streams of n rendered stereo pairs: texture seed, motion and disparity
     differ per lane.  As in the single stream the motion starts over every 40
     frames, so 40 pairs per lane are rendered."""
     streams = []
     for i in range(S):
-        f = fs.texture_fn(4 + i, W=W, H=H)
+        f = fs.texture_fn(4 + i, W=W, H=H, contrast=contrast)
         vx, vy, disp = 1.5 - 0.25 * (i % 5), -0.5 + 0.2 * (i % 4), 12.0 - 0.5 * (i % 3)
         pairs = [(fs.render(f, W, H, vx * k, vy * k), fs.render(f, W, H, vx * k - disp, vy * k))
                  for k in range(min(n, 40))]
@@ -222,7 +230,15 @@ def tracks_leg(cfg, streams, msgs_a, fb):
 
 def lanes_main(a, cfg, W, H):
     cfg = fe_mod.FrontendConfig(**{**vars(cfg), "device_pipeline": True})
-    streams = lane_streams(a.lanes, a.frames, W, H)       # rendered up front: not part of the timing
+    streams = lane_streams(a.lanes, a.frames, W, H, a.contrast)   # rendered up front: not part of the timing
+    if a.stream_only:
+        rate, msgs, calls = run_multi(fe_mod.FrontendConfig(**{**vars(cfg), "device_tracks": a.device_tracks}), streams)
+        print(json.dumps({"component": "stereo front-end (image.py) on GPU, lanes, one stream", "lanes": a.lanes,
+                          "frames_per_lane": a.frames, "equalize": a.equalize, "contrast": a.contrast,
+                          "device_tracks": a.device_tracks, "lane_frames_per_s": round(rate, 1),
+                          "device_calls_per_step": round(calls, 2),
+                          "features_per_frame": float(np.mean([len(m.vio_features) for lane in msgs for m in lane]))}))
+        return
     fa, msgs_a, calls_a = run_singles(cfg, streams)
     fb, msgs_b, calls_b = run_multi(cfg, streams)
     for i, (ma, mb) in enumerate(zip(msgs_a, msgs_b)):
@@ -235,7 +251,8 @@ def lanes_main(a, cfg, W, H):
     run_multi(cfg, streams, profile=prof)
     nfeat = float(np.mean([len(m.vio_features) for lane in msgs_b for m in lane]))
     print(json.dumps({"component": "stereo front-end (image.py) on GPU, lanes", "resolution": [W, H],
-                      "lanes": a.lanes, "frames_per_lane": a.frames, "messages_identical": True,
+                      "lanes": a.lanes, "frames_per_lane": a.frames, "equalize": a.equalize, "contrast": a.contrast,
+                      "messages_identical": True,
                       "lane_frames_per_s": {"single_processors": round(fa, 1), "multi_image_processor": round(fb, 1)},
                       "device_calls_per_step": {"single_processors": round(calls_a, 2),
                                                 "multi_image_processor": round(calls_b, 2)},
@@ -253,16 +270,21 @@ def main():
                     help="also run the stream with FrontendConfig.device_pipeline on")
     ap.add_argument("--device-tracks", action="store_true",
                     help="with --lanes: also run the MultiImageProcessor with FrontendConfig.device_tracks")
+    ap.add_argument("--equalize", choices=sorted(fe_mod.EQ_MODES), default="none",
+                    help="FrontendConfig.equalize: equalise every image on the device at upload")
+    ap.add_argument("--contrast", type=float, default=110.0, help="contrast of the synthetic texture")
+    ap.add_argument("--stream-only", action="store_true",
+                    help="with --lanes: one run of the MultiImageProcessor alone (what a kernel trace should see)")
     a = ap.parse_args()
-    if a.device_tracks and not a.lanes:
-        ap.error("--device-tracks needs --lanes")
+    if (a.device_tracks or a.stream_only) and not a.lanes:
+        ap.error("--device-tracks and --stream-only need --lanes")
     W, H = 752, 480
-    f = fs.texture_fn(4, W=W, H=H)
+    f = fs.texture_fn(4, W=W, H=H, contrast=a.contrast)
     K = np.array([450.0, 450.0, 376.0, 240.0])
     Ti1 = np.eye(4)
     Ti1[0, 3] = -0.11
     cfg = fe_mod.FrontendConfig(T_imu_cam0=np.eye(4), T_imu_cam1=Ti1, cam0_distortion_coeffs=np.zeros(4),
-                                cam1_distortion_coeffs=np.zeros(4), cam0_intrinsics=K, cam1_intrinsics=K)
+                                cam1_distortion_coeffs=np.zeros(4), cam0_intrinsics=K, cam1_intrinsics=K, equalize=a.equalize)
     if a.lanes:
         return lanes_main(a, cfg, W, H)
     frames = []
@@ -293,6 +315,7 @@ def main():
     t1 = time.perf_counter(); fe.lk(0, 1, pts, pts); ops["lk_200pts_ms"] = (time.perf_counter() - t1) * 1e3
     ransac = {"%dx100" % s: ransac_leg(fe, s) for s in (2, 22)}
     print(json.dumps({"component": "stereo front-end (image.py) on GPU", "resolution": [W, H],
+                      "equalize": a.equalize, "contrast": a.contrast,
                       "frames_per_s": round(fps, 1), **extra, "features_per_frame": float(np.mean(nfeat)),
                       "fast_keypoints_frame0": int(len(xy)), "op_wall_ms": {k: round(v, 3) for k, v in ops.items()},
                       "two_point_ransac_n_hyp7": ransac,

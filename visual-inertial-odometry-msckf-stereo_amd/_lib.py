@@ -184,6 +184,16 @@ HANDOFF_SIGS = {
 }
 HANDOFF_EXPORTED = tuple(HANDOFF_SIGS)
 
+# histogram equalisation / CLAHE at upload and the read-back of a slot (include/msckf_equalize.h),
+# same library and context
+EQ_NONE, EQ_HIST, EQ_CLAHE = 0, 1, 2
+EQ_MAX_TILES = 16
+EQUALIZE_SIGS = {
+    "mfe_upload_many_eq": (C.c_int, [_P, C.c_int, _I, _U8, _I, _F, C.c_int, C.c_int]),
+    "mfe_download": (C.c_int, [_P, C.c_int, C.c_int, _U8]),
+}
+EQUALIZE_EXPORTED = tuple(EQUALIZE_SIGS)
+
 # multi-GPU replica transport, RCCL (include/msckf_replicas.h), same library
 REPLICA_SIGS = {
     "msckf_rccl_unique_id": (C.c_int, [_U8]),
@@ -213,7 +223,7 @@ def load_library(path: str = LIB_PATH):
                                   list(FRONTEND_RANSAC_SIGS.items()) + list(FRONTEND_PIPELINE_SIGS.items()) +
                                   list(FRONTEND_LANES_SIGS.items()) + list(FRONTEND_TRACKS_SIGS.items()) +
                                   list(MAP_SIGS.items()) + list(KEYFRAME_SIGS.items()) + list(HANDOFF_SIGS.items()) +
-                                  list(REPLICA_SIGS.items())):
+                                  list(EQUALIZE_SIGS.items()) + list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

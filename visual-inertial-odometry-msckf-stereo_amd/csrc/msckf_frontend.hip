@@ -8,6 +8,9 @@
 // published OpenCV 4.x algorithms -- the same restatement as
 // oracle/frontend_oracle.py (test infrastructure), which the GPU tests check
 // them against:
+//   k_eq_*_sets      histogram equalisation / CLAHE of level 0 at upload (equalizeHist,
+//               clahe.cpp; include/msckf_equalize.h): LDS histograms per tile, the
+//               tiles' tables, the bilinear blend of four tables per pixel
 //   k_pyrdown_sets   Gaussian pyramid level (pyrDown, 5x5 [1 4 6 4 1]^2, REFLECT_101)
 //   k_scharr_sets    Scharr derivatives of a level (calcScharrDeriv)
 //   k_fast_sets      FAST 9/16 segment test + corner score (fast.cpp, fast_score.cpp)
@@ -53,6 +56,7 @@
 #include "../../include/msckf_ransac.h"
 #include "../../include/msckf_handoff.h"
 #include "../../include/msckf_tracks.h"
+#include "../../include/msckf_equalize.h"
 #include "msckf_handoff_dev.h"
 
 namespace {
@@ -163,6 +167,175 @@ __global__ void __launch_bounds__(256) k_image_scatter_sets(const Pyr* __restric
         if (16 * t < bytes) ((uint4*)dst)[t] = ((const uint4*)src)[t];
     } else if (t < bytes) {
         dst[t] = src[t];
+    }
+}
+
+// ----------------------------------------------------------- equalisation --
+// include/msckf_equalize.h: mfe_upload_many_eq's three launches between the packed block and
+// the pyramids.  blockIdx.z = the image of the call; its mode is read per image.
+constexpr int EQ_HCH = 64;      // MFE_EQ_HIST: partial histograms per image
+constexpr int EQ_COPIES = 16;   // interleaved copies of a workgroup's histogram in LDS
+
+struct EqArgs {
+    const Pyr* tab;
+    const int32_t* slots;
+    const int32_t* mode;     // [n]
+    const int32_t* clip;     // [n], bin limit of a CLAHE image (0: none)
+    const uint8_t* images;   // the packed block's [n][H][W]
+    unsigned* hist;          // [n][units][256]
+    uint8_t* lut;            // [n][tiles][256]
+    int W, H, tiles_x, tiles_y, tw, th;
+    int units;               // max(tiles, EQ_HCH)
+};
+
+// One workgroup per histogram: tile blockIdx.x of a CLAHE image (over the padded image,
+// REFLECT_101), or the blockIdx.x-th of EQ_HCH equal runs of a HIST image's pixels.  Lane l adds
+// into copy l % 16 of the bin, the copies of a bin in consecutive words: the lanes of a wave that
+// meet in one bin (a low-contrast image) spread over 16 addresses and banks.  Integer adds: the
+// order does not matter.
+__global__ void __launch_bounds__(256) k_eq_hist_sets(EqArgs a) {
+    const int img = blockIdx.z, u = blockIdx.x, mode = a.mode[img];
+    if (mode == MFE_EQ_NONE || u >= (mode == MFE_EQ_HIST ? EQ_HCH : a.tiles_x * a.tiles_y)) return;
+    __shared__ unsigned h[256 * EQ_COPIES];
+    for (int i = threadIdx.x; i < 256 * EQ_COPIES; i += 256) h[i] = 0;
+    __syncthreads();
+    const uint8_t* src = a.images + (size_t)img * a.W * a.H;
+    const int c = threadIdx.x & (EQ_COPIES - 1);
+    if (mode == MFE_EQ_HIST) {
+        const size_t px = (size_t)a.W * a.H;
+        const size_t lo = px * u / EQ_HCH, hi = px * (u + 1) / EQ_HCH;
+        for (size_t i = lo + threadIdx.x; i < hi; i += 256) atomicAdd(&h[src[i] * EQ_COPIES + c], 1u);
+    } else {
+        const int x0 = (u % a.tiles_x) * a.tw, y0 = (u / a.tiles_x) * a.th;
+        const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
+        for (int j = ly; j < a.th; j += 8) {
+            const uint8_t* row = src + (size_t)refl101(y0 + j, a.H) * a.W;
+            for (int i = lx; i < a.tw; i += 32) atomicAdd(&h[row[refl101(x0 + i, a.W)] * EQ_COPIES + c], 1u);
+        }
+    }
+    __syncthreads();
+    const int k = threadIdx.x;
+    unsigned s = 0;
+#pragma unroll
+    for (int j = 0; j < EQ_COPIES; ++j) s += h[k * EQ_COPIES + ((j + k) & (EQ_COPIES - 1))];
+    a.hist[((size_t)img * a.units + u) * 256 + k] = s;
+}
+
+// inclusive sum over the 256 threads of a workgroup; sh[255] holds the total until the next barrier
+__device__ __forceinline__ int eq_scan256(int v, int* sh) {
+    const int k = threadIdx.x;
+    sh[k] = v;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const int t = k >= d ? sh[k - d] : 0;
+        __syncthreads();
+        sh[k] += t;
+        __syncthreads();
+    }
+    return sh[k];
+}
+
+__device__ __forceinline__ uint8_t eq_sat(float x) {   // saturate_cast<uchar>: half to even, clipped
+    return (uint8_t)(int)fminf(fmaxf(rintf(x), 0.f), 255.f);
+}
+
+// One workgroup per table, thread k = bin k: a CLAHE tile's clipped and redistributed histogram,
+// or (blockIdx.x = 0 only) a HIST image's, summed over its EQ_HCH parts, from the first non-empty bin.
+__global__ void __launch_bounds__(256) k_eq_lut_sets(EqArgs a) {
+#pragma clang fp contract(off)
+    const int img = blockIdx.z, t = blockIdx.x, mode = a.mode[img], k = threadIdx.x;
+    if (mode == MFE_EQ_NONE || (mode == MFE_EQ_HIST && t > 0)) return;
+    __shared__ int sh[256];
+    __shared__ int first[2];
+    const unsigned* hist = a.hist + (size_t)img * a.units * 256;
+    uint8_t* lut = a.lut + ((size_t)img * a.tiles_x * a.tiles_y + t) * 256;
+    if (mode == MFE_EQ_HIST) {
+        int h = 0;
+        for (int u = 0; u < EQ_HCH; ++u) h += (int)hist[u * 256 + k];
+        const int cum = eq_scan256(h, sh);
+        if (h > 0 && cum == h) {   // the first non-empty bin: one thread
+            first[0] = k;
+            first[1] = h;
+        }
+        __syncthreads();
+        const int px = a.W * a.H, i = first[0], hi = first[1];
+        if (hi == px) {            // a constant image stays as it is
+            lut[k] = (uint8_t)k;
+        } else {
+            const float scale = 255.f / (float)(px - hi);
+            lut[k] = k <= i ? (uint8_t)0 : eq_sat((float)(cum - hi) * scale);
+        }
+        return;
+    }
+    int h = (int)hist[t * 256 + k];
+    const int clip = a.clip[img];
+    if (clip > 0) {
+        eq_scan256(h > clip ? h - clip : 0, sh);
+        const int excess = sh[255];
+        __syncthreads();
+        h = min(h, clip) + excess / 256;
+        const int residual = excess % 256;
+        if (residual) {
+            const int step = max(256 / residual, 1);
+            if (k % step == 0 && k / step < residual) ++h;
+        }
+    }
+    const int cum = eq_scan256(h, sh);
+    const float lut_scale = 255.f / (float)(a.tw * a.th);
+    lut[k] = eq_sat((float)cum * lut_scale);
+}
+
+// Packed image -> level 0 of its slot.  One workgroup per interpolation cell (cx, cy), 0 <= cx <=
+// tiles_x: the pixels with floor(txf) = cx - 1 and floor(tyf) = cy - 1, which share their (at most)
+// four tiles; the four tables in LDS.  The cell's extent is taken one pixel wider than the exact
+// bounds and every pixel tested with the float expression the blend itself uses, so each pixel
+// is written by exactly one workgroup whatever the rounding of x * (1.f / tw).  HIST and NONE
+// images go through the same cells with one table and none.
+__global__ void __launch_bounds__(256) k_eq_apply_sets(EqArgs a) {
+#pragma clang fp contract(off)
+    const int img = blockIdx.z, mode = a.mode[img];
+    const int cx = blockIdx.x % (a.tiles_x + 1), cy = blockIdx.x / (a.tiles_x + 1);
+    const uint8_t* src = a.images + (size_t)img * a.W * a.H;
+    uint8_t* dst = a.tab[a.slots[img]].lv[0].img;
+    __shared__ uint8_t l[4][256];
+    if (mode != MFE_EQ_NONE) {
+        const uint8_t* lut = a.lut + (size_t)img * a.tiles_x * a.tiles_y * 256;
+        const int tx1 = max(cx - 1, 0), tx2 = min(cx, a.tiles_x - 1);
+        const int ty1 = max(cy - 1, 0), ty2 = min(cy, a.tiles_y - 1);
+        const int k = threadIdx.x;
+        if (mode == MFE_EQ_HIST) {
+            l[0][k] = lut[k];
+        } else {
+            l[0][k] = lut[(ty1 * a.tiles_x + tx1) * 256 + k];
+            l[1][k] = lut[(ty1 * a.tiles_x + tx2) * 256 + k];
+            l[2][k] = lut[(ty2 * a.tiles_x + tx1) * 256 + k];
+            l[3][k] = lut[(ty2 * a.tiles_x + tx2) * 256 + k];
+        }
+        __syncthreads();
+    }
+    const int x_lo = max(((2 * cx - 1) * a.tw) / 2 - 1, 0), x_hi = min(((2 * cx + 1) * a.tw) / 2 + 1, a.W - 1);
+    const int y_lo = max(((2 * cy - 1) * a.th) / 2 - 1, 0), y_hi = min(((2 * cy + 1) * a.th) / 2 + 1, a.H - 1);
+    const float inv_tw = 1.f / (float)a.tw, inv_th = 1.f / (float)a.th;
+    for (int y = y_lo + (int)(threadIdx.x >> 5); y <= y_hi; y += 8) {
+        const float tyf = (float)y * inv_th - 0.5f, fy = floorf(tyf);
+        if ((int)fy != cy - 1) continue;
+        const float ya = tyf - fy, ya1 = 1.f - ya;
+        for (int x = x_lo + (int)(threadIdx.x & 31); x <= x_hi; x += 32) {
+            const float txf = (float)x * inv_tw - 0.5f, fx = floorf(txf);
+            if ((int)fx != cx - 1) continue;
+            const size_t o = (size_t)y * a.W + x;
+            const int v = src[o];
+            if (mode == MFE_EQ_NONE) {
+                dst[o] = (uint8_t)v;
+            } else if (mode == MFE_EQ_HIST) {
+                dst[o] = l[0][v];
+            } else {
+                const float xa = txf - fx, xa1 = 1.f - xa;
+                const float top = (float)l[0][v] * xa1 + (float)l[1][v] * xa;
+                const float bot = (float)l[2][v] * xa1 + (float)l[3][v] * xa;
+                dst[o] = eq_sat(top * ya1 + bot * ya);
+            }
+        }
     }
 }
 
@@ -1390,6 +1563,10 @@ struct mfe_ctx {
     int32_t* d_slot = nullptr;
     GridWork work{};
     int work_cap = 0;
+    // mfe_upload_many_eq's histograms and tables (msckf_equalize.h), grown to the largest call seen
+    unsigned* eq_hist = nullptr;
+    uint8_t* eq_lut = nullptr;
+    size_t eq_hist_cap = 0, eq_lut_cap = 0;
     // the track tables (msckf_tracks.h), one block of the context's allocations; the host's
     // record of each lane's current table and its row count
     TrkDev trk{};
@@ -1590,6 +1767,8 @@ int mfe_destroy(mfe_ctx_t* c) {
     if (c->rs_dev) (void)hipFree(c->rs_dev);
     if (c->rs_host) (void)hipHostFree(c->rs_host);
     free_grid_work(c);
+    if (c->eq_hist) (void)hipFree(c->eq_hist);
+    if (c->eq_lut) (void)hipFree(c->eq_lut);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return 0;
@@ -1814,6 +1993,94 @@ int mfe_upload_many(mfe_ctx_t* c, int n, const int32_t* slots, const uint8_t* im
     launch_pyramids(c, dslots, n);
     MFE_HIP(hipGetLastError());
     MFE_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// ------------------------------------------- equalisation (msckf_equalize.h) --
+int mfe_upload_many_eq(mfe_ctx_t* c, int n, const int32_t* slots, const uint8_t* images, const int32_t* mode,
+                       const float* clip_limit, int tiles_x, int tiles_y) {
+    if (!c || !images || !mode) MFE_FAIL(-1, "null argument");
+    if (n < 1 || n > c->nslot) MFE_FAIL(-1, "n = %d outside [1, %d]", n, c->nslot);
+    if (check_slots(c, n, slots, "slots")) return -1;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j)
+            if (slots[i] == slots[j]) MFE_FAIL(-1, "slot %d is named twice (images %d and %d)", slots[i], j, i);
+    if (tiles_x < 1 || tiles_x > MFE_EQ_MAX_TILES) MFE_FAIL(-1, "tiles_x = %d outside [1, %d]", tiles_x, MFE_EQ_MAX_TILES);
+    if (tiles_y < 1 || tiles_y > MFE_EQ_MAX_TILES) MFE_FAIL(-1, "tiles_y = %d outside [1, %d]", tiles_y, MFE_EQ_MAX_TILES);
+    if (c->W < tiles_x) MFE_FAIL(-1, "tiles_x = %d above the image width %d", tiles_x, c->W);
+    if (c->H < tiles_y) MFE_FAIL(-1, "tiles_y = %d above the image height %d", tiles_y, c->H);
+    // the tile of the padded image (clahe.cpp: both sides are padded as soon as one does not divide)
+    int Wp = c->W, Hp = c->H;
+    if (c->W % tiles_x || c->H % tiles_y) {
+        Wp += tiles_x - c->W % tiles_x;
+        Hp += tiles_y - c->H % tiles_y;
+    }
+    const int tw = Wp / tiles_x, th = Hp / tiles_y, tiles = tiles_x * tiles_y;
+    const double area = (double)tw * th;
+    std::vector<int32_t> clip(n, 0);
+    for (int i = 0; i < n; ++i) {
+        if (mode[i] != MFE_EQ_NONE && mode[i] != MFE_EQ_HIST && mode[i] != MFE_EQ_CLAHE)
+            MFE_FAIL(-1, "unknown equalisation mode %d (mode[%d])", mode[i], i);
+        if (mode[i] != MFE_EQ_CLAHE) continue;
+        if (!clip_limit) MFE_FAIL(-1, "null clip_limit with a CLAHE image (mode[%d])", i);
+        if (std::isnan(clip_limit[i])) MFE_FAIL(-1, "clip_limit[%d] is NaN", i);
+        if (clip_limit[i] > 0) {   // no bin holds more than area: a limit above it cuts nothing
+            const double cl = std::min((double)clip_limit[i] * area / 256.0, area);
+            clip[i] = std::max((int32_t)cl, 1);
+        }
+    }
+    MFE_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t px = (size_t)c->W * c->H;
+    const int units = std::max(tiles, EQ_HCH);
+    const size_t hist_bytes = (size_t)n * units * 256 * sizeof(unsigned), lut_bytes = (size_t)n * tiles * 256;
+    if (hist_bytes > c->eq_hist_cap) {   // nothing is in flight: every call ends with a synchronisation
+        if (c->eq_hist) (void)hipFree(c->eq_hist);
+        c->eq_hist = nullptr;
+        c->eq_hist_cap = 0;
+        MFE_HIP(hipMalloc((void**)&c->eq_hist, hist_bytes));
+        c->eq_hist_cap = hist_bytes;
+    }
+    if (lut_bytes > c->eq_lut_cap) {
+        if (c->eq_lut) (void)hipFree(c->eq_lut);
+        c->eq_lut = nullptr;
+        c->eq_lut_cap = 0;
+        MFE_HIP(hipMalloc((void**)&c->eq_lut, lut_bytes));
+        c->eq_lut_cap = lut_bytes;
+    }
+    Block b;
+    const size_t o_slots = b.add(4 * (size_t)n), o_mode = b.add(4 * (size_t)n), o_clip = b.add(4 * (size_t)n),
+                 o_img = b.add(px * n);
+    if (int rc = grow_scratch(c, b.size)) return rc;
+    unsigned char *hin = c->rs_host, *d = c->rs_dev;
+    memcpy(hin + o_slots, slots, 4 * (size_t)n);
+    memcpy(hin + o_mode, mode, 4 * (size_t)n);
+    memcpy(hin + o_clip, clip.data(), 4 * (size_t)n);
+    memcpy(hin + o_img, images, px * n);
+    MFE_HIP(hipMemcpyAsync(d, hin, b.size, hipMemcpyHostToDevice, s));
+    const int32_t* dslots = (const int32_t*)(d + o_slots);
+    EqArgs a{};
+    a.tab = c->d_pyr; a.slots = dslots; a.mode = (const int32_t*)(d + o_mode); a.clip = (const int32_t*)(d + o_clip);
+    a.images = d + o_img; a.hist = c->eq_hist; a.lut = c->eq_lut;
+    a.W = c->W; a.H = c->H; a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.tw = tw; a.th = th; a.units = units;
+    hipLaunchKernelGGL(k_eq_hist_sets, dim3(units, 1, n), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_eq_lut_sets, dim3(tiles, 1, n), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_eq_apply_sets, dim3((tiles_x + 1) * (tiles_y + 1), 1, n), dim3(256), 0, s, a);
+    launch_pyramids(c, dslots, n);
+    MFE_HIP(hipGetLastError());
+    MFE_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int mfe_download(mfe_ctx_t* c, int slot, int level, uint8_t* out) {
+    if (!c || !out) MFE_FAIL(-1, "null argument");
+    const int32_t sl = slot;
+    if (check_slots(c, 1, &sl, "slot")) return -1;
+    if (level < 0 || level > c->max_level) MFE_FAIL(-1, "level %d outside [0, %d]", level, c->max_level);
+    MFE_HIP(hipSetDevice(c->device));
+    const Level& L = c->slots[slot].lv[level];
+    MFE_HIP(hipMemcpyAsync(out, L.img, (size_t)L.w * L.h, hipMemcpyDeviceToHost, c->stream));
+    MFE_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -26,6 +26,9 @@ published message -- and every image operator runs in the HIP kernels of
                                                 tables live on the device and a tracked frame of
                                                 all lanes is ONE call (mfe_tracks_step,
                                                 include/msckf_tracks.h), opt-in
+  (none: the image as it comes)                 FrontendConfig.equalize: equalizeHist / CLAHE on the
+                                                device at upload (mfe_upload_many_eq,
+                                                include/msckf_equalize.h), opt-in
 
 cv2 is absent here and on the GPU box: the kernels restate the published
 OpenCV 4.x algorithms (oracle/frontend_oracle.py), parity unpinned against cv2
@@ -142,6 +145,13 @@ class FrontendConfig:
     # whole tracked frame of all lanes as one call (include/msckf_tracks.h); needs device_pipeline;
     # the published messages are the same
     device_tracks: bool = False
+    # not in the reference: every uploaded image is equalised on the device before its pyramid is
+    # built (include/msckf_equalize.h), "none" | "hist" (cv2.equalizeHist) | "clahe" (cv2.createCLAHE
+    # with the two fields below, OpenCV's defaults); detection, tracking and the stereo match then
+    # read the equalised image
+    equalize: str = "none"
+    clahe_clip_limit: float = 40.0
+    clahe_tiles: tuple = (8, 8)
 
     @property
     def grid_num(self):
@@ -157,6 +167,35 @@ class FrontendConfig:
             except AttributeError:
                 pass
         return cls(**kw)
+
+
+EQ_MODES = {"none": _lib.EQ_NONE, "hist": _lib.EQ_HIST, "clahe": _lib.EQ_CLAHE}
+
+
+def _check_tiles(tiles, W, H):
+    """clahe_tiles as (tiles_x, tiles_y) of ints within msckf_equalize.h's limits for a W x H image."""
+    try:
+        tx, ty = (int(v) for v in tiles)
+        if (tx, ty) != tuple(tiles):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("clahe_tiles = %r, expected two integers (tiles_x, tiles_y)" % (tiles,)) from None
+    if not (1 <= tx <= min(_lib.EQ_MAX_TILES, W) and 1 <= ty <= min(_lib.EQ_MAX_TILES, H)):
+        raise ValueError("clahe_tiles = %r outside [1, %d] or above the image size %dx%d"
+                         % (tiles, _lib.EQ_MAX_TILES, W, H))
+    return tx, ty
+
+
+def _equalize_of(config, W, H):
+    """The equalisation argument of Frontend.upload for a config: None for
+    "none", else (mode, clip_limit, (tiles_x, tiles_y)); ValueError on a bad field."""
+    if config.equalize not in EQ_MODES:
+        raise ValueError("equalize = %r, expected one of %s" % (config.equalize, sorted(EQ_MODES)))
+    tiles = _check_tiles(config.clahe_tiles, W, H)
+    clip = float(config.clahe_clip_limit)
+    if np.isnan(clip):
+        raise ValueError("clahe_clip_limit is NaN")
+    return None if config.equalize == "none" else (config.equalize, clip, tiles)
 
 
 class FeatureMetaData:
@@ -227,11 +266,26 @@ class Frontend:
         except Exception:
             pass
 
-    def upload(self, slot, image):
+    def upload(self, slot, image, equalize=None):
+        """mfe_upload; with ``equalize`` = (mode, clip_limit, (tiles_x, tiles_y)),
+        mode "none" | "hist" | "clahe", the image is equalised on the device
+        first (msckf_equalize.h): the set call ``upload_many`` with one image."""
         img = np.ascontiguousarray(image, np.uint8)
         if img.shape != (self.H, self.W):
             raise ValueError("image shape %s, context %dx%d" % (img.shape, self.W, self.H))
+        if equalize is not None:
+            mode, clip, tiles = equalize
+            return self.upload_many([slot], img[None], ([mode], [clip], tiles))
         self._check(self.lib.mfe_upload(self.h, slot, img.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def download(self, slot, level=0):
+        """mfe_download: level ``level`` of a slot as the device holds it, uint8 (h_l, w_l)."""
+        w, h = self.W, self.H
+        for _ in range(max(int(level), 0)):
+            w, h = (w + 1) // 2, (h + 1) // 2
+        out = np.zeros((h, w), np.uint8)
+        self._check(self.lib.mfe_download(self.h, int(slot), int(level), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
 
     def fast(self, slot, threshold, mask=None, max_kp=1 << 16):
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
@@ -380,15 +434,33 @@ class Frontend:
             raise ValueError("%d points in all sets exceed the context's %d" % (off[-1], self.max_points))
         return off
 
-    def upload_many(self, slots, images):
+    def upload_many(self, slots, images, equalize=None):
         """mfe_upload_many: ``images[i]`` into ``slots[i]`` (distinct), all
-        pyramids built by launches over the image index."""
+        pyramids built by launches over the image index.  With ``equalize`` =
+        (modes, clip_limits, (tiles_x, tiles_y)), one mode ("none" | "hist" |
+        "clahe", or its MFE_EQ_* number) and one clip limit per image, it is
+        mfe_upload_many_eq (msckf_equalize.h): each image is equalised on the
+        device before its pyramid is built."""
         sl = np.ascontiguousarray(slots, np.int32)
         imgs = np.ascontiguousarray(images, np.uint8)
         if imgs.shape != (len(sl), self.H, self.W):
             raise ValueError("images of shape %s, expected %s" % (imgs.shape, (len(sl), self.H, self.W)))
-        self._check(self.lib.mfe_upload_many(self.h, len(sl), sl.ctypes.data_as(_I32P),
-                                             imgs.ctypes.data_as(C.POINTER(C.c_uint8))))
+        if equalize is None:
+            self._check(self.lib.mfe_upload_many(self.h, len(sl), sl.ctypes.data_as(_I32P),
+                                                 imgs.ctypes.data_as(C.POINTER(C.c_uint8))))
+            return
+        modes, clips, tiles = equalize
+        try:
+            mode = np.array([EQ_MODES[m] if isinstance(m, str) else int(m) for m in modes], np.int32)
+        except KeyError as e:
+            raise ValueError("equalisation mode %s, expected one of %s" % (e, sorted(EQ_MODES))) from None
+        clip = np.ascontiguousarray(clips, np.float32).reshape(-1)
+        if len(mode) != len(sl) or len(clip) != len(sl):
+            raise ValueError("%d modes and %d clip limits for %d images" % (len(mode), len(clip), len(sl)))
+        self._check(self.lib.mfe_upload_many_eq(self.h, len(sl), sl.ctypes.data_as(_I32P),
+                                                imgs.ctypes.data_as(C.POINTER(C.c_uint8)), mode.ctypes.data_as(_I32P),
+                                                clip.ctypes.data_as(C.POINTER(C.c_float)), int(tiles[0]),
+                                                int(tiles[1])))
 
     def lk_sets(self, sets, win=15, max_level=3, max_iter=30, eps=0.01):
         """mfe_lk_sets.  ``sets``: (slot_prev, slot_next, prev_pts, next_pts) per
@@ -661,6 +733,7 @@ class ImageProcessor:
         self.R_cam1_imu = self.T_cam1_imu[:3, :3]
         self.t_cam1_imu = self.T_cam1_imu[:3, 3]
         W, H = int(self.cam0_resolution[0]), int(self.cam0_resolution[1])
+        self._equalize = _equalize_of(config, W, H)   # None: the uploads stay as they are
         self.fe = fe if fe is not None else Frontend(W, H, nslot=3, max_level=config.pyramid_levels,
                                                      max_points=1 << 16, device=device)
         self._slot_prev, self._slot_c0, self._slot_c1 = slot_base, slot_base + 1, slot_base + 2
@@ -860,7 +933,8 @@ class ImageProcessor:
     # _match_steps (one stereo_match request, or six single calls composed on the spot)
     # and _add_new_steps (a fast_grid request, or a fast request and the host sieve).
     # Requests:
-    #   ("upload", [(slot, image), ...])                                     -> None
+    #   ("upload", [(slot, image), ...][, (mode, clip_limit, tiles)])        -> None  (the third item
+    #                                                  only with config.equalize: Frontend.upload's)
     #   ("fast", slot, threshold[, mask])                                    -> Frontend.fast
     #   ("lk", slot_prev, slot_next, prev_pts, next_pts)                     -> Frontend.lk
     #   ("stereo_match", slot0, slot1, pts, cam0, cam1, R_guess, E, thr)     -> Frontend.stereo_match
@@ -881,7 +955,7 @@ class ImageProcessor:
         kind = req[0]
         if kind == "upload":
             for slot, image in req[1]:
-                self.fe.upload(slot, image)
+                self.fe.upload(slot, image, *req[2:])
             return None
         if kind == "fast":
             return self.fe.fast(*req[1:])
@@ -916,8 +990,11 @@ class ImageProcessor:
             self._end_frame()
 
     def _upload_steps(self):
-        yield ("upload", [(self._slot_c0, self.cam0_curr_img_msg.image),
-                          (self._slot_c1, self.cam1_curr_img_msg.image)])
+        pairs = [(self._slot_c0, self.cam0_curr_img_msg.image), (self._slot_c1, self.cam1_curr_img_msg.image)]
+        if self._equalize is None:
+            yield ("upload", pairs)
+        else:
+            yield ("upload", pairs, self._equalize)
 
     def _first_frame_steps(self):
         xy, resp = yield ("fast", self._slot_c0, self.config.fast_threshold)
@@ -1114,7 +1191,10 @@ class MultiImageProcessor:
 
     Lanes may differ in calibration, grid_min / grid_max_feature_num,
     stereo_threshold and the RANSAC switch, threshold and seed; they must
-    agree on the resolution and the fields of ``_SHARED_FIELDS``.
+    agree on the resolution and the fields of ``_SHARED_FIELDS``.  Each lane
+    has its own ``equalize`` mode and clip limit (msckf_equalize.h: the upload
+    becomes mfe_upload_many_eq as soon as one lane of the step equalises, still
+    one call); the lanes agree on ``clahe_tiles``.
 
     With ``device_tracks`` in every lane's config the per-feature bookkeeping
     leaves the host: the lanes' track tables live on the device
@@ -1147,6 +1227,11 @@ class MultiImageProcessor:
                 if getattr(c, f) != getattr(cfgs[0], f):
                     raise ValueError("lane %d: %s = %r differs from lane 0's %r"
                                      % (i, f, getattr(c, f), getattr(cfgs[0], f)))
+            # mfe_upload_many_eq has one tile grid per call
+            _equalize_of(c, *res(c)[0])
+            if _check_tiles(c.clahe_tiles, *res(c)[0]) != _check_tiles(cfgs[0].clahe_tiles, *res(c)[0]):
+                raise ValueError("lane %d: clahe_tiles = %r differs from lane 0's %r"
+                                 % (i, c.clahe_tiles, cfgs[0].clahe_tiles))
         # device_tracks: all lanes or none, and what mfe_tracks_step shares between lanes
         self.device_tracks = bool(cfgs[0].device_tracks)
         ransac = [i for i, c in enumerate(cfgs) if c.ransac_enabled]
@@ -1299,7 +1384,12 @@ class MultiImageProcessor:
         self.launches[kind] += 1
         if kind == "upload":
             pairs = [p for r in reqs for p in r[1]]
-            fe.upload_many([s for s, _ in pairs], np.stack([np.asarray(im, np.uint8) for _, im in pairs]))
+            eq = ()
+            if any(len(r) > 2 for r in reqs):   # some lane equalises: a mode and a clip limit per image
+                per = [(r[2] if len(r) > 2 else ("none", 0.0, None), len(r[1])) for r in reqs]
+                eq = (([e[0] for e, k in per for _ in range(k)], [e[1] for e, k in per for _ in range(k)],
+                       next(e[2] for e, _ in per if e[2] is not None)),)   # the lanes agree on the tiles
+            fe.upload_many([s for s, _ in pairs], np.stack([np.asarray(im, np.uint8) for _, im in pairs]), *eq)
             return [None] * len(reqs)
         if kind == "lk":
             return fe.lk_sets([r[1:] for r in reqs], **self.lk_kw)
