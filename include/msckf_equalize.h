@@ -78,6 +78,12 @@
  *
  * Synchronises and copies level `level` (0 .. the context's max_level) of a
  * slot, w_l x h_l bytes with w_l = ceil(w_{l-1} / 2), to out.
+ *
+ * mfe_download_deriv
+ *
+ * The same for the level's two Scharr planes (calcScharrDeriv of the level's
+ * image, what LK reads): w_l x h_l int16 each, to ix and iy.  Same argument
+ * checks and errors; a null ix or iy is an error (-1), nothing is written.
  */
 #ifndef MSCKF_EQUALIZE_H
 #define MSCKF_EQUALIZE_H
@@ -101,6 +107,8 @@ int mfe_upload_many_eq(mfe_ctx_t* ctx, int n, const int32_t* slots, const uint8_
                        const int32_t* mode, const float* clip_limit, int tiles_x, int tiles_y);
 /* level `level` (0..max_level) of a slot as the device holds it, w_l x h_l bytes */
 int mfe_download(mfe_ctx_t* ctx, int slot, int level, uint8_t* out);
+/* the Scharr planes of that level as the device holds them, w_l x h_l int16 each */
+int mfe_download_deriv(mfe_ctx_t* ctx, int slot, int level, int16_t* ix, int16_t* iy);
 
 #ifdef __cplusplus
 }

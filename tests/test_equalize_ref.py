@@ -142,7 +142,7 @@ def test_equalize_exports_and_binding():
     """include/msckf_equalize.h is exported by the same library and typed one
     to one by the binding (its own table)."""
     syms = header_symbols("msckf_equalize.h", "mfe_")
-    assert syms == ["mfe_download", "mfe_upload_many_eq"]
+    assert syms == ["mfe_download", "mfe_download_deriv", "mfe_upload_many_eq"]
     assert sorted(_lib.EQUALIZE_EXPORTED) == syms
     assert not set(syms) & (set(_lib.FRONTEND_EXPORTED) | set(_lib.FRONTEND_LANES_EXPORTED) |
                             set(_lib.FRONTEND_PIPELINE_EXPORTED) | set(_lib.TRACKS_EXPORTED))

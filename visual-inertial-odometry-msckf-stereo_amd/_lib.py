@@ -191,6 +191,7 @@ EQ_MAX_TILES = 16
 EQUALIZE_SIGS = {
     "mfe_upload_many_eq": (C.c_int, [_P, C.c_int, _I, _U8, _I, _F, C.c_int, C.c_int]),
     "mfe_download": (C.c_int, [_P, C.c_int, C.c_int, _U8]),
+    "mfe_download_deriv": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int16), C.POINTER(C.c_int16)]),
 }
 EQUALIZE_EXPORTED = tuple(EQUALIZE_SIGS)
 

@@ -2084,6 +2084,20 @@ int mfe_download(mfe_ctx_t* c, int slot, int level, uint8_t* out) {
     return 0;
 }
 
+int mfe_download_deriv(mfe_ctx_t* c, int slot, int level, int16_t* ix, int16_t* iy) {
+    if (!c || !ix || !iy) MFE_FAIL(-1, "null argument");
+    const int32_t sl = slot;
+    if (check_slots(c, 1, &sl, "slot")) return -1;
+    if (level < 0 || level > c->max_level) MFE_FAIL(-1, "level %d outside [0, %d]", level, c->max_level);
+    MFE_HIP(hipSetDevice(c->device));
+    const Level& L = c->slots[slot].lv[level];
+    const size_t bytes = (size_t)L.w * L.h * sizeof(int16_t);
+    MFE_HIP(hipMemcpyAsync(ix, L.ix, bytes, hipMemcpyDeviceToHost, c->stream));
+    MFE_HIP(hipMemcpyAsync(iy, L.iy, bytes, hipMemcpyDeviceToHost, c->stream));
+    MFE_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 int mfe_lk_sets(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const int32_t* slot_prev,
                 const int32_t* slot_next, const float* prev_pts, float* next_pts, uint8_t* status, int win,
                 int max_level, int max_iter, double eps) {

@@ -287,6 +287,18 @@ class Frontend:
         self._check(self.lib.mfe_download(self.h, int(slot), int(level), out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
 
+    def download_deriv(self, slot, level=0):
+        """mfe_download_deriv: the Scharr planes (ix, iy) of level ``level`` of a slot
+        as the device holds them, int16 (h_l, w_l) each."""
+        w, h = self.W, self.H
+        for _ in range(max(int(level), 0)):
+            w, h = (w + 1) // 2, (h + 1) // 2
+        ix, iy = np.zeros((h, w), np.int16), np.zeros((h, w), np.int16)
+        i16 = C.POINTER(C.c_int16)
+        self._check(self.lib.mfe_download_deriv(self.h, int(slot), int(level), ix.ctypes.data_as(i16),
+                                                iy.ctypes.data_as(i16)))
+        return ix, iy
+
     def fast(self, slot, threshold, mask=None, max_kp=1 << 16):
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
         xy = np.zeros((max_kp, 2), np.float32)
