@@ -15,7 +15,9 @@ regions.
 feeds the frames as array messages (msckf.FeatureArrays); --device-keyframes
 (with --device-map) chooses a prune frame's cam states on the device
 (msckf_keyframes.h); --profile prints a cProfile split of the batched replay to
-stderr.
+stderr.  --landmarks {host,device} keeps the landmark archive and --odometry
+reads the pose covariance with every frame (msckf_odometry.h); --kernel-times
+adds the stage times of a second, untimed replay.
 
 On N GPUs every rank replays its share of the sequences (replicas.shard) on
 its own device; the replicas' host TCP hub (msckf_amd.replicas, no RCCL:
@@ -49,16 +51,24 @@ def main():
     ap.add_argument("--device-map", action="store_true")
     ap.add_argument("--device-keyframes", action="store_true")
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--landmarks", choices=("host", "device"), default=None,
+                    help="keep the landmark archive (msckf_odometry.h): in numpy, or on the device (needs --device-map)")
+    ap.add_argument("--odometry", action="store_true", help="the frames' reads bring the pose covariance along")
+    ap.add_argument("--kernel-times", action="store_true",
+                    help="a second, untimed batched replay with every stage timed (msckf_kernel_times)")
     a = ap.parse_args()
     if a.device_keyframes and not a.device_map:
         ap.error("--device-keyframes needs --device-map")
+    if a.landmarks == "device" and not a.device_map:
+        ap.error("--landmarks device needs --device-map")
+    opt = dict(landmarks=a.landmarks, odometry=a.odometry) if a.landmarks or a.odometry else {}
     dtype = np.float32 if a.fp32 else np.float64
     grp = replicas.init()
     mine = replicas.shard(list(range(a.seqs)), grp.rank, grp.world)
     streams = [FeatureStream.from_synthetic(synth.make_sequence(a.frames, 100 + i)) for i in mine]
     n_frames = sum(s.n_frames for s in streams)
     multi = MultiMSCKF(len(streams), dtype=dtype, device=grp.local_rank,
-                       device_map=a.device_map, device_keyframes=a.device_keyframes) if streams else None
+                       device_map=a.device_map, device_keyframes=a.device_keyframes, **opt) if streams else None
     # the messages are the front-end's output: built before either timed
     # region (as the bench's ATE leg does), fresh objects for each run
     msgs = [s.messages(arrays=a.device_map) for s in streams]
@@ -77,14 +87,29 @@ def main():
         pstats.Stats(prof, stream=sys.stderr).sort_stats("tottime").print_stats(25)
     total_frames = grp.sum_over_ranks(n_frames)
     launches = dict(multi.launches) if multi else {}
+    archived = [int(multi.landmarks(i).next_seq) for i in range(len(streams))] if multi and a.landmarks else None
     if multi:
         multi.close()
+    kernel_ms = None
+    if a.kernel_times and streams:   # outside the timed region, on a fresh context: stage times of one replay
+        prof_run = MultiMSCKF(len(streams), dtype=dtype, device=grp.local_rank, device_map=a.device_map,
+                              device_keyframes=a.device_keyframes, **opt)
+        prof_run.ctx.set_profiling(True)
+        prof_run.run_streams(streams, messages=[s.messages(arrays=a.device_map) for s in streams])
+        kernel_ms = {k: [round(ms, 3), n] for k, (ms, n) in prof_run.ctx.kernel_times().items()}
+        prof_run.close()
     out = {"config": "SURVEY config 4 shape: %d synthetic stereo+IMU sequences x %d frames, %s, %d GPU(s)"
                      % (a.seqs, a.frames, "fp32" if a.fp32 else "fp64", grp.world),
            "batched_frames_per_s": round(total_frames / el_b, 1), "batched_s": round(el_b, 2),
            "device_map": bool(a.device_map), "device_keyframes": bool(a.device_keyframes),
            "batched_launches_rank0": launches,
            "ate_vs_gt_m_rank0": [round(ate(t, s.gt), 5) for t, s in zip(trajs, streams)]}
+    if opt:   # (without the options the line is what it was)
+        out.update(landmarks=a.landmarks, odometry=bool(a.odometry))
+    if archived is not None:
+        out["landmarks_archived_rank0"] = archived
+    if kernel_ms is not None:
+        out["kernel_ms_launches_rank0"] = kernel_ms
     if not a.no_single and grp.world == 1:
         evs = [s.events() for s in streams]
         if a.device_map:
@@ -92,7 +117,7 @@ def main():
                     zip(ev, np.cumsum([k for k, _ in ev]) - 1)] for s, ev in zip(streams, evs)]
         t0 = time.perf_counter()
         for s, ev in zip(streams, evs):
-            flt = msckf_amd.MSCKF(dtype=dtype, device_map=a.device_map, device_keyframes=a.device_keyframes)
+            flt = msckf_amd.MSCKF(dtype=dtype, device_map=a.device_map, device_keyframes=a.device_keyframes, **opt)
             replay(flt, s, events=ev)
             flt.close()
         el_s = time.perf_counter() - t0

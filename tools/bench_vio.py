@@ -44,10 +44,10 @@ FILTER_SYNCS = ("map_add_lost", "map_add_lost_tracks", "states", "map_keyframe_s
 class Wired:
     """(a): the two classes joined by hand, behind MultiStereoVIO's interface."""
 
-    def __init__(self, n, frontend_config, dtype):
+    def __init__(self, n, frontend_config, dtype, opt):
         cfg = fe_mod.FrontendConfig(**{**vars(frontend_config), "device_pipeline": True, "device_tracks": True})
         self.frontend = fe_mod.MultiImageProcessor(n, config=cfg)
-        self.filters = MultiMSCKF(n, dtype=dtype, device_map=True, device_keyframes=True)
+        self.filters = MultiMSCKF(n, dtype=dtype, device_map=True, device_keyframes=True, **opt)
 
     def imu_callback(self, i, m):
         self.frontend.imu_callback(i, m)
@@ -65,10 +65,11 @@ class Wired:
         self.filters.close()
 
 
-def make(which, n, cfg, dtype):
+def make(which, n, cfg, dtype, opt):
+    """``opt``: the landmarks / odometry arguments (msckf_odometry.h), the same in every composition."""
     if which == "wired":
-        return Wired(n, cfg, dtype)
-    return MultiStereoVIO(n, frontend_config=cfg, dtype=dtype, handoff=which)
+        return Wired(n, cfg, dtype, opt)
+    return MultiStereoVIO(n, frontend_config=cfg, dtype=dtype, handoff=which, **opt)
 
 
 def pose_bytes(res):
@@ -79,10 +80,10 @@ def pose_bytes(res):
                      res.cam0_pose._vio_t__))
 
 
-def run(which, streams, cfg, dtype):
+def run(which, streams, cfg, dtype, opt):
     """(lane-frames/s from step 2 on, poses per lane as bytes, calls per step by kind)."""
     S, n = len(streams), len(streams[0])
-    vio = make(which, S, cfg, dtype)
+    vio = make(which, S, cfg, dtype, opt)
     poses = [[] for _ in range(S)]
     try:
         for k in range(n):
@@ -111,7 +112,11 @@ def main():
     ap.add_argument("--lanes", type=int, nargs="+", default=[1, 11])
     ap.add_argument("--repeat", type=int, default=1, help="alternating runs of each composition")
     ap.add_argument("--dtype", choices=("f64", "f32"), default="f64")
+    ap.add_argument("--landmarks", choices=("host", "device"), default=None,
+                    help="keep the landmark archive (msckf_odometry.h) in every composition")
+    ap.add_argument("--odometry", action="store_true", help="the frames' reads bring the pose covariance along")
     a = ap.parse_args()
+    opt = dict(landmarks=a.landmarks, odometry=a.odometry) if a.landmarks or a.odometry else {}
     dtype = np.float64 if a.dtype == "f64" else np.float32
     W, H = 752, 480
     K = np.array([450.0, 450.0, 376.0, 240.0])
@@ -124,7 +129,7 @@ def main():
         streams = lane_streams(S, a.frames, W, H)         # rendered up front: not part of the timing
         ref = None
         for r, which in ((r, w) for r in range(a.repeat) for w in ("wired", "host", "device")):
-            fps, poses, per, syncs = run(which, streams, cfg, dtype)
+            fps, poses, per, syncs = run(which, streams, cfg, dtype, opt)
             n_poses = sum(p is not None for lane in poses for p in lane)
             same = None
             if ref is None:
@@ -136,7 +141,7 @@ def main():
                               "frames_per_lane": a.frames, "dtype": a.dtype, "resolution": [W, H],
                               "lane_frames_per_s": round(fps, 1), "device_calls_per_step": per,
                               "synchronisations_per_step": syncs, "poses": n_poses,
-                              "poses_identical_to_first_wired": same,
+                              "poses_identical_to_first_wired": same, **opt,
                               "note": "timed from step 2 on; host bookkeeping in Python; synthetic stream"}),
                   flush=True)
             bad |= n_poses == 0

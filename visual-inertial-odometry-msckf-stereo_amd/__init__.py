@@ -8,10 +8,11 @@ ctypes.  There is no CPU fallback: if ``libmsckf_hip.so`` is missing or no GPU
 is present, the filter raises.
 """
 from .config import FilterConfig, OptimizationConfig, CHI2_05, chi2_threshold  # noqa: F401
-from .msckf import MSCKF, VioResult, FeatureArrays, TrackMessage  # noqa: F401
+from .msckf import MSCKF, VioResult, VioOdometry, FeatureArrays, TrackMessage  # noqa: F401
+from .landmarks import Landmarks  # noqa: F401
 from ._lib import Context, MsckfError, load_library  # noqa: F401
 from .vio import MultiStereoVIO, StereoVIO  # noqa: F401
 
 __all__ = ["FilterConfig", "OptimizationConfig", "CHI2_05", "chi2_threshold", "MSCKF",
-           "VioResult", "FeatureArrays", "TrackMessage", "Context", "MsckfError", "load_library", "MultiStereoVIO",
-           "StereoVIO"]
+           "VioResult", "VioOdometry", "Landmarks", "FeatureArrays", "TrackMessage", "Context", "MsckfError",
+           "load_library", "MultiStereoVIO", "StereoVIO"]

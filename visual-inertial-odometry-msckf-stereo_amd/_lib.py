@@ -195,6 +195,19 @@ EQUALIZE_SIGS = {
 }
 EQUALIZE_EXPORTED = tuple(EQUALIZE_SIGS)
 
+# the landmark archive on the device and the pose / velocity covariance of a frame's read
+# (include/msckf_odometry.h), same library and context
+LANDMARKS_MAX_CAP = 65536
+ODOMETRY_SIGS = {
+    "msckf_landmarks_create": (C.c_int, [_P, C.c_int]),
+    "msckf_landmarks_clear": (C.c_int, [_P, C.c_int, _I]),
+    "msckf_landmarks_archive": (C.c_int, [_P, C.c_int, _I, _I, _I, _I]),
+    "msckf_landmarks_get": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int, _I64, _I64, _I64, _D, _I, _D, _I]),
+    "msckf_readback_odom": (C.c_int, [_P, C.c_int, _I, _D, _D, _I, C.c_int, C.c_int, _D, _U8, _D, _D, _U8, _I, _D, _D,
+                                      _D]),
+}
+ODOMETRY_EXPORTED = tuple(ODOMETRY_SIGS)
+
 # multi-GPU replica transport, RCCL (include/msckf_replicas.h), same library
 REPLICA_SIGS = {
     "msckf_rccl_unique_id": (C.c_int, [_U8]),
@@ -224,7 +237,8 @@ def load_library(path: str = LIB_PATH):
                                   list(FRONTEND_RANSAC_SIGS.items()) + list(FRONTEND_PIPELINE_SIGS.items()) +
                                   list(FRONTEND_LANES_SIGS.items()) + list(FRONTEND_TRACKS_SIGS.items()) +
                                   list(MAP_SIGS.items()) + list(KEYFRAME_SIGS.items()) + list(HANDOFF_SIGS.items()) +
-                                  list(EQUALIZE_SIGS.items()) + list(REPLICA_SIGS.items())):
+                                  list(EQUALIZE_SIGS.items()) + list(ODOMETRY_SIGS.items()) +
+                                  list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -284,6 +298,7 @@ class Context:
         self.lock = threading.RLock()
         self._pending = None   # the loaded batch's results, not read back yet (Pending)
         self.map_cap = None    # rows per filter of the feature map (map_create); None: the context has none
+        self.landmark_cap = None   # rows per filter of the landmark rings (landmarks_create)
 
     def _check(self, rc):
         if rc < 0:
@@ -456,6 +471,16 @@ class Context:
         (imu records (n, IMU_LEN), list of cam arrays, covariance diagonals
         (n, cov[1]) of [cov[0], cov[0] + cov[1]) or None).  An outstanding
         deferred batch (Pending) is read back in the same copy."""
+        return self._readback(filters, want_cams, cov, None)
+
+    def readback_odom(self, filters, R_body, want_cams=True, cov=None):
+        """msckf_readback_odom (msckf_odometry.h): what ``readback`` returns,
+        from the same single read, plus the listed filters' pose covariances
+        (n, 6, 6) and velocity covariances (n, 3, 3) in the frame ``R_body``
+        (3 x 3, the rotation of T_imu_body) rotates to."""
+        return self._readback(filters, want_cams, cov, _f64(R_body, (3, 3)))
+
+    def _readback(self, filters, want_cams, cov, R_body):
         filters = _i32(filters)
         n = len(filters)
         imu = np.zeros((n, IMU_LEN))
@@ -470,16 +495,21 @@ class Context:
             rows = np.zeros(self.B, np.int32)
         else:
             acc = gam = p = v = rows = None
-        with self.lock:
-            self._check(self.lib.msckf_readback(
-                self.h, n, _ptr(filters, C.c_int32), _ptr(imu, C.c_double), _ptr(cams, C.c_double),
+        args = (self.h, n, _ptr(filters, C.c_int32), _ptr(imu, C.c_double), _ptr(cams, C.c_double),
                 _ptr(nc, C.c_int32), int(i0), int(ncv), _ptr(cv, C.c_double), _ptr(acc, C.c_uint8),
-                _ptr(gam, C.c_double), _ptr(p, C.c_double), _ptr(v, C.c_uint8), _ptr(rows, C.c_int32)))
+                _ptr(gam, C.c_double), _ptr(p, C.c_double), _ptr(v, C.c_uint8), _ptr(rows, C.c_int32))
+        with self.lock:
+            if R_body is None:
+                self._check(self.lib.msckf_readback(*args))
+            else:
+                pose_cov, vel_cov = np.zeros((n, 6, 6)), np.zeros((n, 3, 3))
+                self._check(self.lib.msckf_readback_odom(*args, _ptr(R_body, C.c_double), _ptr(pose_cov, C.c_double),
+                                                         _ptr(vel_cov, C.c_double)))
         if pend is not None:
             pend.res = (acc.astype(bool), gam, p, v.astype(bool), rows)
             self._pending = None
         cl = [cams[w, :nc[w]].copy() for w in range(n)] if want_cams else [None] * n
-        return imu, cl, cv
+        return (imu, cl, cv) if R_body is None else (imu, cl, cv, pose_cov, vel_cov)
 
     def batch_triangulate(self):
         self._check(self.lib.msckf_batch_triangulate(self.h))
@@ -656,6 +686,44 @@ class Context:
             self._check(self.lib.msckf_map_prune_commit(self.h, len(filters), _ptr(filters, C.c_int32),
                                                         _ptr(ent_off, C.c_int32), _ptr(rows, C.c_int32),
                                                         _ptr(valid, C.c_uint8), _ptr(p_w, C.c_double)))
+
+    # ---- the landmark archive on the device (msckf_odometry.h) ----
+    def landmarks_create(self, cap):
+        with self.lock:
+            self._check(self.lib.msckf_landmarks_create(self.h, int(cap)))
+        self.landmark_cap = int(cap)
+
+    def landmarks_clear(self, filters):
+        filters = _i32(filters)
+        with self.lock:
+            self._check(self.lib.msckf_landmarks_clear(self.h, len(filters), _ptr(filters, C.c_int32)))
+
+    def landmarks_archive(self, filters, feat_off, rows, stamps):
+        """msckf_landmarks_archive: behind ``map_load(MAP_LOAD_LOST, filters,
+        feat_off, rows, ..)`` and ``batch_update``, with the same lists; the
+        accepted features go into the filters' rings on the device, stamped
+        ``stamps[w]``.  Asynchronous, nothing comes back."""
+        filters, feat_off, rows, stamps = _i32(filters), _i32(feat_off), _i32(rows), _i32(stamps)
+        if len(stamps) != len(filters):
+            raise ValueError("%d stamps for %d filters" % (len(stamps), len(filters)))
+        with self.lock:
+            self._check(self.lib.msckf_landmarks_archive(self.h, len(filters), _ptr(filters, C.c_int32),
+                                                         _ptr(feat_off, C.c_int32), _ptr(rows, C.c_int32),
+                                                         _ptr(stamps, C.c_int32)))
+
+    def landmarks_get(self, f, first_seq=0, max_rows=None):
+        """Filter ``f``'s ring from sequence number ``first_seq`` on, oldest
+        first: (ids, p_w, n_obs, gamma, stamp, first_seq of the rows, seq)."""
+        m = (self.landmark_cap or 1) if max_rows is None else int(max_rows)
+        ids, p_w, n_obs = np.zeros(m, np.int64), np.zeros((m, 3)), np.zeros(m, np.int32)
+        gam, stamp = np.zeros(m), np.zeros(m, np.int32)
+        seq, first = C.c_int64(0), C.c_int64(0)
+        with self.lock:
+            k = self._check(self.lib.msckf_landmarks_get(
+                self.h, f, int(first_seq), m, C.byref(seq), C.byref(first), _ptr(ids, C.c_int64),
+                _ptr(p_w, C.c_double), _ptr(n_obs, C.c_int32), _ptr(gam, C.c_double), _ptr(stamp, C.c_int32)))
+        return (ids[:k].copy(), p_w[:k].copy(), n_obs[:k].copy(), gam[:k].copy(), stamp[:k].copy(), first.value,
+                seq.value)
 
     def device_info(self):
         """(HIP device index, PCI bus id) this context runs on."""

@@ -15,6 +15,7 @@
 #include "../../include/msckf_hip.h"
 #include "../../include/msckf_keyframes.h"
 #include "../../include/msckf_map.h"
+#include "../../include/msckf_odometry.h"
 #include "msckf_common.h"
 #include "msckf_handoff_dev.h"
 #include "msckf_launch.h"
@@ -225,7 +226,18 @@ struct msckf_ctx {
         std::vector<unsigned long long> rm; // [B][2]: the removed slots of the open select
         DBuf<unsigned char> in, out, aux;  // a call's input block, a select's outputs, a load's fill inputs
         DBuf<double> chi2;                 // CHI2_05, 99 entries
+        size_t aux_rows = 0;               // offset in aux of the last load's rows (int per feature, batch order)
     } map;
+    // the landmark rings (msckf_odometry.h): absent until msckf_landmarks_create
+    struct Landmarks {
+        bool on = false;
+        int cap = 0;
+        DBuf<unsigned char> store, in;     // the rings and the counters; an archive call's input block
+        LmDev dev{};
+        // the loaded batch as an archive call must name it: 0 = not a lost-form load, 1 = loaded, 2 = updated
+        int state = 0;
+        std::vector<int> filters, feat_off, rows;
+    } lm;
 };
 
 namespace {
@@ -470,6 +482,7 @@ struct LoadPlan {
 int plan_counts(msckf_ctx* c, int nf, const int32_t* feat_off, int single_filter, const int32_t* obs_off,
                 LoadPlan& pl) {
     std::vector<int>& h_off = pl.h_off;
+    c->lm.state = 0;   // whatever batch was loaded, an archive call can no longer name it
     h_off.assign(c->B + 1, 0);
     if (feat_off) {
         for (int b = 0; b <= c->B; ++b) h_off[b] = feat_off[b];
@@ -1157,30 +1170,75 @@ int do_get_states_batch(msckf_ctx* c, int nfilt, const int32_t* filters, double*
     return 0;
 }
 
+// msckf_readback_odom (include/msckf_odometry.h): the entries of P the pose and velocity covariances are
+// formed from, per listed filter [the 6 x 6 over rows / columns (0 1 2 12 13 14) | the 3 x 3 over (6 7 8)].
+// Every filter's P holds the IMU block: Dmax >= 21.
+constexpr int ODOM_BLOCK = 45;
+template <typename T>
+__global__ void __launch_bounds__(64) k_odom_blocks(const T* __restrict__ P, int Dmax, const int* __restrict__ filters,
+                                                    T* __restrict__ out) {
+    const int e = threadIdx.x;
+    if (e >= ODOM_BLOCK) return;
+    const T* Pf = P + (size_t)filters[blockIdx.x] * Dmax * Dmax;
+    int r, col;
+    if (e < 36) {
+        r = e / 6, col = e - 6 * r;
+        r = r < 3 ? r : r + 9;
+        col = col < 3 ? col : col + 9;
+    } else {
+        r = 6 + (e - 36) / 3, col = 6 + (e - 36) % 3;
+    }
+    out[(size_t)blockIdx.x * ODOM_BLOCK + e] = Pf[(size_t)r * Dmax + col];
+}
+// pose_cov = G S G^T with G = blockdiag(R, R), vel_cov = R V R^T, in double: (R X) first, then (R X) R^T.
+void odom_covariances(const double* blk, const double* R, double* pose_cov, double* vel_cov) {
+    auto sandwich = [&](const double* X, int ldx, double* out, int ldo) {   // out (3 x 3) = R X R^T
+        double t[9];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j)
+                t[i * 3 + j] = R[i * 3] * X[j] + R[i * 3 + 1] * X[ldx + j] + R[i * 3 + 2] * X[2 * ldx + j];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j)
+                out[i * ldo + j] = t[i * 3] * R[j * 3] + t[i * 3 + 1] * R[j * 3 + 1] + t[i * 3 + 2] * R[j * 3 + 2];
+    };
+    if (pose_cov)
+        for (int a = 0; a < 2; ++a)
+            for (int b = 0; b < 2; ++b) sandwich(blk + a * 18 + b * 3, 6, pose_cov + a * 18 + b * 3, 6);
+    if (vel_cov) sandwich(blk + 36, 3, vel_cov, 3);
+}
+
 // One synchronisation for a frame's sync point: the listed filters' IMU (and
 // cam) records, their covariance diagonal [i0, i0 + n), and -- when any result
 // pointer is given -- the loaded batch's results.
 template <typename T>
 int do_readback(msckf_ctx* c, int nfilt, const int32_t* filters, double* imu_out, double* cams_out,
                 int32_t* ncams_out, int i0, int n, double* cov_out, uint8_t* accepted_out, double* gamma_out,
-                double* p_w_out, uint8_t* valid_out, int32_t* rows_out) {
+                double* p_w_out, uint8_t* valid_out, int32_t* rows_out, const double* R_body = nullptr,
+                double* pose_cov_out = nullptr, double* vel_cov_out = nullptr) {
     const size_t ts = sizeof(T);
     const bool cov = nfilt > 0 && n > 0 && cov_out;
-    if (cov) {
-        for (int w = 0; w < nfilt; ++w)
-            if (i0 < 0 || i0 + n > 21 + 6 * c->h_ncams[filters[w]]) FAIL(-1, "diagonal range out of bounds");
+    const bool odom = nfilt > 0 && R_body;   // msckf_readback_odom: the blocks ride behind the diagonal
+    const size_t n_diag = cov ? (size_t)nfilt * n : 0, n_scr = n_diag + (odom ? (size_t)nfilt * ODOM_BLOCK : 0);
+    if (cov || odom) {
+        if (cov)
+            for (int w = 0; w < nfilt; ++w)
+                if (i0 < 0 || i0 + n > 21 + 6 * c->h_ncams[filters[w]]) FAIL(-1, "diagonal range out of bounds");
         std::vector<int> fl(filters, filters + nfilt);
         std::vector<const int*> dl;
         if (int r = upload_ints(c, {&fl}, dl)) return r;
-        HIPC(c->scratch.ensure((size_t)nfilt * n * ts));
-        launch_cov_diag<T>(c->stream, dev_state<T>(c), nfilt, dl[0], i0, n, reinterpret_cast<T*>(c->scratch.p));
+        HIPC(c->scratch.ensure(n_scr * ts));
+        if (cov) launch_cov_diag<T>(c->stream, dev_state<T>(c), nfilt, dl[0], i0, n, reinterpret_cast<T*>(c->scratch.p));
+        if (odom)
+            hipLaunchKernelGGL(k_odom_blocks<T>, dim3(nfilt), dim3(64), 0, c->stream,
+                               reinterpret_cast<const T*>(c->P.p), c->Dmax, dl[0],
+                               reinterpret_cast<T*>(c->scratch.p) + n_diag);
         HIPC(hipGetLastError());
     }
     const bool res = accepted_out || gamma_out || p_w_out || valid_out || rows_out;
     DownList d;
     const size_t o_imu = d.add(c->imu.p, (size_t)c->B * IMU_STRIDE * ts);
     const size_t o_cam = cams_out ? d.add(c->cams.p, (size_t)c->B * c->Nmax * CAM_STRIDE * ts) : 0;
-    const size_t o_cov = cov ? d.add(c->scratch.p, (size_t)nfilt * n * ts) : 0;
+    const size_t o_cov = n_scr ? d.add(c->scratch.p, n_scr * ts) : 0;
     ResultsRead rr;
     if (res) rr = add_results<T>(c, d);
     HIPSYNC(c, d.run(c));
@@ -1202,7 +1260,14 @@ int do_readback(msckf_ctx* c, int nfilt, const int32_t* filters, double* imu_out
                         k < c->h_ncams[f] ? cams_all[((size_t)f * c->Nmax + k) * CAM_STRIDE + e] : 0.0;
         if (ncams_out) ncams_out[w] = c->h_ncams[f];
     }
-    if (cov) to_double<T>(cov_out, d.at(c, o_cov), (size_t)nfilt * n);
+    if (cov) to_double<T>(cov_out, d.at(c, o_cov), n_diag);
+    if (odom) {
+        std::vector<double> blk((size_t)nfilt * ODOM_BLOCK);
+        to_double<T>(blk.data(), d.at(c, o_cov) + n_diag * ts, blk.size());
+        for (int w = 0; w < nfilt; ++w)
+            odom_covariances(&blk[(size_t)w * ODOM_BLOCK], R_body, pose_cov_out ? pose_cov_out + (size_t)w * 36 : nullptr,
+                             vel_cov_out ? vel_cov_out + (size_t)w * 9 : nullptr);
+    }
     return res ? unpack_results<T>(c, d, rr, accepted_out, gamma_out, p_w_out, valid_out, rows_out) : 0;
 }
 
@@ -1311,7 +1376,7 @@ int msckf_destroy(msckf_ctx_t* c) {
         if (s) (void)hipStreamSynchronize(s);
     for (auto* b : {&c->P, &c->imu, &c->cams, &c->P_snap, &c->imu_snap, &c->cams_snap, &c->Hthin, &c->Lc, &c->Vi, &c->Sii, &c->G, &c->Tm, &c->W, &c->Wk,
                     &c->dx, &c->batch, &c->obs_ws, &c->obs_ht, &c->obs_g, &c->fqr, &c->tau, &c->ysq, &c->scratch,
-                    &c->map.store, &c->map.in, &c->map.out, &c->map.aux})
+                    &c->map.store, &c->map.in, &c->map.out, &c->map.aux, &c->lm.store, &c->lm.in})
         b->release();
     c->map.chi2.release();
     for (auto* b : {&c->ncams, &c->ncams_snap, &c->ident, &c->info, &c->afail, &c->row_off, &c->iscratch})
@@ -1477,7 +1542,9 @@ int msckf_batch_load(msckf_ctx_t* c, const int32_t* feat_off, const int32_t* obs
 int msckf_batch_update(msckf_ctx_t* c, int row_cap, int flags) {
     if (c) c->last_async = "msckf_batch_update";
     if (!c) FAIL(-1, "null context");
-    return DISPATCH(c, run_update_chain, c, row_cap, (flags & MSCKF_TRIANGULATE) != 0);
+    const int r = DISPATCH(c, run_update_chain, c, row_cap, (flags & MSCKF_TRIANGULATE) != 0);
+    c->lm.state = (r == 0 && c->lm.state == 1) ? 2 : 0;   // msckf_landmarks_archive follows load + update
+    return r;
 }
 
 int msckf_batch_results(msckf_ctx_t* c, uint8_t* accepted_out, double* gamma_out, double* p_w_out,
@@ -1663,3 +1730,5 @@ int msckf_debug_kalman(msckf_ctx_t* c) {
 // a file of its own but part of this translation unit because it uses the context, the staging helpers and the
 // loader plan above
 #include "msckf_map_api.inc"
+// and of include/msckf_odometry.h
+#include "msckf_odometry_api.inc"

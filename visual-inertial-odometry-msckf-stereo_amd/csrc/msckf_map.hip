@@ -1,7 +1,8 @@
 // msckf_map.hip -- the filter's feature map kept on the device
 // (include/msckf_map.h is the specification, tests/feature_map_ref.py its
 // numpy restatement), and the keyframe choice fused into the prune select
-// (include/msckf_keyframes.h, tests/keyframe_ref.py).  One workgroup of 256 threads (four wavefronts) per named
+// (include/msckf_keyframes.h, tests/keyframe_ref.py), and the landmark archive filled from a lost-form batch
+// (include/msckf_odometry.h, tests/landmarks_ref.py).  One workgroup of 256 threads (four wavefronts) per named
 // filter; a call reads a filter's current table and writes its other one.
 //
 // Rules (those of the front-end's k_trk_* kernels): fixed-stride [filter][cap]
@@ -448,7 +449,54 @@ k_map_gather(MapDev m, int mode, int nf, const int* __restrict__ feat_filter, co
     valid[f] = (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])) ? 2 : 0;
 }
 
+// msckf_landmarks_archive (include/msckf_odometry.h): the accepted features of
+// the filter's part of the loaded batch, in batch order, appended to its ring.
+// The host guarantees count <= ring cap (no slot is written twice in a call) and
+// every frow inside the lost table.
+template <typename T>
+__global__ void __launch_bounds__(MAP_BLOCK)
+k_lm_archive(MapDev m, LmDev L, const int* __restrict__ hdr, const int* __restrict__ frow,
+             const uint8_t* __restrict__ include, const T* __restrict__ p_w, const T* __restrict__ gamma) {
+    __shared__ int s_wcnt[MAP_WAVES];
+    const int w = blockIdx.x, tid = threadIdx.x;
+    const int* h = hdr + w * LM_HDR;
+    const int f = h[0], a0 = h[2], n = h[3], stamp = h[4];
+    const MapTab tab = m.t[h[1]];
+    const size_t fb = (size_t)f * m.cap, rb = (size_t)f * L.cap;
+    const long long seq0 = L.seq[f];
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += MAP_BLOCK) {
+        const int i = i0 + tid;
+        const bool take = i < n && include[a0 + i] != 0;
+        int tot;
+        const int rk = block_rank(take, s_wcnt, tot);
+        if (take) {
+            const size_t row = fb + frow[a0 + i];
+            const size_t d = rb + (size_t)((seq0 + base + rk) % L.cap);
+            L.ids[d] = tab.ids[row];
+            for (int c = 0; c < 3; ++c) L.pw[d * 3 + c] = (double)p_w[(size_t)(a0 + i) * 3 + c];
+            L.gamma[d] = (double)gamma[a0 + i];
+            L.nobs[d] = __popcll(tab.mask[row * 2]) + __popcll(tab.mask[row * 2 + 1]);
+            L.stamp[d] = stamp;
+        }
+        base += tot;
+    }
+    __syncthreads();   // every thread's last use of seq0 lies before the one store to seq
+    if (tid == 0 && base) L.seq[f] = seq0 + base;
+}
+
 }  // namespace
+
+template <typename T>
+void launch_lm_archive(hipStream_t s, const MapDev& m, const LmDev& L, int nfilt, const int* hdr, const int* frow,
+                       const uint8_t* include, const T* p_w, const T* gamma) {
+    if (nfilt <= 0) return;
+    hipLaunchKernelGGL(k_lm_archive<T>, dim3(nfilt), dim3(MAP_BLOCK), 0, s, m, L, hdr, frow, include, p_w, gamma);
+}
+template void launch_lm_archive<float>(hipStream_t, const MapDev&, const LmDev&, int, const int*, const int*,
+                                       const uint8_t*, const float*, const float*);
+template void launch_lm_archive<double>(hipStream_t, const MapDev&, const LmDev&, int, const int*, const int*,
+                                        const uint8_t*, const double*, const double*);
 
 size_t map_lds_bytes(int cap) { return (size_t)cap * 16 + MAP_WAVES * sizeof(int); }
 

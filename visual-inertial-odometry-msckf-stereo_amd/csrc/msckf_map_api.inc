@@ -166,6 +166,14 @@ int do_map_load(msckf_ctx* c, int mode, int nfilt, const int32_t* filters, const
                          reinterpret_cast<T*>(c->obs_z), reinterpret_cast<T*>(c->chi2), c->valid,
                          reinterpret_cast<T*>(c->p_w));
     HIPC(hipGetLastError());
+    mp.aux_rows = o_row;
+    if (mode == MSCKF_MAP_LOAD_LOST) {   // what msckf_landmarks_archive has to name (msckf_odometry.h)
+        auto& lm = c->lm;
+        lm.filters.assign(filters, filters + nfilt);
+        lm.feat_off.assign(feat_off, feat_off + nfilt + 1);
+        lm.rows.assign(rows, rows + (nfilt ? feat_off[nfilt] : 0));
+        lm.state = 1;
+    }
     return 0;
 }
 

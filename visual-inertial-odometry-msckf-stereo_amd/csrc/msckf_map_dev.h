@@ -51,4 +51,24 @@ void launch_map_gather(hipStream_t, const MapDev&, int mode, int nf, const int* 
                        const int* frow, const int* sel, const unsigned long long* rm, const double* host_pw,
                        const double* chi2_tab, T big, int* obs_cam, T* obs_z, T* chi2, uint8_t* valid, T* p_w);
 
+// The landmark rings (include/msckf_odometry.h), fixed stride [filter][cap]:
+//   ids [B][cap], pw [B][cap][3], gamma [B][cap], nobs [B][cap], stamp [B][cap]; seq [B]
+struct LmDev {
+    int64_t* ids;
+    double* pw;
+    double* gamma;
+    int* nobs;
+    int* stamp;
+    long long* seq;
+    int cap;
+};
+constexpr int LM_HDR = 8;   // ints per named filter in an archive call's header
+// msckf_landmarks_archive: per named filter the accepted features [first, first + count) of the loaded batch,
+// in batch order, appended to the filter's ring.  frow: the batch's rows of the lost table (the load's device
+// copy); include / p_w / gamma: the batch's results.
+// hdr: [filter, lost table, first feature of the batch, count (<= ring cap), stamp, -, -, -]
+template <typename T>
+void launch_lm_archive(hipStream_t, const MapDev&, const LmDev&, int nfilt, const int* hdr, const int* frow,
+                       const uint8_t* include, const T* p_w, const T* gamma);
+
 }  // namespace msckf

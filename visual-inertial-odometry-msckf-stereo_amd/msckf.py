@@ -19,7 +19,9 @@ host keeps the decisions' descriptors (ids, track lengths) for its logs, and a
 frame's message may be a ``TrackMessage`` that names where the front-end left
 it on the device (include/msckf_handoff.h); with
 ``device_keyframes=True`` the keyframe selection is part of the prune select's
-device call too (include/msckf_keyframes.h).
+device call too (include/msckf_keyframes.h).  ``landmarks`` / ``odometry`` add
+the outputs of include/msckf_odometry.h: the archive of the features that left
+the map through an accepted update, and the published pose's covariance.
 
 Every device interaction of a frame is expressed as a request yielded by a
 step generator (``_frame_steps``); ``feature_callback`` serves the requests
@@ -43,8 +45,14 @@ import numpy as np
 from . import _lib
 from .config import CHI2_05, FilterConfig, chi2_threshold
 from .geometry import Isometry3d, from_two_vectors, to_quaternion, to_rotation
+from .landmarks import HostRing, Landmarks, check_mode, with_live
 
 VioResult = namedtuple("vio_result", ["timestamp", "pose", "velocity", "cam0_pose"])
+# What feature_callback returns with odometry=True: the vio_result's fields and the 6 x 6 covariance of the pose
+# (orientation error angle, then position) and the 3 x 3 of the velocity, both rotated by T_imu_body's rotation
+# (include/msckf_odometry.h states the frame).
+VioOdometry = namedtuple("vio_odometry", ["timestamp", "pose", "velocity", "cam0_pose", "pose_covariance",
+                                          "velocity_covariance"])
 # A feature message as arrays: ids int64 [n], uv float64 [n][4] (u0 v0 u1 v1).
 # Accepted wherever the reference's feature_msg tuple is.
 FeatureArrays = namedtuple("FeatureArrays", ["timestamp", "ids", "uv"])
@@ -107,13 +115,21 @@ class MSCKF:
     ROW_CAP = 1500   # msckf.py:678
 
     def __init__(self, config=None, dtype=np.float64, device=0, cam_capacity=None, ctx=None, slot=0,
-                 device_map=False, map_capacity=1024, device_keyframes=False):
+                 device_map=False, map_capacity=1024, device_keyframes=False, landmarks=None,
+                 landmark_capacity=4096, odometry=False):
         """``device_map``: keep the feature map in the context's tables
         (msckf_map.h) instead of ``map_server``'s dicts; ``map_capacity``: rows
         per filter.  A shared ``ctx`` must already have its tables.
         ``device_keyframes`` (with ``device_map``): a prune frame's cam states
         are chosen on the device, in the prune select's call
-        (msckf_keyframes.h), instead of from a read of the cam poses."""
+        (msckf_keyframes.h), instead of from a read of the cam poses.
+        ``landmarks``: archive the features that leave the map through an
+        accepted lost-feature update (``landmarks()``), ``landmark_capacity``
+        rows: "device" (with ``device_map``) fills the ring on the device
+        inside the update's calls (msckf_odometry.h), "host" keeps it in numpy
+        from the deferred results.  A shared ``ctx`` must already have its
+        rings.  ``odometry``: the callbacks return ``VioOdometry`` -- the
+        frame's read brings the pose and velocity covariance along."""
         if config is None:
             config = FilterConfig()
         elif not isinstance(config, FilterConfig):
@@ -121,6 +137,9 @@ class MSCKF:
         self.config = config
         self.device_map = bool(device_map)
         self.device_keyframes = bool(device_keyframes)
+        check_mode(landmarks, self.device_map)
+        self.landmark_mode = landmarks
+        self.odometry = bool(odometry)
         if self.device_keyframes and not self.device_map:
             raise ValueError("device_keyframes=True needs device_map=True: the choice is part of the map's prune "
                              "select")
@@ -138,6 +157,8 @@ class MSCKF:
             self.__class__ = _device_map_class(type(self))
             if self._own_ctx:
                 self.ctx.map_create(map_capacity)
+                if landmarks == "device":
+                    self.ctx.landmarks_create(landmark_capacity)
         else:
             self.map_server: "OrderedDict[int, Feature]" = OrderedDict()
         self.cam_ids: list = []            # cam-state ids in slot order (oldest first)
@@ -153,6 +174,7 @@ class MSCKF:
         self.reset_log = []                # frames after which online_reset fired
         self._deferred = []                # (Pending, callback): update results not read back yet
         self._n_published = 0
+        self._ring = HostRing(landmark_capacity) if landmarks == "host" else None
         T_cam0_imu = np.linalg.inv(config.T_imu_cam0)
         self._T_imu_body = Isometry3d(config.T_imu_body[:3, :3], config.T_imu_body[:3, 3])
         imu = _lib.pack_imu(q=[0, 0, 0, 1], p=np.zeros(3), v=config.velocity, bg=np.zeros(3), ba=np.zeros(3),
@@ -215,6 +237,9 @@ class MSCKF:
             return ctx.triangulate(f, req[1], req[2], req[3])
         if kind == "update":
             return ctx.update_async(f, *req[1:])
+        if kind == "states" and len(req) > 3:   # ("states", i0, n, R_body): the read of msckf_readback_odom
+            imu, cams, cv, pc, vc = ctx.readback_odom([f], req[3], cov=req[1:3])
+            return imu[0], cams[0], None if cv is None else cv[0], pc[0], vc[0]
         if kind == "states":   # ("states"[, i0, n]): one read, with P's diagonal [i0, i0 + n) if asked
             imu, cams, cv = ctx.readback([f], cov=req[1:3] if len(req) > 1 else None)
             return (imu[0], cams[0]) if cv is None else (imu[0], cams[0], cv[0])
@@ -240,6 +265,8 @@ class MSCKF:
         if kind == "map_update":   # (kind, form, rows, counts, p_w, triangulate, row cap)
             ctx.map_load(req[1], [f], [0, len(req[2])], req[2], req[3], req[4])
             ctx.batch_update(row_cap=req[6], triangulate=req[5])
+            if self.landmark_mode == "device" and req[1] == _lib.MAP_LOAD_LOST:   # directly behind the update
+                ctx.landmarks_archive([f], [0, len(req[2])], req[2], [self._n_published])
             return ctx.pending([(f, 0, len(req[2]))])[0]
         if kind == "map_prune_commit":
             return ctx.map_prune_commit([f], [0, len(req[1])], req[1], req[2], req[3])
@@ -317,9 +344,14 @@ class MSCKF:
             yield from self._prune_cam_state_buffer()
         # publish and online_reset's position variances in one read
         thr = self.config.position_std_threshold
-        st = yield (("states", 12, 3) if thr > 0 else ("states",))
+        if self.odometry:   # the same read, the pose / velocity covariance with it
+            st = yield ("states", 12, 3 if thr > 0 else 0, self._T_imu_body._vio_R__)
+        else:
+            st = yield (("states", 12, 3) if thr > 0 else ("states",))
         self._settle()
         res = self._publish_from(feature_msg.timestamp, _lib.unpack_imu(st[0]))
+        if self.odometry:
+            res = VioOdometry(*res, st[3], st[4])
         self._n_published += 1
         yield from self._online_reset(st[2] if thr > 0 else None)
         return res
@@ -450,6 +482,22 @@ class MSCKF:
                 self.shape_log.append((frame, rows, D))
         self._deferred.append((pend, apply))
 
+    def _archive_deferred(self, ids, n_obs):
+        """landmarks="host": when the results of the update just deferred -- a
+        lost-path one over the features ``ids`` with ``n_obs`` observations each
+        -- are applied, its accepted features go into the ring, as
+        msckf_landmarks_archive appends them on the device."""
+        if self._ring is None:
+            return
+        pend, fn = self._deferred[-1]
+        ids, n_obs, frame = np.asarray(ids, np.int64), np.asarray(n_obs, np.int64), self._n_published
+
+        def apply(acc, gam, p, valid, rows):
+            fn(acc, gam, p, valid, rows)
+            a = np.flatnonzero(acc)
+            self._ring.append(ids[a], p[a], n_obs[a], gam[a], frame)
+        self._deferred[-1] = (pend, apply)
+
     def _remove_lost_features(self):
         """msckf.py:616-689"""
         sid = self.imu_id
@@ -485,6 +533,7 @@ class MSCKF:
         cam_lists = [list(f.observations.keys()) for f in candidates]
         dofs = [len(cl) - 1 for cl in cam_lists]
         yield from self._update(candidates, cam_lists, dofs, self.ROW_CAP, to_init)
+        self._archive_deferred([f.id for f in candidates], [len(cl) for cl in cam_lists])
 
     def _find_redundant_cam_states(self, cams_arr):
         """msckf.py:691-727 (host; needs the cam poses)."""
@@ -592,6 +641,7 @@ class MSCKF:
         pend = yield ("map_update", _lib.MAP_LOAD_LOST, info[:, 3], M, None, not bool(info[:, 2].all()),
                       self.ROW_CAP)
         self._log_update(pend, cand_ids, M, M - 1, self.ROW_CAP)
+        self._archive_deferred(cand_ids, M)
 
     def _map_prune_cam_state_buffer(self):
         """msckf.py:730-818 on the device table."""
@@ -644,6 +694,41 @@ class MSCKF:
         R_w_c = s["R_imu_cam0"] @ T_i_w._vio_R__.T
         t_c_w = s["p"] + T_i_w._vio_R__ @ s["t_cam0_imu"]
         return VioResult(time, T_b_w, body_velocity, Isometry3d(R_w_c.T, t_c_w))
+
+    # ------------------------------------------------------------ landmarks --
+    def landmarks(self, first=0, live=False):
+        """The archive from sequence number ``first`` on as ``Landmarks``
+        (msckf_odometry.h; oldest first, at most the ring's capacity);
+        ``live``: the map's initialised features appended (stamp -1, gamma
+        NaN).  A deferred update is applied first."""
+        if self.landmark_mode is None:
+            raise ValueError("this filter keeps no landmarks (MSCKF(landmarks='host' | 'device'))")
+        with self._lock:
+            if self._ring is not None:
+                self._settle()
+                rows = self._ring.get(first)
+            else:
+                rows = self.ctx.landmarks_get(self.slot, first)
+            if not live:
+                return Landmarks(*rows)
+            if self.device_map:
+                ids, mask, _, p_w, init = self.ctx.map_get(self.slot)
+                n_obs = np.array([bin(int(m[0])).count("1") + bin(int(m[1])).count("1") for m in mask], np.int32)
+                return with_live(rows, ids[init], p_w[init], n_obs[init])
+            fs = [f for f in self.map_server.values() if f.is_initialized]
+            return with_live(rows, [f.id for f in fs], np.array([f.position for f in fs], float).reshape(-1, 3),
+                             [len(f.observations) for f in fs])
+
+    def clear_landmarks(self):
+        """Empties the archive (an online reset does not: the world frame continues)."""
+        if self.landmark_mode is None:
+            raise ValueError("this filter keeps no landmarks (MSCKF(landmarks='host' | 'device'))")
+        with self._lock:
+            if self._ring is not None:
+                self._settle()
+                self._ring.clear()
+            else:
+                self.ctx.landmarks_clear([self.slot])
 
     def _online_reset(self, d):
         """msckf.py:859-886 (``d``: P's position-block diagonal, read with the

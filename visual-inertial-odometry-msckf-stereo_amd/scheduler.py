@@ -38,6 +38,7 @@ import numpy as np
 from . import _lib
 from .config import FilterConfig
 from .frontend import MultiImageProcessor  # noqa: F401  (the image-side counterpart, same interface)
+from .landmarks import check_mode
 from .msckf import MSCKF
 from .vio import MultiStereoVIO, StereoVIO  # noqa: F401  (both ends in one class)
 from .trajectory import Trajectory
@@ -53,8 +54,12 @@ class MultiMSCKF:
     """``n`` filters (one per sequence) on one device context."""
 
     def __init__(self, n, config=None, dtype=np.float64, device=0, cam_capacity=None, lane_configs=None,
-                 device_map=False, map_capacity=1024, device_keyframes=False):
-        """``device_map`` / ``map_capacity``: every lane keeps its feature map
+                 device_map=False, map_capacity=1024, device_keyframes=False, landmarks=None, landmark_capacity=4096,
+                 odometry=False):
+        """``landmarks`` / ``landmark_capacity`` / ``odometry``: as ``MSCKF``'s,
+        for every lane ("device": one archive call for the lanes of a lost
+        update, msckf_odometry.h; ``landmarks(i)`` reads lane i's).
+        ``device_map`` / ``map_capacity``: every lane keeps its feature map
         in the context's tables (msckf_map.h), as ``MSCKF(device_map=True)``;
         ``device_keyframes``: the lanes' prune frames choose their cam states
         on the device (msckf_keyframes.h), one call for all waiting lanes.
@@ -65,6 +70,7 @@ class MultiMSCKF:
         extrinsics, LM parameters: the C-ABI msckf_config_t)."""
         if device_keyframes and not device_map:
             raise ValueError("device_keyframes=True needs device_map=True")
+        check_mode(landmarks, device_map)
         config = config or FilterConfig()
         if not isinstance(config, FilterConfig):
             config = FilterConfig.from_reference(config)
@@ -86,9 +92,17 @@ class MultiMSCKF:
                     self.ctx.close()
                     raise ValueError("lane %d: device_map=True needs optimization.translation_threshold < 0" % i)
             self.ctx.map_create(map_capacity)
+            if landmarks == "device":
+                try:
+                    self.ctx.landmarks_create(landmark_capacity)
+                except BaseException:
+                    self.ctx.close()
+                    raise
         self.device_keyframes = bool(device_keyframes)
+        self.landmark_mode = landmarks
         self.lanes = [MSCKF(cfgs[i], ctx=self.ctx, slot=i, device_map=self.device_map,
-                            device_keyframes=self.device_keyframes) for i in range(n)]
+                            device_keyframes=self.device_keyframes, landmarks=landmarks,
+                            landmark_capacity=landmark_capacity, odometry=odometry) for i in range(n)]
         self.launches = defaultdict(int)       # batched device calls per request kind
 
     def __len__(self):
@@ -96,6 +110,15 @@ class MultiMSCKF:
 
     def close(self):
         self.ctx.close()
+
+    def landmarks(self, i, first=0, live=False):
+        """Lane i's archive, as ``MSCKF.landmarks``."""
+        return self.lanes[i].landmarks(first, live)
+
+    def clear_landmarks(self, i=None):
+        """Empties lane i's archive (None: every lane's)."""
+        for ln in (self.lanes if i is None else [self.lanes[i]]):
+            ln.clear_landmarks()
 
     # ------------------------------------------------------------ callbacks --
     def imu_callback(self, i, imu_msg):
@@ -115,9 +138,9 @@ class MultiMSCKF:
             if kind in ("update", "map_update"):   # the row cap is per call: lost path 1500, prune path none
                 cap = min(pending[i][6] for i in group)
                 group = [i for i in group if pending[i][6] == cap]
-            elif kind in ("cov_diag", "states"):
-                key = pending[group[0]][1:3]
-                group = [i for i in group if pending[i][1:3] == key]
+            elif kind in ("cov_diag", "states"):   # one diagonal range (and, with odometry, one R_body) per call
+                key = _read_key(pending[group[0]])
+                group = [i for i in group if _read_key(pending[i]) == key]
             elif kind == "map_add_lost_tracks":   # one front-end context per call
                 group = [i for i in group if pending[i][1] is pending[group[0]][1]]
             results = self._serve(kind, group, [pending[i] for i in group])
@@ -156,6 +179,9 @@ class MultiMSCKF:
             tri = any(not np.isfinite(np.asarray(r[4], float)).all() for r in reqs)
             ctx.batch_update(row_cap=reqs[0][6], triangulate=tri)
             return ctx.pending([(s,) + self._ranges[s] for s in slots])
+        if kind == "states" and len(reqs[0]) > 3:   # the same read through msckf_readback_odom
+            imu, cams, cv, pc, vc = ctx.readback_odom(slots, reqs[0][3], cov=reqs[0][1:3])
+            return [(imu[w], cams[w], None if cv is None else cv[w], pc[w], vc[w]) for w in range(len(group))]
         if kind == "states":   # one read for the group (with the deferred batch, if any)
             cov = reqs[0][1:3] if len(reqs[0]) > 1 else None
             imu, cams, cv = ctx.readback(slots, cov=cov)
@@ -198,6 +224,9 @@ class MultiMSCKF:
             self._ranges = ctx.map_load(form, slots, offs([r[2] for r in reqs]), cat([r[2] for r in reqs], np.int32),
                                         cat([r[3] for r in reqs], np.int32), pw)
             ctx.batch_update(row_cap=reqs[0][6], triangulate=any(r[5] for r in reqs))
+            if self.landmark_mode == "device" and form == _lib.MAP_LOAD_LOST:   # directly behind the update
+                ctx.landmarks_archive(slots, offs([r[2] for r in reqs]), cat([r[2] for r in reqs], np.int32),
+                                      [self.lanes[i]._n_published for i in group])
             return ctx.pending([(s,) + self._ranges[s] for s in slots])
         if kind == "map_prune_commit":
             ctx.map_prune_commit(slots, offs([r[1] for r in reqs]), cat([r[1] for r in reqs], np.int32),
@@ -289,6 +318,11 @@ class MultiMSCKF:
                 for m in messages[i][0][imu_pos[i]:]:
                     self.imu_callback(i, m)
         return [Trajectory.from_results(r) for r in results]
+
+
+def _read_key(req):
+    """What the lanes of one ``states`` / ``cov_diag`` call must share."""
+    return tuple(req[1:3]) + ((np.asarray(req[3], float).tobytes(),) if len(req) > 3 else ())
 
 
 def _imu_msg(r):

@@ -53,8 +53,10 @@ class MultiStereoVIO:
 
     def __init__(self, n, filter_config=None, frontend_config=None, lane_filter_configs=None,
                  lane_frontend_configs=None, dtype=np.float64, device=0, map_capacity=1024, device_keyframes=True,
-                 handoff="device"):
-        """``filter_config`` / ``lane_filter_configs``: as ``MultiMSCKF``'s
+                 handoff="device", landmarks=None, landmark_capacity=4096, odometry=False):
+        """``landmarks`` / ``landmark_capacity`` / ``odometry``: as
+        ``MultiMSCKF``'s (msckf_odometry.h).
+        ``filter_config`` / ``lane_filter_configs``: as ``MultiMSCKF``'s
         ``config`` / ``lane_configs``; ``frontend_config`` /
         ``lane_frontend_configs``: as ``MultiImageProcessor``'s (device_pipeline
         and device_tracks are switched on in every lane).  The constructor's
@@ -68,7 +70,8 @@ class MultiStereoVIO:
         try:
             self.filters = MultiMSCKF(n, config=filter_config, dtype=dtype, device=device,
                                       lane_configs=lane_filter_configs, device_map=True, map_capacity=map_capacity,
-                                      device_keyframes=device_keyframes)
+                                      device_keyframes=device_keyframes, landmarks=landmarks,
+                                      landmark_capacity=landmark_capacity, odometry=odometry)
         except BaseException:
             self.frontend.close()
             raise
@@ -97,6 +100,13 @@ class MultiStereoVIO:
     def tracks(self, i):
         """Lane i's track table on the device, as ``MultiImageProcessor.tracks``."""
         return self.frontend.tracks(i)
+
+    def landmarks(self, i, first=0, live=False):
+        """Lane i's landmark archive, as ``MultiMSCKF.landmarks``."""
+        return self.filters.landmarks(i, first, live)
+
+    def clear_landmarks(self, i=None):
+        self.filters.clear_landmarks(i)
 
     # ------------------------------------------------------------ callbacks --
     def imu_callback(self, i, msg):
@@ -146,10 +156,11 @@ class StereoVIO:
     ``stereo_callback(stereo_msg) -> vio_result | None``."""
 
     def __init__(self, filter_config=None, frontend_config=None, dtype=np.float64, device=0, map_capacity=1024,
-                 device_keyframes=True, handoff="device"):
+                 device_keyframes=True, handoff="device", landmarks=None, landmark_capacity=4096, odometry=False):
         self.multi = MultiStereoVIO(1, filter_config=filter_config, frontend_config=frontend_config, dtype=dtype,
                                     device=device, map_capacity=map_capacity, device_keyframes=device_keyframes,
-                                    handoff=handoff)
+                                    handoff=handoff, landmarks=landmarks, landmark_capacity=landmark_capacity,
+                                    odometry=odometry)
         self.handoff = self.multi.handoff
 
     def __enter__(self):
@@ -172,6 +183,12 @@ class StereoVIO:
 
     def tracks(self):
         return self.multi.tracks(0)
+
+    def landmarks(self, first=0, live=False):
+        return self.multi.landmarks(0, first, live)
+
+    def clear_landmarks(self):
+        self.multi.clear_landmarks(0)
 
     def imu_callback(self, msg):
         self.multi.imu_callback(0, msg)
