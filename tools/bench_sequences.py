@@ -17,7 +17,11 @@ feeds the frames as array messages (msckf.FeatureArrays); --device-keyframes
 (msckf_keyframes.h); --profile prints a cProfile split of the batched replay to
 stderr.  --landmarks {host,device} keeps the landmark archive and --odometry
 reads the pose covariance with every frame (msckf_odometry.h); --kernel-times
-adds the stage times of a second, untimed replay.
+adds the stage times of a second, untimed replay.  --zupt turns the
+zero-velocity update on with the default ZuptConfig (msckf_zupt.h; its kernels
+are zupt_gain and zupt_apply in --kernel-times) and reports how many updates
+the device applied; --static-s S is the streams' time at rest before they move
+(synth.make_sequence's static_s).
 
 On N GPUs every rank replays its share of the sequences (replicas.shard) on
 its own device; the replicas' host TCP hub (msckf_amd.replicas, no RCCL:
@@ -54,6 +58,10 @@ def main():
     ap.add_argument("--landmarks", choices=("host", "device"), default=None,
                     help="keep the landmark archive (msckf_odometry.h): in numpy, or on the device (needs --device-map)")
     ap.add_argument("--odometry", action="store_true", help="the frames' reads bring the pose covariance along")
+    ap.add_argument("--zupt", action="store_true",
+                    help="the zero-velocity update (msckf_zupt.h), default ZuptConfig")
+    ap.add_argument("--static-s", type=float, default=None,
+                    help="seconds at rest at the start of every stream (make_sequence's static_s; default: its own)")
     ap.add_argument("--kernel-times", action="store_true",
                     help="a second, untimed batched replay with every stage timed (msckf_kernel_times)")
     a = ap.parse_args()
@@ -62,10 +70,13 @@ def main():
     if a.landmarks == "device" and not a.device_map:
         ap.error("--landmarks device needs --device-map")
     opt = dict(landmarks=a.landmarks, odometry=a.odometry) if a.landmarks or a.odometry else {}
+    if a.zupt:
+        opt["zupt"] = msckf_amd.ZuptConfig()
+    seq_kw = {} if a.static_s is None else dict(static_s=a.static_s)
     dtype = np.float32 if a.fp32 else np.float64
     grp = replicas.init()
     mine = replicas.shard(list(range(a.seqs)), grp.rank, grp.world)
-    streams = [FeatureStream.from_synthetic(synth.make_sequence(a.frames, 100 + i)) for i in mine]
+    streams = [FeatureStream.from_synthetic(synth.make_sequence(a.frames, 100 + i, **seq_kw)) for i in mine]
     n_frames = sum(s.n_frames for s in streams)
     multi = MultiMSCKF(len(streams), dtype=dtype, device=grp.local_rank,
                        device_map=a.device_map, device_keyframes=a.device_keyframes, **opt) if streams else None
@@ -88,6 +99,7 @@ def main():
     total_frames = grp.sum_over_ranks(n_frames)
     launches = dict(multi.launches) if multi else {}
     archived = [int(multi.landmarks(i).next_seq) for i in range(len(streams))] if multi and a.landmarks else None
+    zupt_applied = [[int(ln.zupt_count), len(ln.zupt_log)] for ln in multi.lanes] if multi and a.zupt else None
     if multi:
         multi.close()
     kernel_ms = None
@@ -104,8 +116,12 @@ def main():
            "device_map": bool(a.device_map), "device_keyframes": bool(a.device_keyframes),
            "batched_launches_rank0": launches,
            "ate_vs_gt_m_rank0": [round(ate(t, s.gt), 5) for t, s in zip(trajs, streams)]}
-    if opt:   # (without the options the line is what it was)
+    if a.landmarks or a.odometry:   # (without the options the line is what it was)
         out.update(landmarks=a.landmarks, odometry=bool(a.odometry))
+    if a.static_s is not None:
+        out["static_s"] = a.static_s
+    if zupt_applied is not None:   # per lane: updates applied, updates enqueued
+        out["zupt_applied_of_rank0"] = zupt_applied
     if archived is not None:
         out["landmarks_archived_rank0"] = archived
     if kernel_ms is not None:

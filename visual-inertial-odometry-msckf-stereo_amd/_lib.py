@@ -208,6 +208,21 @@ ODOMETRY_SIGS = {
 }
 ODOMETRY_EXPORTED = tuple(ODOMETRY_SIGS)
 
+# the zero-velocity update (include/msckf_zupt.h), same library and context
+ZUPT_VEL, ZUPT_GYRO, ZUPT_ACC = 1, 2, 4
+
+
+class MsckfZuptParamsT(C.Structure):
+    _fields_ = [("vel_noise", C.c_double), ("gyro_noise", C.c_double), ("acc_noise", C.c_double),
+                ("chi2", C.c_double), ("max_speed", C.c_double), ("rows", C.c_int32)]
+
+
+ZUPT_SIGS = {
+    "msckf_zupt_batch": (C.c_int, [_P, C.c_int, _I, _D, _D, C.POINTER(MsckfZuptParamsT)]),
+    "msckf_zupt_results": (C.c_int, [_P, C.c_int, _I, _I, _D, _I64]),
+}
+ZUPT_EXPORTED = tuple(ZUPT_SIGS)
+
 # multi-GPU replica transport, RCCL (include/msckf_replicas.h), same library
 REPLICA_SIGS = {
     "msckf_rccl_unique_id": (C.c_int, [_U8]),
@@ -238,6 +253,7 @@ def load_library(path: str = LIB_PATH):
                                   list(FRONTEND_LANES_SIGS.items()) + list(FRONTEND_TRACKS_SIGS.items()) +
                                   list(MAP_SIGS.items()) + list(KEYFRAME_SIGS.items()) + list(HANDOFF_SIGS.items()) +
                                   list(EQUALIZE_SIGS.items()) + list(ODOMETRY_SIGS.items()) +
+                                  list(ZUPT_SIGS.items()) +
                                   list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res
@@ -724,6 +740,32 @@ class Context:
                 _ptr(p_w, C.c_double), _ptr(n_obs, C.c_int32), _ptr(gam, C.c_double), _ptr(stamp, C.c_int32)))
         return (ids[:k].copy(), p_w[:k].copy(), n_obs[:k].copy(), gam[:k].copy(), stamp[:k].copy(), first.value,
                 seq.value)
+
+    # ---- the zero-velocity update (msckf_zupt.h) ----
+    def zupt_batch(self, filters, gyro_mean, acc_mean, prm):
+        """msckf_zupt_batch: the gated standstill update of the listed filters
+        with their mean angular rates / specific forces ([n][3] each) and the
+        parameters ``prm`` (a ``MsckfZuptParamsT`` or a ``config.ZuptConfig``).
+        Asynchronous, nothing comes back (``zupt_results``)."""
+        filters = _i32(filters)
+        n = len(filters)
+        gyro_mean, acc_mean = _f64(gyro_mean, (n, 3)), _f64(acc_mean, (n, 3))
+        if not isinstance(prm, MsckfZuptParamsT):
+            prm = prm.params()
+        with self.lock:
+            self._check(self.lib.msckf_zupt_batch(self.h, n, _ptr(filters, C.c_int32), _ptr(gyro_mean, C.c_double),
+                                                  _ptr(acc_mean, C.c_double), C.byref(prm)))
+
+    def zupt_results(self, filters):
+        """msckf_zupt_results (synchronises): (applied bool [n], gamma [n],
+        count int64 [n] -- updates ever applied) of the listed filters."""
+        filters = _i32(filters)
+        n = len(filters)
+        app, gam, cnt = np.zeros(n, np.int32), np.zeros(n), np.zeros(n, np.int64)
+        with self.lock:
+            self._check(self.lib.msckf_zupt_results(self.h, n, _ptr(filters, C.c_int32), _ptr(app, C.c_int32),
+                                                    _ptr(gam, C.c_double), _ptr(cnt, C.c_int64)))
+        return app.astype(bool), gam, cnt
 
     def device_info(self):
         """(HIP device index, PCI bus id) this context runs on."""

@@ -86,6 +86,46 @@ def _default_T_cn_cnm1():
         [0, 0, 0, 1.000000000000000]])
 
 
+_ZUPT_ROWS = {"vel": 1, "gyro": 2, "acc": 4}   # MSCKF_ZUPT_VEL / GYRO / ACC (include/msckf_zupt.h)
+
+
+@dataclass
+class ZuptConfig:
+    """Parameters of the zero-velocity update (include/msckf_zupt.h): the noise
+    variances of the three row groups, the gate on gamma (``chi2``; None: the
+    reference's table at the kept rows' count, ``chi2_threshold(m)``), the gate
+    on the speed and the groups kept.  No reference counterpart."""
+    vel_noise: float = 1e-4
+    gyro_noise: float = 4e-6
+    acc_noise: float = 4e-4
+    chi2: "float | None" = None
+    max_speed: float = 0.1
+    rows: tuple = ("vel", "gyro", "acc")
+
+    def mask(self) -> int:
+        rows = (self.rows,) if isinstance(self.rows, str) else tuple(self.rows)
+        m = 0
+        for r in rows:
+            if r not in _ZUPT_ROWS:
+                raise ValueError("unknown ZUPT row group %r (one of %s)" % (r, ", ".join(_ZUPT_ROWS)))
+            m |= _ZUPT_ROWS[r]
+        if m == 0:
+            raise ValueError("ZuptConfig.rows names no row group")
+        return m
+
+    def n_rows(self) -> int:
+        return 3 * bin(self.mask()).count("1")
+
+    def gate(self) -> float:
+        return chi2_threshold(self.n_rows()) if self.chi2 is None else float(self.chi2)
+
+    def params(self):
+        """The C-ABI's msckf_zupt_params_t."""
+        from ._lib import MsckfZuptParamsT
+        return MsckfZuptParamsT(float(self.vel_noise), float(self.gyro_noise), float(self.acc_noise), self.gate(),
+                                float(self.max_speed), self.mask())
+
+
 @dataclass
 class FilterConfig:
     """Filter fields of the reference ConfigEuRoC (config.py:17-124)."""

@@ -16,11 +16,13 @@
 #include "../../include/msckf_keyframes.h"
 #include "../../include/msckf_map.h"
 #include "../../include/msckf_odometry.h"
+#include "../../include/msckf_zupt.h"
 #include "msckf_common.h"
 #include "msckf_handoff_dev.h"
 #include "msckf_launch.h"
 #include "msckf_map_dev.h"
 #include "msckf_subbatch.h"
+#include "msckf_zupt_dev.h"
 
 using namespace msckf;
 
@@ -238,6 +240,12 @@ struct msckf_ctx {
         int state = 0;
         std::vector<int> filters, feat_off, rows;
     } lm;
+    // the zero-velocity update (msckf_zupt.h): absent until the first msckf_zupt_batch
+    struct Zupt {
+        bool on = false;
+        DBuf<unsigned char> store, in;     // W and the records; a call's input block
+        ZuptDev dev{};
+    } zupt;
 };
 
 namespace {
@@ -1376,7 +1384,7 @@ int msckf_destroy(msckf_ctx_t* c) {
         if (s) (void)hipStreamSynchronize(s);
     for (auto* b : {&c->P, &c->imu, &c->cams, &c->P_snap, &c->imu_snap, &c->cams_snap, &c->Hthin, &c->Lc, &c->Vi, &c->Sii, &c->G, &c->Tm, &c->W, &c->Wk,
                     &c->dx, &c->batch, &c->obs_ws, &c->obs_ht, &c->obs_g, &c->fqr, &c->tau, &c->ysq, &c->scratch,
-                    &c->map.store, &c->map.in, &c->map.out, &c->map.aux, &c->lm.store, &c->lm.in})
+                    &c->map.store, &c->map.in, &c->map.out, &c->map.aux, &c->lm.store, &c->lm.in, &c->zupt.store, &c->zupt.in})
         b->release();
     c->map.chi2.release();
     for (auto* b : {&c->ncams, &c->ncams_snap, &c->ident, &c->info, &c->afail, &c->row_off, &c->iscratch})
@@ -1732,3 +1740,5 @@ int msckf_debug_kalman(msckf_ctx_t* c) {
 #include "msckf_map_api.inc"
 // and of include/msckf_odometry.h
 #include "msckf_odometry_api.inc"
+
+#include "msckf_zupt_api.inc"

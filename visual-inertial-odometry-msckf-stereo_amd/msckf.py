@@ -22,6 +22,8 @@ it on the device (include/msckf_handoff.h); with
 device call too (include/msckf_keyframes.h).  ``landmarks`` / ``odometry`` add
 the outputs of include/msckf_odometry.h: the archive of the features that left
 the map through an accepted update, and the published pose's covariance.
+``zupt`` adds the zero-velocity update of include/msckf_zupt.h: once per frame,
+between propagation and augmentation, gated on the device.
 
 Every device interaction of a frame is expressed as a request yielded by a
 step generator (``_frame_steps``); ``feature_callback`` serves the requests
@@ -43,7 +45,7 @@ from collections import OrderedDict, namedtuple
 import numpy as np
 
 from . import _lib
-from .config import CHI2_05, FilterConfig, chi2_threshold
+from .config import CHI2_05, FilterConfig, ZuptConfig, chi2_threshold
 from .geometry import Isometry3d, from_two_vectors, to_quaternion, to_rotation
 from .landmarks import HostRing, Landmarks, check_mode, with_live
 
@@ -116,7 +118,7 @@ class MSCKF:
 
     def __init__(self, config=None, dtype=np.float64, device=0, cam_capacity=None, ctx=None, slot=0,
                  device_map=False, map_capacity=1024, device_keyframes=False, landmarks=None,
-                 landmark_capacity=4096, odometry=False):
+                 landmark_capacity=4096, odometry=False, zupt=None):
         """``device_map``: keep the feature map in the context's tables
         (msckf_map.h) instead of ``map_server``'s dicts; ``map_capacity``: rows
         per filter.  A shared ``ctx`` must already have its tables.
@@ -129,7 +131,11 @@ class MSCKF:
         inside the update's calls (msckf_odometry.h), "host" keeps it in numpy
         from the deferred results.  A shared ``ctx`` must already have its
         rings.  ``odometry``: the callbacks return ``VioOdometry`` -- the
-        frame's read brings the pose and velocity covariance along."""
+        frame's read brings the pose and velocity covariance along.
+        ``zupt`` (a ``ZuptConfig``; None: off): the zero-velocity update
+        (msckf_zupt.h) of every frame that propagated IMU samples, with their
+        means, between propagation and augmentation; the device gates it, the
+        decisions are read with the frame's state into ``zupt_log``."""
         if config is None:
             config = FilterConfig()
         elif not isinstance(config, FilterConfig):
@@ -140,6 +146,12 @@ class MSCKF:
         check_mode(landmarks, self.device_map)
         self.landmark_mode = landmarks
         self.odometry = bool(odometry)
+        if zupt is not None and not isinstance(zupt, ZuptConfig):
+            raise TypeError("zupt must be a ZuptConfig or None, not %r" % (zupt,))
+        self.zupt = zupt
+        self._zupt_prm = zupt.params() if zupt is not None else None   # checks the row names and chi2's table
+        self.zupt_log = []                 # (frame, applied, gamma), one per zero-velocity update enqueued
+        self._zupt_count = 0
         if self.device_keyframes and not self.device_map:
             raise ValueError("device_keyframes=True needs device_map=True: the choice is part of the map's prune "
                              "select")
@@ -233,6 +245,11 @@ class MSCKF:
             return ctx.propagate(f, req[1], req[2], req[3])
         if kind == "augment":
             return ctx.augment(f)
+        if kind == "zupt":   # (kind, mean angular rate, mean specific force)
+            return ctx.zupt_batch([f], req[1], req[2], self._zupt_prm)
+        if kind == "zupt_results":
+            app, gam, cnt = ctx.zupt_results([f])
+            return bool(app[0]), float(gam[0]), int(cnt[0])
         if kind == "triangulate":
             return ctx.triangulate(f, req[1], req[2], req[3])
         if kind == "update":
@@ -333,7 +350,10 @@ class MSCKF:
         if self.is_first_img:
             self.is_first_img = False
             self.imu_timestamp = feature_msg.timestamp
-        yield from self._batch_imu_processing(feature_msg.timestamp)
+        ws, accs = yield from self._batch_imu_processing(feature_msg.timestamp)
+        zupt = self.zupt is not None and len(ws) > 0
+        if zupt:   # the standstill update with the means of exactly the samples propagated (msckf_zupt.h)
+            yield ("zupt", np.mean(np.array(ws).reshape(-1, 3), axis=0), np.mean(np.array(accs).reshape(-1, 3), axis=0))
         yield from self._state_augmentation()
         if self.device_map:
             yield from self._map_add_and_remove_lost(feature_msg)
@@ -349,6 +369,9 @@ class MSCKF:
         else:
             st = yield (("states", 12, 3) if thr > 0 else ("states",))
         self._settle()
+        if zupt:   # the device has drained: the update's record
+            app, gam, self._zupt_count = yield ("zupt_results",)
+            self.zupt_log.append((self._n_published, app, gam))
         res = self._publish_from(feature_msg.timestamp, _lib.unpack_imu(st[0]))
         if self.odometry:
             res = VioOdometry(*res, st[3], st[4])
@@ -358,7 +381,8 @@ class MSCKF:
 
     # ---------------------------------------------------------- propagation --
     def _batch_imu_processing(self, time_bound):
-        """msckf.py:262-287: host walks the buffer, the device applies the samples."""
+        """msckf.py:262-287: host walks the buffer, the device applies the samples.
+        Returns the angular rates and specific forces handed to the device."""
         used = 0
         dts, ws, accs = [], [], []
         t_state = self.imu_timestamp
@@ -380,6 +404,7 @@ class MSCKF:
         self.imu_id = self._next_id
         self._next_id += 1
         self.imu_msg_buffer = self.imu_msg_buffer[used:]
+        return ws, accs
 
     def _state_augmentation(self):
         """msckf.py:385-407"""
@@ -718,6 +743,12 @@ class MSCKF:
             fs = [f for f in self.map_server.values() if f.is_initialized]
             return with_live(rows, [f.id for f in fs], np.array([f.position for f in fs], float).reshape(-1, 3),
                              [len(f.observations) for f in fs])
+
+    @property
+    def zupt_count(self):
+        """Zero-velocity updates applied to this filter's slot (the device's
+        counter as of the last frame's read)."""
+        return self._zupt_count
 
     def clear_landmarks(self):
         """Empties the archive (an online reset does not: the world frame continues)."""

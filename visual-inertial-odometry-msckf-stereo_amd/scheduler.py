@@ -9,6 +9,9 @@ frame in lock step and serves every kind of request for all waiting lanes
 with ONE batched launch:
 
   propagate   -> msckf_propagate_batch   (IMU propagation fused across filters)
+  zupt        -> msckf_zupt_batch        (zupt=ZuptConfig: the standstill update,
+                 gated on the device; zupt_results -> msckf_zupt_results, behind
+                 the frame's states read)
   augment     -> msckf_augment_batch
   triangulate -> msckf_batch_load + msckf_batch_triangulate
   update      -> msckf_batch_load + msckf_batch_update (per row cap), results
@@ -44,7 +47,8 @@ from .vio import MultiStereoVIO, StereoVIO  # noqa: F401  (both ends in one clas
 from .trajectory import Trajectory
 
 # pipeline order: a lane waiting at an earlier stage is served first
-_ORDER = {"set_state": 0, "propagate": 1, "augment": 2, "map_add_lost": 2.5, "map_add_lost_tracks": 2.5, "triangulate": 3,
+_ORDER = {"set_state": 0, "propagate": 1, "zupt": 1.5, "zupt_results": 5.1,
+          "augment": 2, "map_add_lost": 2.5, "map_add_lost_tracks": 2.5, "triangulate": 3,
           "map_triangulate": 3, "update": 4, "map_update": 4, "states": 5, "map_prune_select": 5.3,
           "map_keyframe_select": 5.3,
           "map_prune_commit": 5.6, "prune": 6, "cov_diag": 7, "map_clear": 8}
@@ -55,8 +59,10 @@ class MultiMSCKF:
 
     def __init__(self, n, config=None, dtype=np.float64, device=0, cam_capacity=None, lane_configs=None,
                  device_map=False, map_capacity=1024, device_keyframes=False, landmarks=None, landmark_capacity=4096,
-                 odometry=False):
-        """``landmarks`` / ``landmark_capacity`` / ``odometry``: as ``MSCKF``'s,
+                 odometry=False, zupt=None):
+        """``zupt``: as ``MSCKF``'s, one ``ZuptConfig`` for all lanes (as the
+        device config is): one msckf_zupt_batch for the lanes of a frame step.
+        ``landmarks`` / ``landmark_capacity`` / ``odometry``: as ``MSCKF``'s,
         for every lane ("device": one archive call for the lanes of a lost
         update, msckf_odometry.h; ``landmarks(i)`` reads lane i's).
         ``device_map`` / ``map_capacity``: every lane keeps its feature map
@@ -102,7 +108,8 @@ class MultiMSCKF:
         self.landmark_mode = landmarks
         self.lanes = [MSCKF(cfgs[i], ctx=self.ctx, slot=i, device_map=self.device_map,
                             device_keyframes=self.device_keyframes, landmarks=landmarks,
-                            landmark_capacity=landmark_capacity, odometry=odometry) for i in range(n)]
+                            landmark_capacity=landmark_capacity, odometry=odometry, zupt=zupt)
+                      for i in range(n)]
         self.launches = defaultdict(int)       # batched device calls per request kind
 
     def __len__(self):
@@ -169,6 +176,13 @@ class MultiMSCKF:
         if kind == "augment":
             ctx.augment_batch(slots)
             return [None] * len(group)
+        if kind == "zupt":   # the lanes share the parameters (one ZuptConfig)
+            ctx.zupt_batch(slots, np.array([r[1] for r in reqs]), np.array([r[2] for r in reqs]),
+                           self.lanes[group[0]]._zupt_prm)
+            return [None] * len(group)
+        if kind == "zupt_results":
+            app, gam, cnt = ctx.zupt_results(slots)
+            return [(bool(app[w]), float(gam[w]), int(cnt[w])) for w in range(len(group))]
         if kind == "triangulate":
             self._load(slots, reqs, with_pw=False)
             ctx.batch_triangulate()

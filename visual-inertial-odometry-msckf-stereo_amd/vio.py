@@ -53,9 +53,10 @@ class MultiStereoVIO:
 
     def __init__(self, n, filter_config=None, frontend_config=None, lane_filter_configs=None,
                  lane_frontend_configs=None, dtype=np.float64, device=0, map_capacity=1024, device_keyframes=True,
-                 handoff="device", landmarks=None, landmark_capacity=4096, odometry=False):
+                 handoff="device", landmarks=None, landmark_capacity=4096, odometry=False, zupt=None):
         """``landmarks`` / ``landmark_capacity`` / ``odometry``: as
-        ``MultiMSCKF``'s (msckf_odometry.h).
+        ``MultiMSCKF``'s (msckf_odometry.h); ``zupt``: as ``MultiMSCKF``'s
+        (msckf_zupt.h; ``zupt_log(i)`` reads lane i's decisions).
         ``filter_config`` / ``lane_filter_configs``: as ``MultiMSCKF``'s
         ``config`` / ``lane_configs``; ``frontend_config`` /
         ``lane_frontend_configs``: as ``MultiImageProcessor``'s (device_pipeline
@@ -71,7 +72,7 @@ class MultiStereoVIO:
             self.filters = MultiMSCKF(n, config=filter_config, dtype=dtype, device=device,
                                       lane_configs=lane_filter_configs, device_map=True, map_capacity=map_capacity,
                                       device_keyframes=device_keyframes, landmarks=landmarks,
-                                      landmark_capacity=landmark_capacity, odometry=odometry)
+                                      landmark_capacity=landmark_capacity, odometry=odometry, zupt=zupt)
         except BaseException:
             self.frontend.close()
             raise
@@ -107,6 +108,10 @@ class MultiStereoVIO:
 
     def clear_landmarks(self, i=None):
         self.filters.clear_landmarks(i)
+
+    def zupt_log(self, i):
+        """Lane i's zero-velocity decisions, (frame, applied, gamma) per update enqueued."""
+        return self.filters.lanes[i].zupt_log
 
     # ------------------------------------------------------------ callbacks --
     def imu_callback(self, i, msg):
@@ -156,11 +161,12 @@ class StereoVIO:
     ``stereo_callback(stereo_msg) -> vio_result | None``."""
 
     def __init__(self, filter_config=None, frontend_config=None, dtype=np.float64, device=0, map_capacity=1024,
-                 device_keyframes=True, handoff="device", landmarks=None, landmark_capacity=4096, odometry=False):
+                 device_keyframes=True, handoff="device", landmarks=None, landmark_capacity=4096, odometry=False,
+                 zupt=None):
         self.multi = MultiStereoVIO(1, filter_config=filter_config, frontend_config=frontend_config, dtype=dtype,
                                     device=device, map_capacity=map_capacity, device_keyframes=device_keyframes,
                                     handoff=handoff, landmarks=landmarks, landmark_capacity=landmark_capacity,
-                                    odometry=odometry)
+                                    odometry=odometry, zupt=zupt)
         self.handoff = self.multi.handoff
 
     def __enter__(self):
@@ -189,6 +195,14 @@ class StereoVIO:
 
     def clear_landmarks(self):
         self.multi.clear_landmarks(0)
+
+    @property
+    def zupt_log(self):
+        return self.multi.zupt_log(0)
+
+    @property
+    def zupt_count(self):
+        return self.filter.zupt_count
 
     def imu_callback(self, msg):
         self.multi.imu_callback(0, msg)
