@@ -21,7 +21,11 @@ adds the stage times of a second, untimed replay.  --zupt turns the
 zero-velocity update on with the default ZuptConfig (msckf_zupt.h; its kernels
 are zupt_gain and zupt_apply in --kernel-times) and reports how many updates
 the device applied; --static-s S is the streams' time at rest before they move
-(synth.make_sequence's static_s).
+(synth.make_sequence's static_s).  --aiding turns the aiding fixes on
+(msckf_aid.h; kernels aid_gain and aid_apply): position + velocity messages
+from the streams' ground truth at --aid-rate Hz (default 5), 12 ms before a
+frame, with 2 cm / 2 cm/s noise, rotated into each filter's world frame, and
+reports how many fixes the device applied.
 
 On N GPUs every rank replays its share of the sequences (replicas.shard) on
 its own device; the replicas' host TCP hub (msckf_amd.replicas, no RCCL:
@@ -46,6 +50,31 @@ from msckf_amd.scheduler import MultiMSCKF  # noqa: E402
 from msckf_amd.trajectory import ate  # noqa: E402
 
 
+def aiding_fixes(seq, static_s, rate, seed, lead=0.012, sigma=0.02, t_start=100.0):
+    """Position + velocity messages for ``seq`` from its ground truth, in the
+    filter's world frame: ``lead`` before every (20 / rate)-th frame from the
+    first one the filter publishes (one second of gravity initialisation), with
+    ``sigma`` noise.  The two world frames are aligned by A = R_filter_iw
+    R_truth_iw^T at that frame, where both origins are 0 (the stream rests): the
+    filter's initial attitude is the one its gravity initialisation will
+    compute from the first 200 IMU samples."""
+    from msckf_amd.geometry import from_two_vectors, to_rotation
+    g_imu = np.mean([m.linear_acceleration for m in seq.imu[:200]], axis=0)
+    q0 = from_two_vectors(-np.array([0.0, 0.0, -np.linalg.norm(g_imu)]), g_imu)
+    first = int(np.searchsorted(seq.gt_t, seq.imu[199].vio_timestamp__))
+    A = to_rotation(q0).T @ seq.gt_R[first].T
+    rng = np.random.default_rng(seed)
+    t0, h, out = t_start + static_s, 1e-4, []
+    for k in range(first, len(seq.gt_t), max(1, int(round(20.0 / rate)))):
+        t = seq.gt_t[k] - lead
+        p = synth._traj(t, t0)[0]
+        v = (synth._traj(t + h, t0)[0] - synth._traj(t - h, t0)[0]) / (2 * h)
+        out.append(msckf_amd.AidingFix(t, position=A @ p + sigma * rng.standard_normal(3),
+                                       velocity=A @ v + sigma * rng.standard_normal(3),
+                                       position_var=sigma ** 2, velocity_var=sigma ** 2))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seqs", type=int, default=11)
@@ -62,6 +91,9 @@ def main():
                     help="the zero-velocity update (msckf_zupt.h), default ZuptConfig")
     ap.add_argument("--static-s", type=float, default=None,
                     help="seconds at rest at the start of every stream (make_sequence's static_s; default: its own)")
+    ap.add_argument("--aiding", action="store_true",
+                    help="aiding fixes (msckf_aid.h): synthetic position + velocity messages from the ground truth")
+    ap.add_argument("--aid-rate", type=float, default=5.0, help="fixes per second and stream with --aiding")
     ap.add_argument("--kernel-times", action="store_true",
                     help="a second, untimed batched replay with every stage timed (msckf_kernel_times)")
     a = ap.parse_args()
@@ -72,17 +104,26 @@ def main():
     opt = dict(landmarks=a.landmarks, odometry=a.odometry) if a.landmarks or a.odometry else {}
     if a.zupt:
         opt["zupt"] = msckf_amd.ZuptConfig()
+    if a.aiding:
+        opt["aiding"] = msckf_amd.AidingConfig()
     seq_kw = {} if a.static_s is None else dict(static_s=a.static_s)
     dtype = np.float32 if a.fp32 else np.float64
     grp = replicas.init()
     mine = replicas.shard(list(range(a.seqs)), grp.rank, grp.world)
-    streams = [FeatureStream.from_synthetic(synth.make_sequence(a.frames, 100 + i, **seq_kw)) for i in mine]
+    seqs = [synth.make_sequence(a.frames, 100 + i, **seq_kw) for i in mine]
+    streams = [FeatureStream.from_synthetic(q) for q in seqs]
+    fixes = [aiding_fixes(q, 1.2 if a.static_s is None else a.static_s, a.aid_rate, 1000 + i)
+             for q, i in zip(seqs, mine)] if a.aiding else None
     n_frames = sum(s.n_frames for s in streams)
     multi = MultiMSCKF(len(streams), dtype=dtype, device=grp.local_rank,
                        device_map=a.device_map, device_keyframes=a.device_keyframes, **opt) if streams else None
     # the messages are the front-end's output: built before either timed
     # region (as the bench's ATE leg does), fresh objects for each run
     msgs = [s.messages(arrays=a.device_map) for s in streams]
+    if fixes:   # the messages of the aiding sensor are inputs too
+        for i, fx in enumerate(fixes):
+            for f in fx:
+                multi.aiding_callback(i, f)
     grp.barrier()
     prof = None
     if a.profile:
@@ -100,6 +141,7 @@ def main():
     launches = dict(multi.launches) if multi else {}
     archived = [int(multi.landmarks(i).next_seq) for i in range(len(streams))] if multi and a.landmarks else None
     zupt_applied = [[int(ln.zupt_count), len(ln.zupt_log)] for ln in multi.lanes] if multi and a.zupt else None
+    aid_applied = [[int(ln.aid_count), len(ln.aid_log)] for ln in multi.lanes] if multi and a.aiding else None
     if multi:
         multi.close()
     kernel_ms = None
@@ -107,6 +149,9 @@ def main():
         prof_run = MultiMSCKF(len(streams), dtype=dtype, device=grp.local_rank, device_map=a.device_map,
                               device_keyframes=a.device_keyframes, **opt)
         prof_run.ctx.set_profiling(True)
+        for i, fx in enumerate(fixes or []):
+            for f in fx:
+                prof_run.aiding_callback(i, f)
         prof_run.run_streams(streams, messages=[s.messages(arrays=a.device_map) for s in streams])
         kernel_ms = {k: [round(ms, 3), n] for k, (ms, n) in prof_run.ctx.kernel_times().items()}
         prof_run.close()
@@ -122,6 +167,8 @@ def main():
         out["static_s"] = a.static_s
     if zupt_applied is not None:   # per lane: updates applied, updates enqueued
         out["zupt_applied_of_rank0"] = zupt_applied
+    if aid_applied is not None:   # per lane: fixes applied, fixes enqueued
+        out["aid_applied_of_rank0"] = aid_applied
     if archived is not None:
         out["landmarks_archived_rank0"] = archived
     if kernel_ms is not None:
@@ -132,8 +179,10 @@ def main():
             evs = [[(k, m if k == 0 else s.frame_arrays(j)) for (k, m), j in
                     zip(ev, np.cumsum([k for k, _ in ev]) - 1)] for s, ev in zip(streams, evs)]
         t0 = time.perf_counter()
-        for s, ev in zip(streams, evs):
+        for i, (s, ev) in enumerate(zip(streams, evs)):
             flt = msckf_amd.MSCKF(dtype=dtype, device_map=a.device_map, device_keyframes=a.device_keyframes, **opt)
+            for f in (fixes[i] if fixes else []):
+                flt.aiding_callback(f)
             replay(flt, s, events=ev)
             flt.close()
         el_s = time.perf_counter() - t0

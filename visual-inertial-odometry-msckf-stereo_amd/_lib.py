@@ -223,6 +223,34 @@ ZUPT_SIGS = {
 }
 ZUPT_EXPORTED = tuple(ZUPT_SIGS)
 
+# the aiding fixes (include/msckf_aid.h), same library and context
+AID_POS, AID_VEL, AID_BVEL, AID_DIR = 0x007, 0x038, 0x1c0, 0xe00
+
+
+class MsckfAidParamsT(C.Structure):
+    _fields_ = [("lever", C.c_double * 3), ("R_body", C.c_double * 9), ("dir_w", C.c_double * 3),
+                ("chi2", C.c_double * 12)]
+
+
+class MsckfAidFixT(C.Structure):
+    _fields_ = [("z", C.c_double * 12), ("var", C.c_double * 12), ("dt", C.c_double), ("rows", C.c_int32)]
+
+
+def aid_fix(z, var, dt, rows):
+    """A msckf_aid_fix_t from z (12), var (12), the age dt and the row mask."""
+    f = MsckfAidFixT()
+    f.z[:] = [float(x) for x in z]
+    f.var[:] = [float(x) for x in var]
+    f.dt, f.rows = float(dt), int(rows)
+    return f
+
+
+AID_SIGS = {
+    "msckf_aid_batch": (C.c_int, [_P, C.c_int, _I, C.POINTER(MsckfAidFixT), C.POINTER(MsckfAidParamsT)]),
+    "msckf_aid_results": (C.c_int, [_P, C.c_int, _I, _I, _D, _I, _I64]),
+}
+AID_EXPORTED = tuple(AID_SIGS)
+
 # multi-GPU replica transport, RCCL (include/msckf_replicas.h), same library
 REPLICA_SIGS = {
     "msckf_rccl_unique_id": (C.c_int, [_U8]),
@@ -253,7 +281,7 @@ def load_library(path: str = LIB_PATH):
                                   list(FRONTEND_LANES_SIGS.items()) + list(FRONTEND_TRACKS_SIGS.items()) +
                                   list(MAP_SIGS.items()) + list(KEYFRAME_SIGS.items()) + list(HANDOFF_SIGS.items()) +
                                   list(EQUALIZE_SIGS.items()) + list(ODOMETRY_SIGS.items()) +
-                                  list(ZUPT_SIGS.items()) +
+                                  list(ZUPT_SIGS.items()) + list(AID_SIGS.items()) +
                                   list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res
@@ -766,6 +794,36 @@ class Context:
             self._check(self.lib.msckf_zupt_results(self.h, n, _ptr(filters, C.c_int32), _ptr(app, C.c_int32),
                                                     _ptr(gam, C.c_double), _ptr(cnt, C.c_int64)))
         return app.astype(bool), gam, cnt
+
+    # ---- the aiding fixes (msckf_aid.h) ----
+    def aid_batch(self, filters, fixes, prm):
+        """msckf_aid_batch: the gated update of the listed filters, each with its
+        own fix (``MsckfAidFixT``, see ``aid_fix``), and the parameters ``prm``
+        (a ``MsckfAidParamsT`` or a ``config.AidingConfig``).  Asynchronous,
+        nothing comes back (``aid_results``)."""
+        filters = _i32(filters)
+        n = len(filters)
+        fixes = list(fixes)
+        if len(fixes) != n:
+            raise ValueError("aid_batch: %d filters but %d fixes" % (n, len(fixes)))
+        arr = (MsckfAidFixT * max(n, 1))(*fixes)
+        if not isinstance(prm, MsckfAidParamsT):
+            prm = prm.params()
+        with self.lock:
+            self._check(self.lib.msckf_aid_batch(self.h, n, _ptr(filters, C.c_int32), arr, C.byref(prm)))
+
+    def aid_results(self, filters):
+        """msckf_aid_results (synchronises): (applied bool [n], gamma [n], rows
+        int32 [n] -- the last fix's mask, count int64 [n] -- fixes ever applied)
+        of the listed filters."""
+        filters = _i32(filters)
+        n = len(filters)
+        app, gam, rows, cnt = np.zeros(n, np.int32), np.zeros(n), np.zeros(n, np.int32), np.zeros(n, np.int64)
+        with self.lock:
+            self._check(self.lib.msckf_aid_results(self.h, n, _ptr(filters, C.c_int32), _ptr(app, C.c_int32),
+                                                   _ptr(gam, C.c_double), _ptr(rows, C.c_int32),
+                                                   _ptr(cnt, C.c_int64)))
+        return app.astype(bool), gam, rows, cnt
 
     def device_info(self):
         """(HIP device index, PCI bus id) this context runs on."""

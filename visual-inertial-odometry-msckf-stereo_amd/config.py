@@ -59,6 +59,17 @@ def chi2_threshold(dof: int) -> float:
     return CHI2_05[dof - 1]
 
 
+# chi2.ppf(0.95, dof) for dof = 1..12: the UPPER 0.95 quantiles, the gate of the
+# aiding fixes (include/msckf_aid.h).  chi2_threshold is the reference's lower
+# 0.05 tail (quirk Q6) and would reject 95 % of good fixes.
+CHI2_95 = (
+    3.841458820694124, 5.991464547107979, 7.814727903251179,
+    9.487729036781154, 11.070497693516351, 12.591587243743977,
+    14.067140449340169, 15.50731305586545, 16.918977604620448,
+    18.307038053275146, 19.67513757268249, 21.02606981748307,
+)
+
+
 @dataclass
 class OptimizationConfig:
     """Reference OptimizationConfigEuRoC (config.py:5-15)."""
@@ -124,6 +135,133 @@ class ZuptConfig:
         from ._lib import MsckfZuptParamsT
         return MsckfZuptParamsT(float(self.vel_noise), float(self.gyro_noise), float(self.acc_noise), self.gate(),
                                 float(self.max_speed), self.mask())
+
+
+AID_GROUPS = ("position", "velocity", "body_velocity", "direction")   # rows 3 g + axis (include/msckf_aid.h)
+
+
+def _orthonormal(R, what):
+    R = np.asarray(R, float)
+    if R.shape != (3, 3) or not (np.abs(R @ R.T - np.eye(3)).max() <= 1e-6):
+        raise ValueError("%s must be a 3 x 3 orthonormal matrix (to 1e-6)" % what)
+    return R
+
+
+@dataclass
+class AidingFix:
+    """One aiding message: any of an antenna position and an IMU velocity (both
+    in the external frame of ``AidingConfig.world_from_ext``), a velocity in the
+    odometer frame and the reference direction as seen in the IMU frame, taken
+    at ``timestamp``.  ``*_var``: the variance, a scalar or one per axis;
+    ``*_axes``: which axes are used (a barometer is ``position`` with
+    ``position_axes=(0, 0, 1)``)."""
+    timestamp: float
+    position: "np.ndarray | None" = None
+    velocity: "np.ndarray | None" = None
+    body_velocity: "np.ndarray | None" = None
+    direction: "np.ndarray | None" = None
+    position_var: "float | tuple" = 4e-4
+    velocity_var: "float | tuple" = 4e-4
+    body_velocity_var: "float | tuple" = 4e-4
+    direction_var: "float | tuple" = 1e-4
+    position_axes: tuple = (1, 1, 1)
+    velocity_axes: tuple = (1, 1, 1)
+    body_velocity_axes: tuple = (1, 1, 1)
+    direction_axes: tuple = (1, 1, 1)
+
+
+@dataclass
+class AidingConfig:
+    """Parameters of the aiding fixes (include/msckf_aid.h): the antenna's lever
+    arm in the IMU frame, the rotation IMU -> odometer frame, the reference
+    direction in the filter's world frame, the gate on gamma (``chi2``; None: the
+    upper 0.95 quantile ``CHI2_95`` at the kept rows' count, a float: that value
+    for every count), the largest age at which a fix is still used, and
+    ``world_from_ext`` = (R, t): external positions become R x + t and external
+    velocities R v in the filter's world frame (gravity-aligned, origin and yaw
+    set at initialisation).  No reference counterpart."""
+    lever: tuple = (0.0, 0.0, 0.0)
+    R_body: "np.ndarray" = field(default_factory=lambda: np.eye(3))
+    dir_w: tuple = (1.0, 0.0, 0.0)
+    chi2: "float | None" = None
+    max_age: float = 0.05
+    world_from_ext: tuple = field(default_factory=lambda: (np.eye(3), np.zeros(3)))
+
+    def gates(self):
+        """The gate by the number of kept rows, 1..12."""
+        return tuple(CHI2_95) if self.chi2 is None else (float(self.chi2),) * 12
+
+    def check(self):
+        if np.asarray(self.lever, float).shape != (3,) or not np.isfinite(np.asarray(self.lever, float)).all():
+            raise ValueError("AidingConfig.lever must be three finite numbers")
+        _orthonormal(self.R_body, "AidingConfig.R_body")
+        d = np.asarray(self.dir_w, float)
+        if d.shape != (3,) or not (abs(np.linalg.norm(d) - 1.0) <= 1e-6):
+            raise ValueError("AidingConfig.dir_w must be a unit vector (to 1e-6)")
+        if not (self.max_age >= 0.0):
+            raise ValueError("AidingConfig.max_age = %r must be >= 0" % (self.max_age,))
+        if np.isnan(self.gates()).any():
+            raise ValueError("AidingConfig.chi2 is NaN")
+        R, t = self.world_from_ext
+        _orthonormal(R, "AidingConfig.world_from_ext's rotation")
+        if np.asarray(t, float).shape != (3,):
+            raise ValueError("AidingConfig.world_from_ext's translation must be three numbers")
+
+    def params(self):
+        """The C-ABI's msckf_aid_params_t."""
+        from ._lib import MsckfAidParamsT
+        self.check()
+        p = MsckfAidParamsT()
+        p.lever[:] = [float(x) for x in self.lever]
+        p.R_body[:] = [float(x) for x in np.asarray(self.R_body, float).ravel()]
+        p.dir_w[:] = [float(x) for x in self.dir_w]
+        p.chi2[:] = self.gates()
+        return p
+
+    def rows_of(self, fix):
+        """(z (12), var (12), mask) of an ``AidingFix`` in the filter's world
+        frame; the entries of rows the fix does not carry are 0 / 1."""
+        R, t = np.asarray(self.world_from_ext[0], float), np.asarray(self.world_from_ext[1], float)
+        z, var, mask = np.zeros(12), np.ones(12), 0
+        for g, name in enumerate(AID_GROUPS):
+            val = getattr(fix, name)
+            if val is None:
+                continue
+            val = np.asarray(val, float).reshape(3)
+            if name == "position":
+                val = R @ val + t
+            elif name == "velocity":
+                val = R @ val
+            axes = tuple(getattr(fix, name + "_axes"))
+            if len(axes) != 3:
+                raise ValueError("AidingFix.%s_axes must have three entries" % name)
+            z[3 * g:3 * g + 3] = val
+            var[3 * g:3 * g + 3] = np.broadcast_to(np.asarray(getattr(fix, name + "_var"), float), (3,))
+            for ax in range(3):
+                if axes[ax]:
+                    mask |= 1 << (3 * g + ax)
+        return z, var, mask
+
+    def merge(self, fixes, t_frame):
+        """The fixes with t_frame - max_age <= timestamp <= t_frame merged into
+        one measurement, each group from the newest fix that carries it:
+        (z (12), var (12), dt, mask), or None if there is none.  dt is the age
+        of the fix that gave the position rows (the only rows that use it), or
+        of the newest fix without them."""
+        z, var, mask, dt = np.zeros(12), np.ones(12), 0, None
+        for fix in sorted((f for f in fixes if t_frame - self.max_age <= f.timestamp <= t_frame),
+                          key=lambda f: -f.timestamp):
+            zf, vf, mf = self.rows_of(fix)
+            if dt is None and mf:
+                dt = t_frame - fix.timestamp
+            for g in range(4):
+                grp = 7 << (3 * g)
+                if (mf & grp) and not (mask & grp):
+                    z[3 * g:3 * g + 3], var[3 * g:3 * g + 3] = zf[3 * g:3 * g + 3], vf[3 * g:3 * g + 3]
+                    mask |= mf & grp
+                    if g == 0:
+                        dt = t_frame - fix.timestamp
+        return (z, var, float(dt), mask) if mask else None
 
 
 @dataclass

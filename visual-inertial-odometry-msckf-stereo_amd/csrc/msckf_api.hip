@@ -17,6 +17,8 @@
 #include "../../include/msckf_map.h"
 #include "../../include/msckf_odometry.h"
 #include "../../include/msckf_zupt.h"
+#include "../../include/msckf_aid.h"
+#include "msckf_aid_dev.h"
 #include "msckf_common.h"
 #include "msckf_handoff_dev.h"
 #include "msckf_launch.h"
@@ -246,6 +248,12 @@ struct msckf_ctx {
         DBuf<unsigned char> store, in;     // W and the records; a call's input block
         ZuptDev dev{};
     } zupt;
+    // the aiding fixes (msckf_aid.h): absent until the first msckf_aid_batch
+    struct Aid {
+        bool on = false;
+        DBuf<unsigned char> store, in;     // W and the records; a call's input block
+        AidDev dev{};
+    } aid;
 };
 
 namespace {
@@ -1384,7 +1392,8 @@ int msckf_destroy(msckf_ctx_t* c) {
         if (s) (void)hipStreamSynchronize(s);
     for (auto* b : {&c->P, &c->imu, &c->cams, &c->P_snap, &c->imu_snap, &c->cams_snap, &c->Hthin, &c->Lc, &c->Vi, &c->Sii, &c->G, &c->Tm, &c->W, &c->Wk,
                     &c->dx, &c->batch, &c->obs_ws, &c->obs_ht, &c->obs_g, &c->fqr, &c->tau, &c->ysq, &c->scratch,
-                    &c->map.store, &c->map.in, &c->map.out, &c->map.aux, &c->lm.store, &c->lm.in, &c->zupt.store, &c->zupt.in})
+                    &c->map.store, &c->map.in, &c->map.out, &c->map.aux, &c->lm.store, &c->lm.in, &c->zupt.store, &c->zupt.in,
+                    &c->aid.store, &c->aid.in})
         b->release();
     c->map.chi2.release();
     for (auto* b : {&c->ncams, &c->ncams_snap, &c->ident, &c->info, &c->afail, &c->row_off, &c->iscratch})
@@ -1742,3 +1751,5 @@ int msckf_debug_kalman(msckf_ctx_t* c) {
 #include "msckf_odometry_api.inc"
 
 #include "msckf_zupt_api.inc"
+
+#include "msckf_aid_api.inc"

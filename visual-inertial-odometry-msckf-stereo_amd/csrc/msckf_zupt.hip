@@ -9,13 +9,15 @@
 //                 state correction.  Reads P, writes none of it.
 //   k_zupt_apply  one workgroup per 32 x 32 tile of the lower triangle and listed
 //                 filter: P_ij <- T(double(P_ij) - sum_k W_ik W_jk), k ascending,
-//                 mirrored into the upper triangle through LDS.
+//                 mirrored into the upper triangle through LDS
+//                 (msckf_rank_apply.h, shared with the aiding fixes).
 // The gain reads rows 0:12 of P, which the rank-m update rewrites: with more than
 // one workgroup per filter they have to be separate launches.  All arithmetic is
 // fp64 whatever T; no atomics, no data-dependent order.
 #include "../../include/msckf_zupt.h"
 #include "msckf_common.h"
 #include "msckf_correct.h"
+#include "msckf_rank_apply.h"
 #include "msckf_zupt_dev.h"
 
 namespace msckf {
@@ -173,58 +175,13 @@ __global__ void __launch_bounds__(ZG_NT) k_zupt_gain(DevState<T> st, ZuptDev z, 
     }
 }
 
-// Tile t of the lower triangle (column-major enumeration, colmajor_col) of listed
-// filter w.  Every value is computed before the workgroup's first store: a diagonal
-// tile reads P[max(i,j)][min(i,j)] for both (i,j) and (j,i), so both get the same
-// bits, and those are entries other threads of the tile write.
+// Tile bk.x of the lower triangle of listed filter bk.y (msckf_rank_apply.h).
 template <typename T>
 __global__ void __launch_bounds__(256) k_zupt_apply(DevState<T> st, ZuptDev z, int m, const int* filters) {
     const Blk3 bk = xcd_blk3();
     const int b = filters[bk.y];
     if (!z.applied[b]) return;
-    const int D = 21 + 6 * st.ncams[b], ld = st.Dmax, nt = (D + ZUPT_TS - 1) / ZUPT_TS;
-    if (bk.x >= nt * (nt + 1) / 2) return;
-    const int tj = colmajor_col(bk.x, nt), ti = tj + bk.x - (tj * nt - tj * (tj - 1) / 2);
-    const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
-    __shared__ double Wi[ZUPT_TS][ZUPT_M], Wj[ZUPT_TS][ZUPT_M];
-    __shared__ T tile[ZUPT_TS][ZUPT_TS + 1];
-    const double* W = z.W + (size_t)b * ld * ZUPT_M;
-    for (int e = tid; e < ZUPT_TS * ZUPT_M; e += 256) {
-        const int row = e / ZUPT_M, k = e - row * ZUPT_M;
-        const int gi = ZUPT_TS * ti + row, gj = ZUPT_TS * tj + row;
-        Wi[row][k] = (gi < D && k < m) ? W[(size_t)gi * ZUPT_M + k] : 0.0;
-        Wj[row][k] = (gj < D && k < m) ? W[(size_t)gj * ZUPT_M + k] : 0.0;
-    }
-    __syncthreads();
-    T* P = st.P + (size_t)b * ld * ld;
-    const bool diag = ti == tj;
-    const int j = ZUPT_TS * tj + tx;
-    T v[4];
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-        const int li = ty + 8 * rr, i = ZUPT_TS * ti + li;
-        v[rr] = T(0);
-        if (i < D && j < D) {
-            const int hi = (diag && j > i) ? j : i, lo = (diag && j > i) ? i : j;
-            double s = 0.0;
-            for (int k = 0; k < m; ++k) s += Wi[li][k] * Wj[tx][k];
-            v[rr] = (T)((double)P[(size_t)hi * ld + lo] - s);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-        const int li = ty + 8 * rr, i = ZUPT_TS * ti + li;
-        if (i < D && j < D) P[(size_t)i * ld + j] = v[rr];
-        tile[li][tx] = v[rr];
-    }
-    if (diag) return;
-    __syncthreads();
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {   // the mirror: row (tj, lj) of the upper triangle, contiguous over tx
-        const int lj = ty + 8 * rr, jj = ZUPT_TS * tj + lj, ii = ZUPT_TS * ti + tx;
-        if (jj < D && ii < D) P[(size_t)jj * ld + ii] = tile[tx][lj];
-    }
+    rank_apply_tile<T, ZUPT_M>(st, b, z.W + (size_t)b * st.Dmax * ZUPT_M, m, bk.x);
 }
 
 template <typename T>

@@ -23,7 +23,9 @@ device call too (include/msckf_keyframes.h).  ``landmarks`` / ``odometry`` add
 the outputs of include/msckf_odometry.h: the archive of the features that left
 the map through an accepted update, and the published pose's covariance.
 ``zupt`` adds the zero-velocity update of include/msckf_zupt.h: once per frame,
-between propagation and augmentation, gated on the device.
+between propagation and augmentation, gated on the device.  ``aiding`` adds the
+aiding fixes of include/msckf_aid.h: external position, velocity, body-frame
+velocity and heading messages (``aiding_callback``), applied at the same point.
 
 Every device interaction of a frame is expressed as a request yielded by a
 step generator (``_frame_steps``); ``feature_callback`` serves the requests
@@ -45,7 +47,7 @@ from collections import OrderedDict, namedtuple
 import numpy as np
 
 from . import _lib
-from .config import CHI2_05, FilterConfig, ZuptConfig, chi2_threshold
+from .config import CHI2_05, AidingConfig, FilterConfig, ZuptConfig, chi2_threshold
 from .geometry import Isometry3d, from_two_vectors, to_quaternion, to_rotation
 from .landmarks import HostRing, Landmarks, check_mode, with_live
 
@@ -118,7 +120,7 @@ class MSCKF:
 
     def __init__(self, config=None, dtype=np.float64, device=0, cam_capacity=None, ctx=None, slot=0,
                  device_map=False, map_capacity=1024, device_keyframes=False, landmarks=None,
-                 landmark_capacity=4096, odometry=False, zupt=None):
+                 landmark_capacity=4096, odometry=False, zupt=None, aiding=None):
         """``device_map``: keep the feature map in the context's tables
         (msckf_map.h) instead of ``map_server``'s dicts; ``map_capacity``: rows
         per filter.  A shared ``ctx`` must already have its tables.
@@ -135,7 +137,12 @@ class MSCKF:
         ``zupt`` (a ``ZuptConfig``; None: off): the zero-velocity update
         (msckf_zupt.h) of every frame that propagated IMU samples, with their
         means, between propagation and augmentation; the device gates it, the
-        decisions are read with the frame's state into ``zupt_log``."""
+        decisions are read with the frame's state into ``zupt_log``.
+        ``aiding`` (an ``AidingConfig``; None: off): the fixes given to
+        ``aiding_callback`` are applied by the frame that follows them within
+        ``max_age`` (msckf_aid.h), after propagation (and the zero-velocity
+        update) and before augmentation; the device gates them, the decisions
+        are read with the frame's state into ``aid_log``."""
         if config is None:
             config = FilterConfig()
         elif not isinstance(config, FilterConfig):
@@ -152,6 +159,13 @@ class MSCKF:
         self._zupt_prm = zupt.params() if zupt is not None else None   # checks the row names and chi2's table
         self.zupt_log = []                 # (frame, applied, gamma), one per zero-velocity update enqueued
         self._zupt_count = 0
+        if aiding is not None and not isinstance(aiding, AidingConfig):
+            raise TypeError("aiding must be an AidingConfig or None, not %r" % (aiding,))
+        self.aiding = aiding
+        self._aid_prm = aiding.params() if aiding is not None else None   # checks R_body, dir_w, world_from_ext
+        self._aid_buffer = []              # AidingFix messages not yet past a frame
+        self.aid_log = []                  # (frame, rows, applied, gamma), one per fix enqueued
+        self._aid_count = 0
         if self.device_keyframes and not self.device_map:
             raise ValueError("device_keyframes=True needs device_map=True: the choice is part of the map's prune "
                              "select")
@@ -250,6 +264,11 @@ class MSCKF:
         if kind == "zupt_results":
             app, gam, cnt = ctx.zupt_results([f])
             return bool(app[0]), float(gam[0]), int(cnt[0])
+        if kind == "aid":   # (kind, the frame's merged fix)
+            return ctx.aid_batch([f], [req[1]], self._aid_prm)
+        if kind == "aid_results":
+            app, gam, rows, cnt = ctx.aid_results([f])
+            return bool(app[0]), float(gam[0]), int(rows[0]), int(cnt[0])
         if kind == "triangulate":
             return ctx.triangulate(f, req[1], req[2], req[3])
         if kind == "update":
@@ -317,6 +336,31 @@ class MSCKF:
                 self._drive(self._initialize_gravity_and_bias())
                 self.is_gravity_set = True
 
+    def aiding_callback(self, fix):
+        """Buffers an ``AidingFix``; the next frame at or after its timestamp
+        applies it if it is no older than ``max_age`` by then."""
+        if self.aiding is None:
+            raise ValueError("aiding_callback needs MSCKF(aiding=AidingConfig())")
+        with self._lock:
+            buf = self._aid_buffer   # kept in time order; messages usually arrive so
+            k = len(buf)
+            while k > 0 and buf[k - 1].timestamp > fix.timestamp:
+                k -= 1
+            buf.insert(k, fix)
+
+    def _take_fix(self, t_frame):
+        """The frame's merged fix as a msckf_aid_fix_t (None without one); the
+        fixes up to the frame time leave the buffer."""
+        buf = self._aid_buffer
+        if not buf or buf[0].timestamp > t_frame:
+            return None
+        n = 1
+        while n < len(buf) and buf[n].timestamp <= t_frame:
+            n += 1
+        self._aid_buffer = buf[n:]
+        merged = self.aiding.merge(buf[:n], t_frame)
+        return _lib.aid_fix(*merged) if merged is not None else None
+
     def _initialize_gravity_and_bias(self):
         """msckf.py:235-258"""
         sw = np.zeros(3)
@@ -354,6 +398,9 @@ class MSCKF:
         zupt = self.zupt is not None and len(ws) > 0
         if zupt:   # the standstill update with the means of exactly the samples propagated (msckf_zupt.h)
             yield ("zupt", np.mean(np.array(ws).reshape(-1, 3), axis=0), np.mean(np.array(accs).reshape(-1, 3), axis=0))
+        fix = self._take_fix(feature_msg.timestamp) if self.aiding is not None else None
+        if fix is not None:   # the frame's aiding fix (msckf_aid.h)
+            yield ("aid", fix)
         yield from self._state_augmentation()
         if self.device_map:
             yield from self._map_add_and_remove_lost(feature_msg)
@@ -372,6 +419,9 @@ class MSCKF:
         if zupt:   # the device has drained: the update's record
             app, gam, self._zupt_count = yield ("zupt_results",)
             self.zupt_log.append((self._n_published, app, gam))
+        if fix is not None:
+            app, gam, rows, self._aid_count = yield ("aid_results",)
+            self.aid_log.append((self._n_published, rows, app, gam))
         res = self._publish_from(feature_msg.timestamp, _lib.unpack_imu(st[0]))
         if self.odometry:
             res = VioOdometry(*res, st[3], st[4])
@@ -749,6 +799,12 @@ class MSCKF:
         """Zero-velocity updates applied to this filter's slot (the device's
         counter as of the last frame's read)."""
         return self._zupt_count
+
+    @property
+    def aid_count(self):
+        """Aiding fixes applied to this filter's slot (the device's counter as
+        of the last frame's read)."""
+        return self._aid_count
 
     def clear_landmarks(self):
         """Empties the archive (an online reset does not: the world frame continues)."""

@@ -12,6 +12,9 @@ with ONE batched launch:
   zupt        -> msckf_zupt_batch        (zupt=ZuptConfig: the standstill update,
                  gated on the device; zupt_results -> msckf_zupt_results, behind
                  the frame's states read)
+  aid         -> msckf_aid_batch         (aiding=AidingConfig: the lanes that have
+                 a fix at this frame, each with its own; aid_results ->
+                 msckf_aid_results, behind the frame's states read)
   augment     -> msckf_augment_batch
   triangulate -> msckf_batch_load + msckf_batch_triangulate
   update      -> msckf_batch_load + msckf_batch_update (per row cap), results
@@ -47,7 +50,7 @@ from .vio import MultiStereoVIO, StereoVIO  # noqa: F401  (both ends in one clas
 from .trajectory import Trajectory
 
 # pipeline order: a lane waiting at an earlier stage is served first
-_ORDER = {"set_state": 0, "propagate": 1, "zupt": 1.5, "zupt_results": 5.1,
+_ORDER = {"set_state": 0, "propagate": 1, "zupt": 1.5, "zupt_results": 5.1, "aid": 1.7, "aid_results": 5.2,
           "augment": 2, "map_add_lost": 2.5, "map_add_lost_tracks": 2.5, "triangulate": 3,
           "map_triangulate": 3, "update": 4, "map_update": 4, "states": 5, "map_prune_select": 5.3,
           "map_keyframe_select": 5.3,
@@ -59,8 +62,11 @@ class MultiMSCKF:
 
     def __init__(self, n, config=None, dtype=np.float64, device=0, cam_capacity=None, lane_configs=None,
                  device_map=False, map_capacity=1024, device_keyframes=False, landmarks=None, landmark_capacity=4096,
-                 odometry=False, zupt=None):
-        """``zupt``: as ``MSCKF``'s, one ``ZuptConfig`` for all lanes (as the
+                 odometry=False, zupt=None, aiding=None):
+        """``aiding``: as ``MSCKF``'s, one ``AidingConfig`` for all lanes (they
+        share the parameters); ``aiding_callback(i, fix)`` feeds lane i, and one
+        msckf_aid_batch per frame step lists only the lanes that have a fix.
+        ``zupt``: as ``MSCKF``'s, one ``ZuptConfig`` for all lanes (as the
         device config is): one msckf_zupt_batch for the lanes of a frame step.
         ``landmarks`` / ``landmark_capacity`` / ``odometry``: as ``MSCKF``'s,
         for every lane ("device": one archive call for the lanes of a lost
@@ -108,7 +114,7 @@ class MultiMSCKF:
         self.landmark_mode = landmarks
         self.lanes = [MSCKF(cfgs[i], ctx=self.ctx, slot=i, device_map=self.device_map,
                             device_keyframes=self.device_keyframes, landmarks=landmarks,
-                            landmark_capacity=landmark_capacity, odometry=odometry, zupt=zupt)
+                            landmark_capacity=landmark_capacity, odometry=odometry, zupt=zupt, aiding=aiding)
                       for i in range(n)]
         self.launches = defaultdict(int)       # batched device calls per request kind
 
@@ -130,6 +136,9 @@ class MultiMSCKF:
     # ------------------------------------------------------------ callbacks --
     def imu_callback(self, i, imu_msg):
         self.lanes[i].imu_callback(imu_msg)
+
+    def aiding_callback(self, i, fix):
+        self.lanes[i].aiding_callback(fix)
 
     def feature_callbacks(self, msgs):
         """``msgs``: {lane index: feature_msg}.  Returns {lane index:
@@ -183,6 +192,12 @@ class MultiMSCKF:
         if kind == "zupt_results":
             app, gam, cnt = ctx.zupt_results(slots)
             return [(bool(app[w]), float(gam[w]), int(cnt[w])) for w in range(len(group))]
+        if kind == "aid":   # the lanes share the parameters (one AidingConfig), each has its own fix
+            ctx.aid_batch(slots, [r[1] for r in reqs], self.lanes[group[0]]._aid_prm)
+            return [None] * len(group)
+        if kind == "aid_results":
+            app, gam, rows, cnt = ctx.aid_results(slots)
+            return [(bool(app[w]), float(gam[w]), int(rows[w]), int(cnt[w])) for w in range(len(group))]
         if kind == "triangulate":
             self._load(slots, reqs, with_pw=False)
             ctx.batch_triangulate()

@@ -53,10 +53,13 @@ class MultiStereoVIO:
 
     def __init__(self, n, filter_config=None, frontend_config=None, lane_filter_configs=None,
                  lane_frontend_configs=None, dtype=np.float64, device=0, map_capacity=1024, device_keyframes=True,
-                 handoff="device", landmarks=None, landmark_capacity=4096, odometry=False, zupt=None):
+                 handoff="device", landmarks=None, landmark_capacity=4096, odometry=False, zupt=None,
+                 aiding=None):
         """``landmarks`` / ``landmark_capacity`` / ``odometry``: as
         ``MultiMSCKF``'s (msckf_odometry.h); ``zupt``: as ``MultiMSCKF``'s
-        (msckf_zupt.h; ``zupt_log(i)`` reads lane i's decisions).
+        (msckf_zupt.h; ``zupt_log(i)`` reads lane i's decisions); ``aiding``:
+        as ``MultiMSCKF``'s (msckf_aid.h; ``aiding_callback(i, fix)``,
+        ``aid_log(i)``).
         ``filter_config`` / ``lane_filter_configs``: as ``MultiMSCKF``'s
         ``config`` / ``lane_configs``; ``frontend_config`` /
         ``lane_frontend_configs``: as ``MultiImageProcessor``'s (device_pipeline
@@ -72,7 +75,8 @@ class MultiStereoVIO:
             self.filters = MultiMSCKF(n, config=filter_config, dtype=dtype, device=device,
                                       lane_configs=lane_filter_configs, device_map=True, map_capacity=map_capacity,
                                       device_keyframes=device_keyframes, landmarks=landmarks,
-                                      landmark_capacity=landmark_capacity, odometry=odometry, zupt=zupt)
+                                      landmark_capacity=landmark_capacity, odometry=odometry, zupt=zupt,
+                                      aiding=aiding)
         except BaseException:
             self.frontend.close()
             raise
@@ -113,10 +117,17 @@ class MultiStereoVIO:
         """Lane i's zero-velocity decisions, (frame, applied, gamma) per update enqueued."""
         return self.filters.lanes[i].zupt_log
 
+    def aid_log(self, i):
+        """Lane i's aiding decisions, (frame, rows, applied, gamma) per fix enqueued."""
+        return self.filters.lanes[i].aid_log
+
     # ------------------------------------------------------------ callbacks --
     def imu_callback(self, i, msg):
         self.frontend.imu_callback(i, msg)
         self.filters.imu_callback(i, msg)
+
+    def aiding_callback(self, i, fix):
+        self.filters.aiding_callback(i, fix)
 
     def stereo_callbacks(self, msgs):
         """``msgs``: {lane index: stereo_msg}.  Returns {lane index:
@@ -162,11 +173,11 @@ class StereoVIO:
 
     def __init__(self, filter_config=None, frontend_config=None, dtype=np.float64, device=0, map_capacity=1024,
                  device_keyframes=True, handoff="device", landmarks=None, landmark_capacity=4096, odometry=False,
-                 zupt=None):
+                 zupt=None, aiding=None):
         self.multi = MultiStereoVIO(1, filter_config=filter_config, frontend_config=frontend_config, dtype=dtype,
                                     device=device, map_capacity=map_capacity, device_keyframes=device_keyframes,
                                     handoff=handoff, landmarks=landmarks, landmark_capacity=landmark_capacity,
-                                    odometry=odometry, zupt=zupt)
+                                    odometry=odometry, zupt=zupt, aiding=aiding)
         self.handoff = self.multi.handoff
 
     def __enter__(self):
@@ -204,8 +215,19 @@ class StereoVIO:
     def zupt_count(self):
         return self.filter.zupt_count
 
+    @property
+    def aid_log(self):
+        return self.multi.aid_log(0)
+
+    @property
+    def aid_count(self):
+        return self.filter.aid_count
+
     def imu_callback(self, msg):
         self.multi.imu_callback(0, msg)
+
+    def aiding_callback(self, fix):
+        self.multi.aiding_callback(0, fix)
 
     def stereo_callback(self, stereo_msg):
         return self.multi.stereo_callbacks({0: stereo_msg})[0]
