@@ -211,6 +211,10 @@ struct msckf_ctx {
     int gc_cut[GATE_NLIST] = {}, sc_cut[SegClasses::NC] = {};   // where lane 1 begins in each list (subbatch_cut_lists)
     DBuf<unsigned char> obs_ws, obs_ht, obs_g, fqr, tau, ysq;
     bool gram = true;   // k_feature writes the Gram records (record-reading assembly)
+    // the lean feature path (FeatLean, fused assembly only): ill lists, and per lane
+    // two sets of counts with the set the lane's next lean step appends to
+    DBuf<int> ill_list, ill_cnt;
+    int ill_set[2] = {0, 0};
     // misc scratch
     DBuf<unsigned char> scratch;
     DBuf<int> iscratch;
@@ -661,6 +665,13 @@ int plan_commit(msckf_ctx* c, const int32_t* obs_off, const LoadPlan& pl) {
     // (allocated in either case: k_feature writes the records of ill-conditioned
     // features for the fused assembly too -- FQR_FLAG)
     HIPC(c->obs_g.ensure(((size_t)pl.nobs + 1) * OBG_STRIDE * sizeof(double)));
+    if (!c->gram) {   // the lean feature path's table and ill lists (launch_feature)
+        HIPC(c->ill_list.ensure((size_t)pl.nf + 1));
+        if (!c->ill_cnt.p) {
+            HIPC(c->ill_cnt.ensure(4 * FEAT_LEAN_NCLS));
+            HIPC(hipMemset(c->ill_cnt.p, 0, 4 * FEAT_LEAN_NCLS * sizeof(int)));
+        }
+    }
     c->h_feat_off = h_off;
     return 0;
 }
@@ -754,6 +765,22 @@ LaneRef lane_ref(msckf_ctx* c, int lane, int nlanes) {
     return {c->stream1, &c->timer1, b0, b1 - b0};
 }
 
+// Which feature kernel a lane's chain runs where the lean one applies (fused
+// assembly): MSCKF_FEATURE=full|lean (environment, read per call like
+// MSCKF_SUBBATCH); lean by default, full = k_feature for every feature.
+FeatLean feat_lean(msckf_ctx* c, int lane) {
+    FeatLean fl;
+    const char* e = getenv("MSCKF_FEATURE");
+    fl.on = !c->gram && c->ill_cnt.p && !(e && std::strcmp(e, "full") == 0);
+    fl.ill_list = c->ill_list.p;
+    if (fl.on) {
+        int* sets = c->ill_cnt.p + lane * 2 * FEAT_LEAN_NCLS;
+        fl.ill_cnt = sets + c->ill_set[lane] * FEAT_LEAN_NCLS;
+        fl.ill_cnt_next = sets + (c->ill_set[lane] ^ 1) * FEAT_LEAN_NCLS;
+    }
+    return fl;
+}
+
 // The update chain of one lane, enqueued on the lane's streams.  Per-filter
 // kernels get the lane's views of the state, the workspace and feat_off;
 // per-feature kernels keep the absolute views (they index by feat_filter[f]) and
@@ -804,7 +831,7 @@ int enqueue_chain(msckf_ctx* c, const LaneRef& L, int nlanes, int lane, int row_
         HIPC(hipEventRecord(c->ev_join, c->side));
     }
     kt.begin(s, "feature_jacobian");
-    launch_feature<T>(s, st_all, prm, fb_all, sc);
+    if (launch_feature<T>(s, st_all, prm, fb_all, sc, feat_lean(c, lane))) c->ill_set[lane] ^= 1;
     kt.end(s);
     kt.begin(s, "gate");
     if (const int u = launch_gate<T>(s, st_all, prm, fb_all, gc)) c->gate_unrouted = u;   // reported by unpack_results
@@ -1396,7 +1423,8 @@ int msckf_destroy(msckf_ctx_t* c) {
                     &c->aid.store, &c->aid.in})
         b->release();
     c->map.chi2.release();
-    for (auto* b : {&c->ncams, &c->ncams_snap, &c->ident, &c->info, &c->afail, &c->row_off, &c->iscratch})
+    for (auto* b : {&c->ncams, &c->ncams_snap, &c->ident, &c->info, &c->afail, &c->row_off, &c->iscratch, &c->ill_list,
+                    &c->ill_cnt})
         b->release();
     c->up.release();
     c->down.release();

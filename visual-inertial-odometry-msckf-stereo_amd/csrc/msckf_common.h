@@ -55,6 +55,15 @@ constexpr int OBG_G = 0, OBG_DS = 18, OBG_UB = 39, OBG_CAM = 45, OBG_STRIDE = 46
 // Jacobian blocks instead of reading obs_g.
 constexpr int FQR_X = 0, FQR_G = 6, FQR_FLAG = 9, FQR_STRIDE = 10;
 constexpr double FQR_RMAX = 1e3, FQR_KAPPA = 1e4;   // FQR_FLAG: Gram records written (k_feature)
+// Per-cam geometry record (fp64; cam_geometry): R0 = R_w_c0 | R1 = R01 R0 | t1 |
+// p | R(q_null) g.  k_info_fused keeps it per cam in LDS, the lean feature
+// kernel builds it per observation.
+constexpr int CG_R0 = 0, CG_R1 = 9, CG_T1 = 18, CG_P = 21, CG_UN = 24, CG_LEN = 27;
+// Lean feature path (k_feature_lean): the segment classes with one observation
+// per lane (S = 8, 16, 32, 64), an ill list and count each; waves per SIMD the
+// kernel is held to (__launch_bounds__).
+constexpr int FEAT_LEAN_NCLS = 4, FEAT_LEAN_WAVES = 4;
+struct IllLists { int beg[FEAT_LEAN_NCLS]; };   // first entry of each class's ill list
 
 template <typename T>
 struct Params {

@@ -1091,13 +1091,14 @@ __device__ __forceinline__ void store_pairs(T* dst, const S* src, int n) {
 // GRAM: also write the per-observation Gram records (obs_g) for the
 // record-reading assembly; the fused assembly (k_info_fused) rebuilds them
 // from the Jacobians and needs only the per-feature QR record (fqr).
+// (the body of wavefront `wid` of the list: k_feature runs it once per
+// wavefront, k_feature_ill in a loop over a device-side list)
 template <typename T, int S, int OPL, bool GRAM>
-__global__ void __launch_bounds__(256, OPL == 1 ? 3 : 1) k_feature(DevState<T> st, Params<T> prm, FeatBatch<T> fb,
-                                                 const int* __restrict__ flist, int cnt) {
+__device__ __forceinline__ void feature_seg(const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
+                                            const int* __restrict__ flist, const int cnt, const int wid) {
     using CT = double;
     constexpr int PER = 64 / S;   // features per wavefront, one S-lane segment each
     const int lane = threadIdx.x & 63, l = lane & (S - 1), b0 = lane & ~(S - 1);
-    const int wid = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (wid * PER >= cnt) return;
     const int li = wid * PER + lane / S;
     const int f = li < cnt ? flist[li] : 0;
@@ -1351,6 +1352,307 @@ __global__ void __launch_bounds__(256, OPL == 1 ? 3 : 1) k_feature(DevState<T> s
         for (int e = OBG_UB + 6; e < OBG_STRIDE; ++e) rec[e] = 0;
         rec[OBG_CAM] = (CT)fb.obs_cam[o0 + i];
         store_pairs(fb.obs_g + (size_t)(o0 + i) * OBG_STRIDE, rec, OBG_STRIDE);
+    }
+}
+
+template <typename T, int S, int OPL, bool GRAM>
+__global__ void __launch_bounds__(256, OPL == 1 ? 3 : 1) k_feature(DevState<T> st, Params<T> prm, FeatBatch<T> fb,
+                                                 const int* __restrict__ flist, int cnt) {
+    feature_seg<T, S, OPL, GRAM>(st, prm, fb, flist, cnt, blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+}
+
+// The second pass of the lean path: the features k_feature_lean found
+// ill-conditioned (its per-class device lists, counts in device memory), through
+// the full body with the Gram records on, so that their obs_ht, fqr and obs_g are
+// what k_feature alone would have written.  A small fixed grid, blockIdx.y = the
+// segment class; a class with an empty list leaves at once.  The counts come in
+// two sets used by alternate steps: this launch zeroes the set of the next step,
+// so no step needs a reset of its own on the stream.
+template <typename T>
+__global__ void __launch_bounds__(256, 3) k_feature_ill(DevState<T> st, Params<T> prm, FeatBatch<T> fb,
+                                                        const int* __restrict__ ill_list, IllLists il,
+                                                        const int* __restrict__ ill_cnt, int* __restrict__ ill_cnt_next) {
+    // the counts the next step appends to (the other set: nothing in flight touches it)
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < FEAT_LEAN_NCLS) ill_cnt_next[threadIdx.x] = 0;
+    const int k = blockIdx.y, cnt = ill_cnt[k];
+    if (cnt == 0) return;
+    const int* list = ill_list + il.beg[k];
+    const int w0 = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nw = gridDim.x * (blockDim.x >> 6);
+    auto run = [&](auto sc) {
+        constexpr int S = decltype(sc)::value;
+        for (int wid = w0; wid * (64 / S) < cnt; wid += nw) feature_seg<T, S, 1, true>(st, prm, fb, list, cnt, wid);
+    };
+    if (k == 0) run(std::integral_constant<int, 8>{});
+    else if (k == 1) run(std::integral_constant<int, 16>{});
+    else if (k == 2) run(std::integral_constant<int, 32>{});
+    else run(std::integral_constant<int, 64>{});
+}
+
+// ===========================================================================
+// Lean feature Jacobians for the fused assembly (no Gram records, no compact
+// factors, one observation per lane).  Downstream only obs_ht (Ht 3 x 6 and
+// [r~ | r_n] per observation, gating) and fqr (X = R^-1, g, flag per feature,
+// k_info_fused) are read, so nothing else is formed:
+//   * the cam geometry is the record of k_info_fused's prologue (cam_geometry),
+//     with the quaternions normalised by if_rsq;
+//   * the Jacobian stays factored, Hx_i = Jc B~ (Jc 4 x 3 = dz/dp_c0, B~ 3 x 6 =
+//     [ [p_c0]x | -R_w_c0 ] observability-projected, as in k_info_fused): the
+//     reflector that maps Jc's unit left null vector to +-e_4 is applied to Jc,
+//     and Ht_i = (reflected Jc)[0:3] B~ -- the 4 x 6 Hx is never formed;
+//   * the reflected H_f,i is -Ht_i[:, 3:6] over an exactly zero fourth row, so
+//     the Householder QR (dlarfg convention, pivot rows = observation 0 in the
+//     segment's first lane) runs on the 3M x 3 rotated rows.  Its R differs from
+//     k_feature's by row signs only; X's columns and g change sign with them and
+//     k_info_fused's G^T G and G^T g do not.
+//   * reciprocals and square roots are if_rcp / if_rsq.
+// Ill-conditioned features (k_feature's FQR_RMAX / FQR_KAPPA test on this R)
+// write nothing here: the segment's first lane appends the feature to the
+// class's ill list and k_feature_ill runs k_feature's body on it.
+// ===========================================================================
+
+// Reciprocal and reciprocal square root of the fused producer and the lean
+// feature kernel: the hardware approximations (v_rcp_f64 / v_rsq_f64) and one
+// Newton step each -- within a couple of ulps, against ~10 instructions of an
+// IEEE division / sqrt.  (The assembled information is invariant to these
+// rounding-level choices well inside the 1e-9 fp64 parity bound.)
+__device__ __forceinline__ double if_rcp(double x) {
+    const double r = __builtin_amdgcn_rcp(x);
+    return r * fma(-x, r, 2.0);
+}
+__device__ __forceinline__ double if_rsq(double x) {
+    const double r = __builtin_amdgcn_rsq(x);
+    return r * fma(-0.5 * x * r, r, 1.5);
+}
+
+// quat_to_rot with 1 / |q| by if_rsq
+__device__ __forceinline__ void quat_to_rot_rsq(const double* q, double* R) {
+    const double in = if_rsq(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double v[3] = {q[0] * in, q[1] * in, q[2] * in}, w = q[3] * in;
+    double S[9];
+    skew3(v, S);
+    const double a = 2 * w * w - 1, tw = 2 * w;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) R[3 * i + j] = (i == j ? a : 0.0) - tw * S[3 * i + j] + (2 * v[i]) * v[j];
+}
+// Per-cam geometry record (fp64): R0 = R_w_c0 | R1 = R01 R0 | t1 (cam-1 centre)
+// | p (cam-0 centre) | R(q_null) g.  One function for k_info_fused's prologue
+// (once per cam) and the lean feature kernel (per observation; FAST: the
+// quaternions normalised by if_rsq instead of an IEEE square root and four
+// divisions each).
+template <bool FAST = false, typename T>
+__device__ __forceinline__ void cam_geometry(const T* cq, const Params<T>& prm, const double* g, double* cg) {
+    double q0[4], qn[4], R0[9], R1[9], Rn[9], R01[9], t01[3], tmp[3];
+    for (int k = 0; k < 4; ++k) { q0[k] = (double)cq[C_Q + k]; qn[k] = (double)cq[C_QN + k]; }
+    for (int k = 0; k < 9; ++k) R01[k] = (double)prm.R01[k];
+    for (int k = 0; k < 3; ++k) t01[k] = (double)prm.t01[k];
+    if constexpr (FAST) quat_to_rot_rsq(q0, R0);
+    else quat_to_rot(q0, R0);
+    mat3_mul(R01, R0, R1);
+    mat3T_vec(R1, t01, tmp);
+    if constexpr (FAST) quat_to_rot_rsq(qn, Rn);
+    else quat_to_rot(qn, Rn);
+    for (int k = 0; k < 9; ++k) { cg[CG_R0 + k] = R0[k]; cg[CG_R1 + k] = R1[k]; }
+    for (int k = 0; k < 3; ++k) {
+        const double cp = (double)cq[C_P + k];
+        cg[CG_T1 + k] = cp - tmp[k];
+        cg[CG_P + k] = cp;
+    }
+    mat3_vec(Rn, g, cg + CG_UN);
+}
+
+template <typename T, int S>
+__global__ void __launch_bounds__(256, FEAT_LEAN_WAVES) k_feature_lean(DevState<T> st, Params<T> prm, FeatBatch<T> fb,
+                                                         const int* __restrict__ flist, int cnt,
+                                                         int* __restrict__ ill_list, int* __restrict__ ill_cnt) {
+    constexpr int PER = 64 / S;   // features per wavefront, one S-lane segment each
+    const int lane = threadIdx.x & 63, l = lane & (S - 1), sb = lane & ~(S - 1);
+    const int wid = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (wid * PER >= cnt) return;
+    const int li = wid * PER + lane / S;
+    const int f = li < cnt ? flist[li] : 0;
+    const bool fvalid = li < cnt && fb.valid[f];
+    const int b = fb.feat_filter[f];
+    const int o0 = fb.obs_off[f], M = fvalid ? fb.obs_off[f + 1] - o0 : 0;
+    const bool own = l < M;   // lane l of the segment owns observation l
+    double Hf[9], rq[3];      // the rotated rows 3l..3l+2 of H_f and of r (zero: no observation)
+    T Hts[18], rts[4];        // the observation's obs_ht record, held back until the feature is known well-conditioned
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Hf[e] = 0.0;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) rq[e] = 0.0;
+#pragma unroll
+    for (int e = 0; e < 18; ++e) Hts[e] = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) rts[e] = 0;
+    if (own) {
+        const int cam = fb.obs_cam[o0 + l];
+        const T* zp = fb.obs_z + (size_t)(o0 + l) * 4;
+        const double z0 = (double)zp[0], z1 = (double)zp[1], z2 = (double)zp[2], z3 = (double)zp[3];
+        double g[3], pw[3], R01[9];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            g[k] = (double)st.imu[(size_t)b * IMU_STRIDE + I_G + k];
+            pw[k] = (double)fb.p_w[3 * f + k];
+        }
+        double cg[CG_LEN];
+        cam_geometry<true>(st.cams + ((size_t)b * st.Nmax + cam) * CAM_STRIDE, prm, g, cg);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R01[k] = (double)prm.R01[k];
+        double d0[3], d1[3], pc0[3], pc1[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { d0[k] = pw[k] - cg[CG_P + k]; d1[k] = pw[k] - cg[CG_T1 + k]; }
+        mat3_vec(cg + CG_R0, d0, pc0);
+        mat3_vec(cg + CG_R1, d1, pc1);
+        // Jc (msckf.py:457-475): rows [a00 0 a02], [0 a00 a12], the b-rows times R01
+        const double i0 = if_rcp(pc0[2]), i1 = if_rcp(pc1[2]);
+        const double a00 = i0, a02 = -pc0[0] * i0 * i0, a12 = -pc0[1] * i0 * i0;
+        const double b00 = i1, b02 = -pc1[0] * i1 * i1, b12 = -pc1[1] * i1 * i1;
+        double J[12] = {a00, 0.0, a02, 0.0, a00, a12, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            J[6 + m] = b00 * R01[m] + b02 * R01[6 + m];
+            J[9 + m] = b00 * R01[3 + m] + b12 * R01[6 + m];
+        }
+        const double r[4] = {z0 - pc0[0] * i0, z1 - pc0[1] * i0, z2 - pc1[0] * i1, z3 - pc1[1] * i1};
+        // B~ = [ [p_c0]x | -R_w_c0 ] (I - u u^T / u^T u), u = [R(q_null) g ; (p_w - p) x g]  (msckf.py:484-490)
+        double u[6];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) u[k] = cg[CG_UN + k];
+        u[3] = d0[1] * g[2] - d0[2] * g[1];
+        u[4] = d0[2] * g[0] - d0[0] * g[2];
+        u[5] = d0[0] * g[1] - d0[1] * g[0];
+        double uu = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) uu += u[k] * u[k];
+        const double iuu = if_rcp(uu);
+        double B[3][6];
+        {
+            const double Sk[9] = {0.0, -pc0[2], pc0[1], pc0[2], 0.0, -pc0[0], -pc0[1], pc0[0], 0.0};
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                double row[6];
+#pragma unroll
+                for (int m = 0; m < 3; ++m) { row[m] = Sk[3 * a + m]; row[3 + m] = -cg[CG_R0 + 3 * a + m]; }
+                double bu = 0.0;
+#pragma unroll
+                for (int m = 0; m < 6; ++m) bu += row[m] * u[m];
+                bu *= iuu;
+#pragma unroll
+                for (int m = 0; m < 6; ++m) B[a][m] = row[m] - bu * u[m];
+            }
+        }
+        // Jc's unit left null vector n and the reflector I - beta v v^T, v = n + sign(n_3) e_4,
+        // that maps n to -sign(n_3) e_4: rows 0..2 of the reflected [Hx | r] are the range
+        // rows, row 3 carries only the residual r_n.
+        auto det3 = [](const double* x, const double* y, const double* w) {
+            return x[0] * (y[1] * w[2] - y[2] * w[1]) - x[1] * (y[0] * w[2] - y[2] * w[0]) +
+                   x[2] * (y[0] * w[1] - y[1] * w[0]);
+        };
+        double nv[4] = {det3(J + 3, J + 6, J + 9), -det3(J, J + 6, J + 9), det3(J, J + 3, J + 9),
+                        -det3(J, J + 3, J + 6)};
+        const double nn2 = nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2] + nv[3] * nv[3];
+        if (!(nn2 > 0)) {
+            nv[0] = nv[1] = nv[2] = 0.0;
+            nv[3] = 1.0;
+        } else {
+            const double inn = if_rsq(nn2);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) nv[k] *= inn;
+        }
+        const double beta = if_rcp(1.0 + fabs(nv[3]));
+        nv[3] += nv[3] >= 0 ? 1.0 : -1.0;
+        double Jt[9];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double w = nv[0] * J[c] + nv[1] * J[3 + c] + nv[2] * J[6 + c] + nv[3] * J[9 + c];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) Jt[3 * a + c] = J[3 * a + c] - beta * nv[a] * w;
+        }
+        const double wr = nv[0] * r[0] + nv[1] * r[1] + nv[2] * r[2] + nv[3] * r[3];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const double v = r[a] - beta * nv[a] * wr;
+            rts[a] = (T)v;
+            if (a < 3) rq[a] = v;
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int m = 0; m < 6; ++m) {
+                const double v = Jt[3 * a] * B[0][m] + Jt[3 * a + 1] * B[1][m] + Jt[3 * a + 2] * B[2][m];
+                Hts[6 * a + m] = (T)v;
+                if (m >= 3) Hf[3 * a + m - 3] = -v;
+            }
+    }
+    // ---- Householder QR of the rotated H_f (rows 3l..3l+2 with observation l) ----
+    double rd[3];   // R's diagonal (beta_j)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double alpha = __shfl(Hf[3 * j + j], sb, 64);   // pivot row j: observation 0, the segment's first lane
+        double xs = 0.0;
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+            if (3 * l + a > j) xs += Hf[3 * a + j] * Hf[3 * a + j];
+        xs = seg_sum<S>(xs);
+        double tj = 0.0, scale = 0.0, beta = alpha;
+        if (xs != 0.0) {
+            const double n2 = alpha * alpha + xs, irs = if_rsq(n2), nrm = n2 * irs;
+            beta = alpha >= 0 ? -nrm : nrm;
+            tj = (beta - alpha) * (alpha >= 0 ? -irs : irs);
+            scale = if_rcp(alpha - beta);
+        }
+        rd[j] = beta;
+        // v_j: v[j] = 1, v[row > j] = Hf[row][j] * scale, 0 above
+        double v[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int row = 3 * l + a;
+            v[a] = !own ? 0.0 : (row == j ? 1.0 : (row > j ? Hf[3 * a + j] * scale : 0.0));
+        }
+        // apply H_j to the remaining H_f columns and to r
+#pragma unroll
+        for (int c = j + 1; c <= 3; ++c) {
+            double w = 0.0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) w += v[a] * (c < 3 ? Hf[3 * a + c] : rq[a]);
+            w = seg_sum<S>(w) * tj;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                if (c < 3) Hf[3 * a + c] -= v[a] * w;
+                else rq[a] -= v[a] * w;
+            }
+        }
+    }
+    // k_feature's test, on this R (segment-uniform: every lane holds the same rd)
+    const double rmax = fmax(fabs(rd[0]), fmax(fabs(rd[1]), fabs(rd[2])));
+    const double rmin = fmin(fabs(rd[0]), fmin(fabs(rd[1]), fabs(rd[2])));
+    const bool ill = !(rmax <= FQR_RMAX) || !(rmax <= FQR_KAPPA * rmin);
+    if (M == 0) return;
+    if (ill) {   // to the full kernel (k_feature_ill); nothing of the feature is written here
+        if (l == 0) ill_list[atomicAdd(ill_cnt, 1)] = f;
+        return;
+    }
+    if (own) {
+        T* wsr = fb.obs_ht + (size_t)(o0 + l) * OBS_HTS;
+        store_pairs(wsr + OBS_HT, Hts, 18);
+        store_pairs(wsr + OBS_RT, rts, 4);
+    }
+    if (l == 0) {   // X = R^-1 and g = (Q^T r)[0:3]; a zero pivot drops its direction (k_feature)
+        const double r01 = Hf[1], r02 = Hf[2], r12 = Hf[5];
+        const double x00 = rd[0] != 0.0 ? if_rcp(rd[0]) : 0.0, x11 = rd[1] != 0.0 ? if_rcp(rd[1]) : 0.0;
+        const double x22 = rd[2] != 0.0 ? if_rcp(rd[2]) : 0.0;
+        double q[FQR_STRIDE];
+        q[FQR_X + 0] = x00;
+        q[FQR_X + 1] = -r01 * x00 * x11;
+        q[FQR_X + 2] = (r01 * r12 * x11 - r02) * x00 * x22;
+        q[FQR_X + 3] = x11;
+        q[FQR_X + 4] = -r12 * x11 * x22;
+        q[FQR_X + 5] = x22;
+        for (int t = 0; t < 3; ++t) q[FQR_G + t] = rq[t];
+        q[FQR_FLAG] = 0.0;
+        store_pairs(fb.fqr + (size_t)f * FQR_STRIDE, q, FQR_STRIDE);
     }
 }
 // ===========================================================================
@@ -2271,7 +2573,7 @@ __global__ void __launch_bounds__(64 * IB_NW) k_info_big(DevState<T> st, FeatBat
 // the producer's fp64 chain beside 20 accumulator tiles per owner wave.
 // ---------------------------------------------------------------------------
 constexpr int IF_KF = 8, IF_KR = 3 * IF_KF, IF_NKS = IF_KR / 4, IF_NP = 32 * IF_KF;
-constexpr int IF_ACC = 27, IF_CG = 27;   // doubles per accumulator slot / per cam geometry record
+constexpr int IF_ACC = 27, IF_CG = CG_LEN;   // doubles per accumulator slot / per cam geometry record
 constexpr int IF_NPW = IF_NP / 64;       // producer waves
 // Phase timing (probe builds, -DMSCKF_GATE_PROBE; tools/probes/info_phases.py):
 // s_memtime sums of one producer and one tile-owner wave per filter --
@@ -2293,20 +2595,6 @@ constexpr int IF_NW = 8;                 // waves per workgroup: 4 producers + 4
 
 __host__ __device__ constexpr size_t info_fused_lds(int maxnf) {
     return (size_t)(2 * IF_KR * IM_GS + IF_KF * 32 * IF_ACC + 32 * IF_CG) * sizeof(double) + (size_t)maxnf * 48 + 16;
-}
-
-// Reciprocal and reciprocal square root of the fused producer: the hardware
-// approximations (v_rcp_f64 / v_rsq_f64) and one Newton step each -- within a
-// couple of ulps, against ~10 instructions of an IEEE division / sqrt.  (The
-// assembled information is invariant to these rounding-level choices well
-// inside the 1e-9 fp64 parity bound.)
-__device__ __forceinline__ double if_rcp(double x) {
-    const double r = __builtin_amdgcn_rcp(x);
-    return r * fma(-x, r, 2.0);
-}
-__device__ __forceinline__ double if_rsq(double x) {
-    const double r = __builtin_amdgcn_rsq(x);
-    return r * fma(-0.5 * x * r, r, 1.5);
 }
 
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order
@@ -2448,23 +2736,7 @@ __global__ void __launch_bounds__(64 * NW) k_info_fused(DevState<T> st, Params<T
 #pragma unroll
     for (int k = 0; k < 3; ++k) g[k] = (double)st.imu[(size_t)b * IMU_STRIDE + I_G + k];
     if (tid < nc) {   // per-cam geometry (k_feature's per-observation poses, once per cam)
-        const T* cq = st.cams + ((size_t)b * st.Nmax + tid) * CAM_STRIDE;
-        double q0[4], qn[4], R0[9], R1[9], Rn[9], R01[9], t01[3], tmp[3];
-        for (int k = 0; k < 4; ++k) { q0[k] = (double)cq[C_Q + k]; qn[k] = (double)cq[C_QN + k]; }
-        for (int k = 0; k < 9; ++k) R01[k] = (double)prm.R01[k];
-        for (int k = 0; k < 3; ++k) t01[k] = (double)prm.t01[k];
-        quat_to_rot(q0, R0);
-        mat3_mul(R01, R0, R1);
-        mat3T_vec(R1, t01, tmp);
-        quat_to_rot(qn, Rn);
-        double* cg = camg + tid * IF_CG;
-        for (int k = 0; k < 9; ++k) { cg[k] = R0[k]; cg[9 + k] = R1[k]; }
-        for (int k = 0; k < 3; ++k) {
-            const double cp = (double)cq[C_P + k];
-            cg[18 + k] = cp - tmp[k];
-            cg[21 + k] = cp;
-        }
-        mat3_vec(Rn, g, cg + 24);
+        cam_geometry(st.cams + ((size_t)b * st.Nmax + tid) * CAM_STRIDE, prm, g, camg + tid * IF_CG);
     }
     __syncthreads();
     for (int f = tid >> 5; f < nf; f += NT / 32) {   // cam -> observation, 32 lanes per feature
@@ -2787,9 +3059,35 @@ void launch_triangulate(hipStream_t s, const DevState<T>& st, const Params<T>& p
     });
 }
 template <typename T>
-void launch_feature(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
-                    const SegClasses& sc) {
-    if (fb.nf == 0) return;
+bool launch_feature(hipStream_t s, const DevState<T>& st, const Params<T>& prm, const FeatBatch<T>& fb,
+                    const SegClasses& sc, const FeatLean& fl) {
+    if (fb.nf == 0) return false;
+    // Fused assembly, no compact factors: the lean kernel on the one-observation-
+    // per-lane classes, then the full kernel over what those found ill-conditioned
+    // (device lists, no host round trip).
+    if (fl.on && !fb.gram && !fb.compact) {
+        static_assert(SegClasses::NC == FEAT_LEAN_NCLS + 1 && SegClasses::S[FEAT_LEAN_NCLS - 1] == 64, "lean classes");
+        int k = 0, ill_blocks = 0;
+        for_seg_classes(sc, [&](auto lanes, auto per, dim3 blocks, const int* list, int cnt) {
+            constexpr int S = decltype(lanes)::value;
+            if constexpr (decltype(per)::value == 1) {
+                while (SegClasses::S[k] != S) ++k;
+                hipLaunchKernelGGL((k_feature_lean<T, S>), blocks, dim3(256), 0, s, st, prm, fb, list, cnt,
+                                   fl.ill_list + sc.beg[k], fl.ill_cnt + k);
+                ill_blocks = std::max(ill_blocks, std::min((int)blocks.x, 16));
+            } else {
+                hipLaunchKernelGGL((k_feature<T, S, decltype(per)::value, false>), blocks, dim3(256), 0, s, st, prm, fb,
+                                   list, cnt);
+            }
+        });
+        if (ill_blocks > 0) {
+            IllLists il;
+            for (int c = 0; c < FEAT_LEAN_NCLS; ++c) il.beg[c] = sc.beg[c];
+            hipLaunchKernelGGL(k_feature_ill<T>, dim3(ill_blocks, FEAT_LEAN_NCLS), dim3(256), 0, s, st, prm, fb,
+                               fl.ill_list, il, fl.ill_cnt, fl.ill_cnt_next);
+        }
+        return ill_blocks > 0;
+    }
     auto go = [&](auto gram) {
         for_seg_classes(sc, [&](auto lanes, auto per, dim3 blocks, const int* list, int cnt) {
             hipLaunchKernelGGL((k_feature<T, decltype(lanes)::value, decltype(per)::value, decltype(gram)::value>),
@@ -2798,6 +3096,7 @@ void launch_feature(hipStream_t s, const DevState<T>& st, const Params<T>& prm, 
     };
     if (fb.gram) go(std::true_type{});
     else go(std::false_type{});
+    return false;
 }
 
 // Features are launched by the lists of msckf_gate_routes.h (filled on the host
@@ -2912,7 +3211,8 @@ void launch_kalman(hipStream_t s, const DevState<T>& st, const Params<T>& prm, c
     template void launch_cov_diag<T>(hipStream_t, const DevState<T>&, int, const int*, int, int, T*);      \
     template void launch_triangulate<T>(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&,  \
                                         const SegClasses&);                                                 \
-    template void launch_feature<T>(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const SegClasses&); \
+    template bool launch_feature<T>(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const SegClasses&, \
+                                    const FeatLean&);                                                       \
     template int launch_gate<T>(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const GateClasses&); \
     template void launch_select<T>(hipStream_t, const DevState<T>&, const FeatBatch<T>&, const UpdWs<T>&, int); \
     template void launch_compress<T>(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const UpdWs<T>&, int, int); \

@@ -113,8 +113,22 @@ struct SegClasses {
 };
 template <typename T>
 void launch_triangulate(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const SegClasses&);
+// The lean feature path of one lane (fused assembly, no compact factors; the
+// classes with one observation per lane): the ill lists (laid out as the class
+// lists: a lane's part of a class has its own range) and the lane's two sets
+// of FEAT_LEAN_NCLS counts -- the step appends to ill_cnt, and its second pass
+// zeroes ill_cnt_next, which the lane's next lean step uses (both zero at
+// allocation).  on == false (MSCKF_FEATURE=full): k_feature for every feature.
+struct FeatLean {
+    bool on = false;
+    int* ill_list = nullptr;
+    int* ill_cnt = nullptr;
+    int* ill_cnt_next = nullptr;
+};
+// Returns whether the lean second pass ran (the caller then swaps the lane's count sets).
 template <typename T>
-void launch_feature(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const SegClasses&);
+bool launch_feature(hipStream_t, const DevState<T>&, const Params<T>&, const FeatBatch<T>&, const SegClasses&,
+                    const FeatLean&);
 // Feature index lists per gating route (device pointer + host offsets), one
 // level: list l = gate_list_of(M) of msckf_gate_routes.h holds the tracks of
 // exactly l + 1 16-row blocks (M <= 82), the last list M >= 83; gate_route
