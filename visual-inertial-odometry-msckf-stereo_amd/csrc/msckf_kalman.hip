@@ -21,9 +21,11 @@
 // Choleskys (k_gchol_*) and B / E as 64 x 64-tiled GEMMs (k_kal_b1/b2, k_kal_e).
 #include "msckf_common.h"
 #include "msckf_launch.h"
+#include "msckf_mchol_slots.h"
 #include "msckf_rchol.h"
 
 #include <stdlib.h>
+#include <type_traits>
 
 namespace msckf {
 
@@ -1111,6 +1113,8 @@ __global__ void __launch_bounds__(64 * NW) k_kal_e1(DevState<T> st, Params<T> pr
 // parallel scan of the failure flags).
 // ===========================================================================
 constexpr int MK_PS = 4;   // doubles per panel row (the step's four columns)
+// slots whose operand reads are in flight ahead of the MFMA (8 VGPRs each: what the accumulators leave)
+__host__ __device__ constexpr int mk_lookahead(int SL) { return SL > 20 ? 1 : 2; }
 
 __device__ __forceinline__ double mk_rcp(double x) {   // 1 / x: hardware reciprocal + one Newton step
     const double r = __builtin_amdgcn_rcp(x);
@@ -1119,11 +1123,179 @@ __device__ __forceinline__ double mk_rcp(double x) {   // 1 / x: hardware recipr
 
 __host__ __device__ constexpr int mk_lds_doubles(int NBR) { return 2 * 16 * NBR * MK_PS + 16; }
 
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order
+template <int N, class Fn>
+__device__ __forceinline__ void mk_static_for(Fn&& f) {
+    if constexpr (N > 0) {
+        mk_static_for<N - 1>(f);
+        f(std::integral_constant<int, N - 1>{});
+    }
+}
+
+// Wave WV's part of one factorisation of T (stage C1, mk_factor).  Which block a
+// slot holds is compile-time data (msckf_mchol_slots.h): one code path per wave
+// and block column KB, a runtime loop over the column's four pivot steps.  The
+// slots a step updates are a suffix of the wave's slots -- those of block
+// column KB itself (on the column's first three steps: one uniform test) and
+// those right of it (no test).  A slot's operand reads are in flight under the
+// MFMAs of the slots before it.  Returns false on a failed pivot (uniform over
+// the workgroup).
+template <typename T, int NW, int NBR, int WV>
+__device__ __forceinline__ bool mk_wave(const DevState<T>& st, const UpdWs<T>& ws, int b, double floor, double lo,
+                                        double* pan0) {
+    constexpr int SL = mk_nslots(NBR, NW), JN = mk_used_slots(NBR, NW, WV), MK_LA = mk_lookahead(SL);
+    const int tid = threadIdx.x, lane = tid & 63, lc = lane & 15, lr = lane >> 4;
+    const int C = 6 * st.ncams[b], Cp = round4(C);
+    const int nrows = C;   // rows beyond: identity padding up to 16 NBR
+    const int nsteps = Cp / 4;
+    const int ldt = ws.Cmax + 1;
+    const KT* Tm = ws.Tm + (size_t)b * ws.Cmax * ldt;
+    KT* LT = ws.G + (size_t)b * ws.Cmax * ldt;
+    // (branch-free: a padding entry reads element 0 and discards it, so that a slot's
+    // loads are one straight run)
+    auto load = [&](int i, int j) -> double {
+        const bool pad = i >= C || j >= C;
+        const int ri = ws.rev ? C - 1 - i : i, rj = ws.rev ? C - 1 - j : j;   // rev: J T J (k_kal_c1)
+        const double v = Tm[pad ? (size_t)0 : (ri >= rj ? (size_t)ri * ldt + rj : (size_t)rj * ldt + ri)];
+        return pad ? (i == j ? 1.0 : 0.0) : v;
+    };
+    // blocks of this wave: slot j holds block WV + NW j of the column-major lower order
+    using v4d_t = double __attribute__((ext_vector_type(4)));
+    v4d_t acc[SL];
+    mk_static_for<JN>([&](auto jc) {
+        constexpr int j = decltype(jc)::value, r = mk_brow(NBR, NW, WV, j), c = mk_bcol(NBR, NW, WV, j);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[j][q] = load(16 * r + lr + 4 * q, 16 * c + lc);
+        __builtin_amdgcn_sched_barrier(0);   // slot by slot: the addresses of all of them at once do not fit
+    });
+    const double oh[4] = {lr == 0 ? 1.0 : 0.0, lr == 1 ? 1.0 : 0.0, lr == 2 ? 1.0 : 0.0, lr == 3 ? 1.0 : 0.0};
+    int status = 0;   // 1: all nsteps done, 2: failed pivot (uniform)
+    mk_static_for<NBR>([&](auto kbc) {
+      constexpr int KB = decltype(kbc)::value;
+      // slots [J0, J1): block column KB, [J1, JN): the columns right of it
+      constexpr int J0 = mk_first_slot(NBR, NW, WV, KB), J1 = mk_first_slot(NBR, NW, WV, KB + 1);
+      if (status != 0) return;
+#pragma nounroll
+      for (int sc = 0; sc < 4; ++sc) {
+        if (4 * KB + sc >= nsteps) { status = 1; break; }
+        const int p0 = 16 * KB + 4 * sc;
+        double* pan = pan0 + (sc & 1) * 16 * NBR * MK_PS;
+        // 1. the owners of columns p0 .. p0 + 3 dump them (rows of block column KB)
+        if ((lc >> 2) == sc) {
+            double* d = pan + lr * MK_PS + (lc & 3);
+            mk_static_for<J1 - J0>([&](auto jc) {
+                constexpr int j = J0 + decltype(jc)::value, r = mk_brow(NBR, NW, WV, j);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) d[(16 * r + 4 * q) * MK_PS] = acc[j][q];
+            });
+        }
+        __syncthreads();
+        // 2. A_d = L D L^T (lower entries of the panel's rows p0 .. p0 + 3), floored pivots
+        const double* ad = pan + p0 * MK_PS;
+        const double a10 = ad[4], a20 = ad[8], a30 = ad[12];
+        const double a21 = ad[9], a31 = ad[13], a32 = ad[14];
+        const double d0 = pivot_floored(ad[0], floor, lo), e0 = mk_rcp(d0);
+        const double l10 = a10 * e0, l20 = a20 * e0, l30 = a30 * e0;
+        const double d1 = pivot_floored(ad[5] - l10 * a10, floor, lo), e1 = mk_rcp(d1);
+        const double m21 = a21 - l20 * a10, m31 = a31 - l30 * a10;
+        const double l21 = m21 * e1, l31 = m31 * e1;
+        const double d2 = pivot_floored(ad[10] - l20 * a20 - l21 * m21, floor, lo), e2 = mk_rcp(d2);
+        const double m32 = a32 - l30 * a20 - l31 * m21;
+        const double l32 = m32 * e2;
+        const double d3 = pivot_floored(ad[15] - l30 * a30 - l31 * m31 - l32 * m32, floor, lo), e3 = mk_rcp(d3);
+        // (every lane reads the same A_d: the first lane's verdict is the workgroup's)
+        if (__builtin_amdgcn_readfirstlane((int)(!(d0 > 0.0) || !(d1 > 0.0) || !(d2 > 0.0) || !(d3 > 0.0)))) {
+            status = 2;
+            break;
+        }
+        // 3. Cholesky columns p0 .. p0 + 3: y = x L_u^-T D^-1/2, one panel row per thread
+        {
+            const int r = p0 + tid;
+            if (r < nrows) {
+                const double* x = pan + r * MK_PS;
+                const double z0 = x[0], z1 = x[1] - l10 * z0, z2 = x[2] - l20 * z0 - l21 * z1;
+                const double z3 = x[3] - l30 * z0 - l31 * z1 - l32 * z2;
+                const int k = r - p0;   // rows of the diagonal block: zeros above the diagonal
+                // the diagonal entries take the (possibly floored) pivot itself: z_k
+                // of row p0 + k is the unfloored Schur value (a floored -1e-12 would
+                // otherwise give L_kk = -1e-12 / sqrt(s2) instead of sqrt(s2))
+                const double y0 = (k == 0 ? d0 : z0) * rchol_rsq(d0);
+                const double y1 = k >= 1 ? (k == 1 ? d1 : z1) * rchol_rsq(d1) : 0.0;
+                const double y2 = k >= 2 ? (k == 2 ? d2 : z2) * rchol_rsq(d2) : 0.0;
+                const double y3 = k >= 3 ? (k == 3 ? d3 : z3) * rchol_rsq(d3) : 0.0;
+                KT* dst = LT + (size_t)r * ldt + p0;
+                dst[0] = y0;
+                if (p0 + 1 < C) dst[1] = y1;
+                if (p0 + 2 < C) dst[2] = y2;
+                if (p0 + 3 < C) dst[3] = y3;
+            }
+        }
+        // 4. m = -A_d^-1 e_lr (h = L^-1 e, u = D^-1 h, m = L^-T u), then the
+        //    rank-4 update of every block right of the pivots
+        const double h0 = oh[0];
+        const double h1 = fma(-l10, h0, oh[1]);
+        const double h2 = fma(-l21, h1, fma(-l20, h0, oh[2]));
+        const double h3 = fma(-l32, h2, fma(-l31, h1, fma(-l30, h0, oh[3])));
+        const double u0 = h0 * e0, u1 = h1 * e1, u2 = h2 * e2, u3 = h3 * e3;
+        const double w2 = fma(-l32, u3, u2);
+        const double w1 = fma(-l31, u3, fma(-l21, w2, u1));
+        const double w0 = fma(-l30, u3, fma(-l20, w2, fma(-l10, w1, u0)));
+        //    of the slots [JA, JB): a slot's operand reads (its block row's panel row for
+        //    X m, its block column's B value where the column changes) are issued MK_LA
+        //    slots ahead of its MFMA
+        const double* pa = pan + lc * MK_PS;        // + 16 r MK_PS: row lc of block row r
+        const double* pb = pan + lc * MK_PS + lr;   // + 16 c MK_PS: B operand of block column c
+        double x[SL][4], bv[NBR];
+        auto update = [&](auto jac, auto jbc) {
+            constexpr int JA = decltype(jac)::value, JB = decltype(jbc)::value;
+            auto ldo = [&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                if constexpr (j < JB) {
+                    constexpr int r = mk_brow(NBR, NW, WV, j), c = mk_bcol(NBR, NW, WV, j);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) x[j][i] = pa[16 * r * MK_PS + i];
+                    if constexpr (j == JA || mk_bcol(NBR, NW, WV, j - 1) != c) bv[c] = pb[16 * c * MK_PS];
+                }
+            };
+            mk_static_for<MK_LA>([&](auto lc_) { ldo(std::integral_constant<int, JA + decltype(lc_)::value>{}); });
+            mk_static_for<JB - JA>([&](auto jc) {
+                constexpr int j = JA + decltype(jc)::value, c = mk_bcol(NBR, NW, WV, j);
+                ldo(std::integral_constant<int, j + MK_LA>{});
+                // -(x0 w0 + x1 w1 + x2 w2 + x3 u3), contracted as the single-path kernel's was (the
+                // product that stays a product is x1 w1): left to the compiler, a quarter of the
+                // unrolled instances start from x0 w0 and the factor moves in its last bit
+                const double av = -fma(x[j][3], u3, fma(x[j][2], w2, fma(x[j][0], w0, x[j][1] * w1)));
+                acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv[c], acc[j], 0, 0, 0);
+            });
+        };
+        __builtin_amdgcn_sched_barrier(0);   // (operand reads hoisted over the factorisation spill)
+        //    block column KB's own slots, while one of its pivot steps is still to come
+        if constexpr (J1 > J0)
+            if (sc < 3) update(std::integral_constant<int, J0>{}, std::integral_constant<int, J1>{});
+        //    the columns right of it
+        update(std::integral_constant<int, J1>{}, std::integral_constant<int, JN>{});
+      }
+    });
+    return status != 2;
+}
+
 // One factorisation of filter b (stage A: P_cc + shift I).  Returns false on a
 // failed pivot; all outputs written on success.
 template <typename T, int NW, int NBR, int STAGE>
 __device__ __forceinline__ bool mk_factor(const DevState<T>& st, const UpdWs<T>& ws, int b, double shift,
                                           double floor, double lo, double* pan0) {
+    if constexpr (STAGE == 1) {   // one code path per wave (stage A's 23 accumulators leave it no room: DESIGN 5.7)
+        static_assert(NW == 4, "one mk_wave code path per wave");
+        bool ok = false;
+        switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) {
+        case 0: ok = mk_wave<T, NW, NBR, 0>(st, ws, b, floor, lo, pan0); break;
+        case 1: ok = mk_wave<T, NW, NBR, 1>(st, ws, b, floor, lo, pan0); break;
+        case 2: ok = mk_wave<T, NW, NBR, 2>(st, ws, b, floor, lo, pan0); break;
+        default: ok = mk_wave<T, NW, NBR, 3>(st, ws, b, floor, lo, pan0); break;
+        }
+        __syncthreads();   // every wave's panel reads are done before the next factorisation's dumps
+        return ok;
+    }
     constexpr int NBLK = NBR * (NBR + 1) / 2, SL = (NBLK + NW - 1) / NW;
     const int tid = threadIdx.x, lane = tid & 63, lc = lane & 15, lr = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
