@@ -25,7 +25,11 @@ the device applied; --static-s S is the streams' time at rest before they move
 (msckf_aid.h; kernels aid_gain and aid_apply): position + velocity messages
 from the streams' ground truth at --aid-rate Hz (default 5), 12 ms before a
 frame, with 2 cm / 2 cm/s noise, rotated into each filter's world frame, and
-reports how many fixes the device applied.
+reports how many fixes the device applied.  --anchors turns the anchor fixes on
+(msckf_anchor.h; kernels anchor_gain and anchor_apply): --anchor-n (default 8)
+points per stream surveyed to 5 mm, their stereo observations from the ground
+truth with the streams' pixel noise at --anchor-rate Hz (default 5), at the
+frame times, and reports how many updates the device applied.
 
 On N GPUs every rank replays its share of the sequences (replicas.shard) on
 its own device; the replicas' host TCP hub (msckf_amd.replicas, no RCCL:
@@ -58,11 +62,7 @@ def aiding_fixes(seq, static_s, rate, seed, lead=0.012, sigma=0.02, t_start=100.
     R_truth_iw^T at that frame, where both origins are 0 (the stream rests): the
     filter's initial attitude is the one its gravity initialisation will
     compute from the first 200 IMU samples."""
-    from msckf_amd.geometry import from_two_vectors, to_rotation
-    g_imu = np.mean([m.linear_acceleration for m in seq.imu[:200]], axis=0)
-    q0 = from_two_vectors(-np.array([0.0, 0.0, -np.linalg.norm(g_imu)]), g_imu)
-    first = int(np.searchsorted(seq.gt_t, seq.imu[199].vio_timestamp__))
-    A = to_rotation(q0).T @ seq.gt_R[first].T
+    A, first = _alignment(seq)
     rng = np.random.default_rng(seed)
     t0, h, out = t_start + static_s, 1e-4, []
     for k in range(first, len(seq.gt_t), max(1, int(round(20.0 / rate)))):
@@ -72,6 +72,47 @@ def aiding_fixes(seq, static_s, rate, seed, lead=0.012, sigma=0.02, t_start=100.
         out.append(msckf_amd.AidingFix(t, position=A @ p + sigma * rng.standard_normal(3),
                                        velocity=A @ v + sigma * rng.standard_normal(3),
                                        position_var=sigma ** 2, velocity_var=sigma ** 2))
+    return out
+
+
+def _alignment(seq):
+    """(A, first): A rotates the synthetic world into the filter's (aiding_fixes), first the first published frame."""
+    from msckf_amd.geometry import from_two_vectors, to_rotation
+    g_imu = np.mean([m.linear_acceleration for m in seq.imu[:200]], axis=0)
+    q0 = from_two_vectors(-np.array([0.0, 0.0, -np.linalg.norm(g_imu)]), g_imu)
+    first = int(np.searchsorted(seq.gt_t, seq.imu[199].vio_timestamp__))
+    return to_rotation(q0).T @ seq.gt_R[first].T, first
+
+
+def anchor_fixes(seq, rate, n, seed, sigma=0.005, pix_sigma=0.5 / 458.654):
+    """Anchor messages for ``seq`` from its ground truth: ``n`` points uniform
+    in the box [4, -2.5, -1.5] .. [7, 2.5, 1.5] of the synthetic world, given in
+    the filter's world frame (aligned as in ``aiding_fixes``) with ``sigma``
+    survey noise and declared so; a message AT every (20 / rate)-th frame from
+    the first one the filter publishes with the points that pass
+    make_sequence's visibility test, their true projections plus ``pix_sigma``
+    noise."""
+    cfg = msckf_amd.FilterConfig()
+    R_ic, t_ic = cfg.T_imu_cam0[:3, :3], cfg.T_imu_cam0[:3, 3]
+    Rcc, tcc = cfg.T_cn_cnm1[:3, :3], cfg.T_cn_cnm1[:3, 3]
+    A, first = _alignment(seq)
+    rng = np.random.default_rng(seed)
+    lo, hi = np.array([4.0, -2.5, -1.5]), np.array([7.0, 2.5, 1.5])
+    L = lo + (hi - lo) * rng.random((n, 3))
+    declared = L @ A.T + sigma * rng.standard_normal((n, 3))
+    out = []
+    for k in range(first, len(seq.gt_t), max(1, int(round(20.0 / rate)))):
+        R0 = R_ic @ seq.gt_R[k].T
+        t_c0 = seq.gt_p[k] + seq.gt_R[k] @ (-R_ic.T @ t_ic)
+        R1 = Rcc @ R0
+        pc0, pc1 = (L - t_c0) @ R0.T, (L - (t_c0 - R1.T @ tcc)) @ R1.T
+        with np.errstate(divide="ignore", invalid="ignore"):
+            uv = np.stack([pc0[:, 0] / pc0[:, 2], pc0[:, 1] / pc0[:, 2], pc1[:, 0] / pc1[:, 2], pc1[:, 1] / pc1[:, 2]], 1)
+        vis = (pc0[:, 2] > 0.5) & (pc1[:, 2] > 0.5) & (np.abs(uv[:, [0, 2]]) < 0.75).all(1) & (np.abs(uv[:, [1, 3]]) < 0.5).all(1)
+        idx = np.flatnonzero(vis)
+        if len(idx):
+            out.append(msckf_amd.AnchorFix(seq.gt_t[k], declared[idx], uv[idx] + pix_sigma * rng.standard_normal((len(idx), 4)),
+                                           sigma ** 2))
     return out
 
 
@@ -94,6 +135,10 @@ def main():
     ap.add_argument("--aiding", action="store_true",
                     help="aiding fixes (msckf_aid.h): synthetic position + velocity messages from the ground truth")
     ap.add_argument("--aid-rate", type=float, default=5.0, help="fixes per second and stream with --aiding")
+    ap.add_argument("--anchors", action="store_true",
+                    help="anchor fixes (msckf_anchor.h): synthetic surveyed points observed from the ground truth")
+    ap.add_argument("--anchor-n", type=int, default=8, help="anchors per stream with --anchors")
+    ap.add_argument("--anchor-rate", type=float, default=5.0, help="anchor messages per second and stream with --anchors")
     ap.add_argument("--kernel-times", action="store_true",
                     help="a second, untimed batched replay with every stage timed (msckf_kernel_times)")
     a = ap.parse_args()
@@ -106,6 +151,8 @@ def main():
         opt["zupt"] = msckf_amd.ZuptConfig()
     if a.aiding:
         opt["aiding"] = msckf_amd.AidingConfig()
+    if a.anchors:
+        opt["anchors"] = msckf_amd.AnchorConfig()
     seq_kw = {} if a.static_s is None else dict(static_s=a.static_s)
     dtype = np.float32 if a.fp32 else np.float64
     grp = replicas.init()
@@ -114,6 +161,7 @@ def main():
     streams = [FeatureStream.from_synthetic(q) for q in seqs]
     fixes = [aiding_fixes(q, 1.2 if a.static_s is None else a.static_s, a.aid_rate, 1000 + i)
              for q, i in zip(seqs, mine)] if a.aiding else None
+    anchor_msgs = [anchor_fixes(q, a.anchor_rate, a.anchor_n, 2000 + i) for q, i in zip(seqs, mine)] if a.anchors else None
     n_frames = sum(s.n_frames for s in streams)
     multi = MultiMSCKF(len(streams), dtype=dtype, device=grp.local_rank,
                        device_map=a.device_map, device_keyframes=a.device_keyframes, **opt) if streams else None
@@ -124,6 +172,9 @@ def main():
         for i, fx in enumerate(fixes):
             for f in fx:
                 multi.aiding_callback(i, f)
+    for i, fx in enumerate(anchor_msgs or []):
+        for f in fx:
+            multi.anchor_callback(i, f)
     grp.barrier()
     prof = None
     if a.profile:
@@ -142,6 +193,7 @@ def main():
     archived = [int(multi.landmarks(i).next_seq) for i in range(len(streams))] if multi and a.landmarks else None
     zupt_applied = [[int(ln.zupt_count), len(ln.zupt_log)] for ln in multi.lanes] if multi and a.zupt else None
     aid_applied = [[int(ln.aid_count), len(ln.aid_log)] for ln in multi.lanes] if multi and a.aiding else None
+    anchor_applied = [[int(ln.anchor_count), len(ln.anchor_log)] for ln in multi.lanes] if multi and a.anchors else None
     if multi:
         multi.close()
     kernel_ms = None
@@ -152,6 +204,9 @@ def main():
         for i, fx in enumerate(fixes or []):
             for f in fx:
                 prof_run.aiding_callback(i, f)
+        for i, fx in enumerate(anchor_msgs or []):
+            for f in fx:
+                prof_run.anchor_callback(i, f)
         prof_run.run_streams(streams, messages=[s.messages(arrays=a.device_map) for s in streams])
         kernel_ms = {k: [round(ms, 3), n] for k, (ms, n) in prof_run.ctx.kernel_times().items()}
         prof_run.close()
@@ -169,6 +224,8 @@ def main():
         out["zupt_applied_of_rank0"] = zupt_applied
     if aid_applied is not None:   # per lane: fixes applied, fixes enqueued
         out["aid_applied_of_rank0"] = aid_applied
+    if anchor_applied is not None:   # per lane: updates applied, messages enqueued
+        out["anchor_applied_of_rank0"] = anchor_applied
     if archived is not None:
         out["landmarks_archived_rank0"] = archived
     if kernel_ms is not None:
@@ -183,6 +240,8 @@ def main():
             flt = msckf_amd.MSCKF(dtype=dtype, device_map=a.device_map, device_keyframes=a.device_keyframes, **opt)
             for f in (fixes[i] if fixes else []):
                 flt.aiding_callback(f)
+            for f in (anchor_msgs[i] if anchor_msgs else []):
+                flt.anchor_callback(f)
             replay(flt, s, events=ev)
             flt.close()
         el_s = time.perf_counter() - t0

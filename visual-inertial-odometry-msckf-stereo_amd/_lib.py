@@ -251,6 +251,40 @@ AID_SIGS = {
 }
 AID_EXPORTED = tuple(AID_SIGS)
 
+# the anchor fixes (include/msckf_anchor.h), same library and context
+ANCHOR_MAX = 64
+ANCHOR_USED, ANCHOR_GATED, ANCHOR_DEPTH, ANCHOR_NOT_PD = 0, 1, 2, 3
+
+
+class MsckfAnchorT(C.Structure):
+    _fields_ = [("p_w", C.c_double * 3), ("cov", C.c_double * 6), ("z", C.c_double * 4)]
+
+
+class MsckfAnchorParamsT(C.Structure):
+    _fields_ = [("obs_var", C.c_double), ("chi2", C.c_double), ("min_depth", C.c_double),
+                ("min_anchors", C.c_int32)]
+
+
+ANCHOR_DTYPE = np.dtype([("p_w", "<f8", 3), ("cov", "<f8", 6), ("z", "<f8", 4)])   # msckf_anchor_t, packed doubles
+
+
+def pack_anchors(p, cov, z):
+    """msckf_anchor_t records of p (K, 3), cov (K, 3, 3) and z (K, 4): cov's six upper entries xx xy xz yy yz zz."""
+    p, cov, z = np.asarray(p, float).reshape(-1, 3), np.asarray(cov, float).reshape(-1, 3, 3), \
+        np.asarray(z, float).reshape(-1, 4)
+    a = np.zeros(len(p), ANCHOR_DTYPE)
+    a["p_w"], a["z"] = p, z
+    a["cov"] = cov[:, [0, 0, 0, 1, 1, 2], [0, 1, 2, 1, 2, 2]]
+    return a
+
+
+ANCHOR_SIGS = {
+    "msckf_anchor_batch": (C.c_int, [_P, C.c_int, _I, _I, C.POINTER(MsckfAnchorT), C.POINTER(MsckfAnchorParamsT)]),
+    "msckf_anchor_results": (C.c_int, [_P, C.c_int, _I, _I, _I, _I, _I64]),
+    "msckf_anchor_status": (C.c_int, [_P, C.c_int, C.c_int, _U8, _D, _I]),
+}
+ANCHOR_EXPORTED = tuple(ANCHOR_SIGS)
+
 # multi-GPU replica transport, RCCL (include/msckf_replicas.h), same library
 REPLICA_SIGS = {
     "msckf_rccl_unique_id": (C.c_int, [_U8]),
@@ -281,7 +315,7 @@ def load_library(path: str = LIB_PATH):
                                   list(FRONTEND_LANES_SIGS.items()) + list(FRONTEND_TRACKS_SIGS.items()) +
                                   list(MAP_SIGS.items()) + list(KEYFRAME_SIGS.items()) + list(HANDOFF_SIGS.items()) +
                                   list(EQUALIZE_SIGS.items()) + list(ODOMETRY_SIGS.items()) +
-                                  list(ZUPT_SIGS.items()) + list(AID_SIGS.items()) +
+                                  list(ZUPT_SIGS.items()) + list(AID_SIGS.items()) + list(ANCHOR_SIGS.items()) +
                                   list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res
@@ -824,6 +858,49 @@ class Context:
                                                    _ptr(gam, C.c_double), _ptr(rows, C.c_int32),
                                                    _ptr(cnt, C.c_int64)))
         return app.astype(bool), gam, rows, cnt
+
+    # ---- the anchor fixes (msckf_anchor.h) ----
+    def anchor_batch(self, filters, anchors, prm):
+        """msckf_anchor_batch: the gated update of the listed filters, each with
+        its own anchors -- ``anchors[k]`` is ``(p (K, 3), cov (K, 3, 3), z (K,
+        4))`` in the filter's world frame or a ``pack_anchors`` array -- and the
+        parameters ``prm`` (a ``MsckfAnchorParamsT``).  Asynchronous, nothing
+        comes back (``anchor_results``, ``anchor_status``)."""
+        filters = _i32(filters)
+        n = len(filters)
+        anchors = [a if isinstance(a, np.ndarray) and a.dtype == ANCHOR_DTYPE else pack_anchors(*a) for a in anchors]
+        if len(anchors) != n:
+            raise ValueError("anchor_batch: %d filters but %d anchor lists" % (n, len(anchors)))
+        off = np.zeros(n + 1, np.int32)
+        off[1:] = np.cumsum([len(a) for a in anchors])
+        arr = np.ascontiguousarray(np.concatenate(anchors)) if n else np.zeros(0, ANCHOR_DTYPE)
+        if len(arr) == 0:
+            arr = np.zeros(1, ANCHOR_DTYPE)
+        with self.lock:
+            self._check(self.lib.msckf_anchor_batch(self.h, n, _ptr(filters, C.c_int32), _ptr(off, C.c_int32),
+                                                    arr.ctypes.data_as(C.POINTER(MsckfAnchorT)), C.byref(prm)))
+
+    def anchor_results(self, filters):
+        """msckf_anchor_results (synchronises): (applied bool [n], used int32
+        [n], rows int32 [n], count int64 [n] -- updates ever applied) of the
+        listed filters."""
+        filters = _i32(filters)
+        n = len(filters)
+        app, used, rows, cnt = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64)
+        with self.lock:
+            self._check(self.lib.msckf_anchor_results(self.h, n, _ptr(filters, C.c_int32), _ptr(app, C.c_int32),
+                                                      _ptr(used, C.c_int32), _ptr(rows, C.c_int32),
+                                                      _ptr(cnt, C.c_int64)))
+        return app.astype(bool), used, rows, cnt
+
+    def anchor_status(self, filter):
+        """msckf_anchor_status (synchronises): (status uint8 [K], gamma [K]) of
+        the anchors of the filter's last call."""
+        status, gamma, n = np.zeros(ANCHOR_MAX, np.uint8), np.zeros(ANCHOR_MAX), np.zeros(1, np.int32)
+        with self.lock:
+            self._check(self.lib.msckf_anchor_status(self.h, int(filter), ANCHOR_MAX, _ptr(status, C.c_uint8),
+                                                     _ptr(gamma, C.c_double), _ptr(n, C.c_int32)))
+        return status[:n[0]].copy(), gamma[:n[0]].copy()
 
     def device_info(self):
         """(HIP device index, PCI bus id) this context runs on."""

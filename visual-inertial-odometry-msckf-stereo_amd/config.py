@@ -264,6 +264,94 @@ class AidingConfig:
         return (z, var, float(dt), mask) if mask else None
 
 
+ANCHOR_MAX = 64   # MSCKF_ANCHOR_MAX: anchors per filter and call (include/msckf_anchor.h)
+
+
+@dataclass
+class AnchorFix:
+    """One anchor message: K points with known positions ``p`` (K, 3) in the
+    external frame of ``AnchorConfig.world_from_ext``, their stereo observations
+    ``z`` (K, 4) = (u0, v0, u1, v1) in the feature message's normalised
+    coordinates, taken at ``timestamp``, and the positions' covariance ``cov``:
+    a scalar variance, (K,) variances or (K, 3, 3)."""
+    timestamp: float
+    p: "np.ndarray"
+    z: "np.ndarray"
+    cov: "float | np.ndarray" = 1e-4
+
+    def arrays(self):
+        """(p (K, 3), z (K, 4), cov (K, 3, 3)), shapes checked."""
+        p = np.asarray(self.p, float).reshape(-1, 3)
+        z = np.asarray(self.z, float).reshape(-1, 4)
+        K = len(p)
+        if len(z) != K:
+            raise ValueError("AnchorFix: %d points but %d observations" % (K, len(z)))
+        c = np.asarray(self.cov, float)
+        if c.ndim == 0:
+            cov = np.broadcast_to(float(c) * np.eye(3), (K, 3, 3))
+        elif c.shape == (K,):
+            cov = c[:, None, None] * np.eye(3)
+        elif c.shape == (K, 3, 3):
+            cov = c
+        else:
+            raise ValueError("AnchorFix.cov must be a scalar, (K,) or (K, 3, 3), not %r" % (c.shape,))
+        return p, z, cov
+
+
+@dataclass
+class AnchorConfig:
+    """Parameters of the anchor fixes (include/msckf_anchor.h): the variance of a
+    normalised coordinate (``obs_var``; None: the filter's
+    ``observation_noise``), the per-anchor gate on gamma (``chi2``; None: the
+    upper 0.95 quantile at four rows, ``CHI2_95[3]``), the least depth in both
+    cameras, the least number of used anchors for an update, how far a message's
+    timestamp may lie from its frame's, and ``world_from_ext`` = (R, t):
+    external points become R x + t and their covariances R S R^T in the filter's
+    world frame.  No reference counterpart."""
+    obs_var: "float | None" = None
+    chi2: "float | None" = None
+    min_depth: float = 0.1
+    min_anchors: int = 1
+    time_tol: float = 1e-6
+    world_from_ext: tuple = field(default_factory=lambda: (np.eye(3), np.zeros(3)))
+
+    def gate(self):
+        return CHI2_95[3] if self.chi2 is None else float(self.chi2)
+
+    def check(self):
+        if self.obs_var is not None and not (self.obs_var > 0.0 and np.isfinite(self.obs_var)):
+            raise ValueError("AnchorConfig.obs_var = %r must be > 0" % (self.obs_var,))
+        if np.isnan(self.gate()):
+            raise ValueError("AnchorConfig.chi2 is NaN")
+        if not (self.min_depth > 0.0 and np.isfinite(self.min_depth)):
+            raise ValueError("AnchorConfig.min_depth = %r must be > 0" % (self.min_depth,))
+        if int(self.min_anchors) != self.min_anchors or self.min_anchors < 1:
+            raise ValueError("AnchorConfig.min_anchors = %r must be an integer >= 1" % (self.min_anchors,))
+        if not (self.time_tol >= 0.0):
+            raise ValueError("AnchorConfig.time_tol = %r must be >= 0" % (self.time_tol,))
+        R, t = self.world_from_ext
+        _orthonormal(R, "AnchorConfig.world_from_ext's rotation")
+        if np.asarray(t, float).shape != (3,) or not np.isfinite(np.asarray(t, float)).all():
+            raise ValueError("AnchorConfig.world_from_ext's translation must be three finite numbers")
+
+    def params(self, observation_noise=None):
+        """The C-ABI's msckf_anchor_params_t; ``observation_noise`` stands in for
+        an ``obs_var`` of None."""
+        from ._lib import MsckfAnchorParamsT
+        self.check()
+        var = self.obs_var if self.obs_var is not None else observation_noise
+        if var is None:
+            raise ValueError("AnchorConfig.obs_var is None and no observation_noise was given")
+        return MsckfAnchorParamsT(float(var), self.gate(), float(self.min_depth), int(self.min_anchors))
+
+    def in_world(self, fix):
+        """(p (K, 3), cov (K, 3, 3), z (K, 4)) of an ``AnchorFix`` in the filter's
+        world frame."""
+        R, t = np.asarray(self.world_from_ext[0], float), np.asarray(self.world_from_ext[1], float)
+        p, z, cov = fix.arrays()
+        return p @ R.T + t, R @ cov @ R.T, z
+
+
 @dataclass
 class FilterConfig:
     """Filter fields of the reference ConfigEuRoC (config.py:17-124)."""

@@ -26,6 +26,8 @@ the map through an accepted update, and the published pose's covariance.
 between propagation and augmentation, gated on the device.  ``aiding`` adds the
 aiding fixes of include/msckf_aid.h: external position, velocity, body-frame
 velocity and heading messages (``aiding_callback``), applied at the same point.
+``anchors`` adds the anchor fixes of include/msckf_anchor.h: stereo observations
+of points with known world positions (``anchor_callback``), applied behind them.
 
 Every device interaction of a frame is expressed as a request yielded by a
 step generator (``_frame_steps``); ``feature_callback`` serves the requests
@@ -47,7 +49,7 @@ from collections import OrderedDict, namedtuple
 import numpy as np
 
 from . import _lib
-from .config import CHI2_05, AidingConfig, FilterConfig, ZuptConfig, chi2_threshold
+from .config import ANCHOR_MAX, CHI2_05, AidingConfig, AnchorConfig, FilterConfig, ZuptConfig, chi2_threshold
 from .geometry import Isometry3d, from_two_vectors, to_quaternion, to_rotation
 from .landmarks import HostRing, Landmarks, check_mode, with_live
 
@@ -120,7 +122,7 @@ class MSCKF:
 
     def __init__(self, config=None, dtype=np.float64, device=0, cam_capacity=None, ctx=None, slot=0,
                  device_map=False, map_capacity=1024, device_keyframes=False, landmarks=None,
-                 landmark_capacity=4096, odometry=False, zupt=None, aiding=None):
+                 landmark_capacity=4096, odometry=False, zupt=None, aiding=None, anchors=None):
         """``device_map``: keep the feature map in the context's tables
         (msckf_map.h) instead of ``map_server``'s dicts; ``map_capacity``: rows
         per filter.  A shared ``ctx`` must already have its tables.
@@ -142,7 +144,13 @@ class MSCKF:
         ``aiding_callback`` are applied by the frame that follows them within
         ``max_age`` (msckf_aid.h), after propagation (and the zero-velocity
         update) and before augmentation; the device gates them, the decisions
-        are read with the frame's state into ``aid_log``."""
+        are read with the frame's state into ``aid_log``.
+        ``anchors`` (an ``AnchorConfig``; None: off): the messages given to
+        ``anchor_callback`` are applied by the frame whose timestamp lies within
+        ``time_tol`` of theirs (msckf_anchor.h), after propagation (and the
+        zero-velocity update and the aiding fix) and before augmentation; the
+        device gates every anchor, the records are read with the frame's state
+        into ``anchor_log``."""
         if config is None:
             config = FilterConfig()
         elif not isinstance(config, FilterConfig):
@@ -166,6 +174,14 @@ class MSCKF:
         self._aid_buffer = []              # AidingFix messages not yet past a frame
         self.aid_log = []                  # (frame, rows, applied, gamma), one per fix enqueued
         self._aid_count = 0
+        if anchors is not None and not isinstance(anchors, AnchorConfig):
+            raise TypeError("anchors must be an AnchorConfig or None, not %r" % (anchors,))
+        self.anchors = anchors
+        self._anchor_prm = anchors.params(config.observation_noise) if anchors is not None else None   # checks it
+        self._anchor_buffer = []           # (timestamp, msckf_anchor_t records) not yet past a frame, in time order
+        self.anchor_log = []               # (frame, n, used, applied), one per message enqueued
+        self.anchor_dropped = 0            # messages no frame matched
+        self._anchor_count = 0
         if self.device_keyframes and not self.device_map:
             raise ValueError("device_keyframes=True needs device_map=True: the choice is part of the map's prune "
                              "select")
@@ -269,6 +285,11 @@ class MSCKF:
         if kind == "aid_results":
             app, gam, rows, cnt = ctx.aid_results([f])
             return bool(app[0]), float(gam[0]), int(rows[0]), int(cnt[0])
+        if kind == "anchor":   # (kind, the frame's msckf_anchor_t records)
+            return ctx.anchor_batch([f], [req[1]], self._anchor_prm)
+        if kind == "anchor_results":
+            app, used, rows, cnt = ctx.anchor_results([f])
+            return bool(app[0]), int(used[0]), int(rows[0]), int(cnt[0])
         if kind == "triangulate":
             return ctx.triangulate(f, req[1], req[2], req[3])
         if kind == "update":
@@ -361,6 +382,43 @@ class MSCKF:
         merged = self.aiding.merge(buf[:n], t_frame)
         return _lib.aid_fix(*merged) if merged is not None else None
 
+    def anchor_callback(self, fix):
+        """Buffers an ``AnchorFix``; the frame whose timestamp lies within
+        ``time_tol`` of the message's applies it.  A message no frame matches
+        (an older one, or one from before gravity initialisation) is dropped
+        and counted in ``anchor_dropped``."""
+        if self.anchors is None:
+            raise ValueError("anchor_callback needs MSCKF(anchors=AnchorConfig())")
+        p, cov, z = self.anchors.in_world(fix)
+        if len(p) > ANCHOR_MAX:
+            raise ValueError("an AnchorFix holds at most %d anchors, not %d" % (ANCHOR_MAX, len(p)))
+        rec = _lib.pack_anchors(p, cov, z)
+        with self._lock:
+            buf = self._anchor_buffer   # kept in time order; messages usually arrive so
+            k = len(buf)
+            while k > 0 and buf[k - 1][0] > fix.timestamp:
+                k -= 1
+            buf.insert(k, (float(fix.timestamp), rec))
+
+    def _take_anchors(self, t_frame):
+        """The frame's anchor records (None without a message); the messages
+        up to the frame time leave the buffer."""
+        buf, tol, msg = self._anchor_buffer, self.anchors.time_tol, None
+        while buf and buf[0][0] <= t_frame + tol:
+            t, rec = buf.pop(0)
+            if t >= t_frame - tol and msg is None:
+                msg = rec
+            else:
+                self.anchor_dropped += 1
+        return msg
+
+    def anchor_status(self):
+        """(status uint8 [K], gamma [K]) of the anchors of the last message
+        applied (_lib.ANCHOR_USED / GATED / DEPTH / NOT_PD); synchronises."""
+        if self.anchors is None:
+            raise ValueError("anchor_status needs MSCKF(anchors=AnchorConfig())")
+        return self.ctx.anchor_status(self.slot)
+
     def _initialize_gravity_and_bias(self):
         """msckf.py:235-258"""
         sw = np.zeros(3)
@@ -390,6 +448,8 @@ class MSCKF:
             raise TypeError("a TrackMessage names a message on the device, which only the device feature map reads: "
                             "it needs MSCKF(device_map=True)")
         if not self.is_gravity_set:
+            if self.anchors is not None and self._take_anchors(feature_msg.timestamp) is not None:
+                self.anchor_dropped += 1   # before gravity initialisation
             return None
         if self.is_first_img:
             self.is_first_img = False
@@ -401,6 +461,9 @@ class MSCKF:
         fix = self._take_fix(feature_msg.timestamp) if self.aiding is not None else None
         if fix is not None:   # the frame's aiding fix (msckf_aid.h)
             yield ("aid", fix)
+        anc = self._take_anchors(feature_msg.timestamp) if self.anchors is not None else None
+        if anc is not None:   # the frame's anchor message (msckf_anchor.h)
+            yield ("anchor", anc)
         yield from self._state_augmentation()
         if self.device_map:
             yield from self._map_add_and_remove_lost(feature_msg)
@@ -422,6 +485,9 @@ class MSCKF:
         if fix is not None:
             app, gam, rows, self._aid_count = yield ("aid_results",)
             self.aid_log.append((self._n_published, rows, app, gam))
+        if anc is not None:
+            app, used, _, self._anchor_count = yield ("anchor_results",)
+            self.anchor_log.append((self._n_published, len(anc), used, app))
         res = self._publish_from(feature_msg.timestamp, _lib.unpack_imu(st[0]))
         if self.odometry:
             res = VioOdometry(*res, st[3], st[4])
@@ -805,6 +871,12 @@ class MSCKF:
         """Aiding fixes applied to this filter's slot (the device's counter as
         of the last frame's read)."""
         return self._aid_count
+
+    @property
+    def anchor_count(self):
+        """Anchor updates applied to this filter's slot (the device's counter
+        as of the last frame's read)."""
+        return self._anchor_count
 
     def clear_landmarks(self):
         """Empties the archive (an online reset does not: the world frame continues)."""

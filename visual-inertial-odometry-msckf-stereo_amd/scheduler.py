@@ -15,6 +15,10 @@ with ONE batched launch:
   aid         -> msckf_aid_batch         (aiding=AidingConfig: the lanes that have
                  a fix at this frame, each with its own; aid_results ->
                  msckf_aid_results, behind the frame's states read)
+  anchor      -> msckf_anchor_batch      (anchors=AnchorConfig: the lanes that
+                 have an anchor message at this frame, each with its own;
+                 anchor_results -> msckf_anchor_results, behind the frame's
+                 states read)
   augment     -> msckf_augment_batch
   triangulate -> msckf_batch_load + msckf_batch_triangulate
   update      -> msckf_batch_load + msckf_batch_update (per row cap), results
@@ -51,6 +55,7 @@ from .trajectory import Trajectory
 
 # pipeline order: a lane waiting at an earlier stage is served first
 _ORDER = {"set_state": 0, "propagate": 1, "zupt": 1.5, "zupt_results": 5.1, "aid": 1.7, "aid_results": 5.2,
+          "anchor": 1.8, "anchor_results": 5.25,
           "augment": 2, "map_add_lost": 2.5, "map_add_lost_tracks": 2.5, "triangulate": 3,
           "map_triangulate": 3, "update": 4, "map_update": 4, "states": 5, "map_prune_select": 5.3,
           "map_keyframe_select": 5.3,
@@ -62,8 +67,11 @@ class MultiMSCKF:
 
     def __init__(self, n, config=None, dtype=np.float64, device=0, cam_capacity=None, lane_configs=None,
                  device_map=False, map_capacity=1024, device_keyframes=False, landmarks=None, landmark_capacity=4096,
-                 odometry=False, zupt=None, aiding=None):
-        """``aiding``: as ``MSCKF``'s, one ``AidingConfig`` for all lanes (they
+                 odometry=False, zupt=None, aiding=None, anchors=None):
+        """``anchors``: as ``MSCKF``'s, one ``AnchorConfig`` for all lanes;
+        ``anchor_callback(i, fix)`` feeds lane i, and one msckf_anchor_batch per
+        frame step lists only the lanes that have a message.
+        ``aiding``: as ``MSCKF``'s, one ``AidingConfig`` for all lanes (they
         share the parameters); ``aiding_callback(i, fix)`` feeds lane i, and one
         msckf_aid_batch per frame step lists only the lanes that have a fix.
         ``zupt``: as ``MSCKF``'s, one ``ZuptConfig`` for all lanes (as the
@@ -114,7 +122,8 @@ class MultiMSCKF:
         self.landmark_mode = landmarks
         self.lanes = [MSCKF(cfgs[i], ctx=self.ctx, slot=i, device_map=self.device_map,
                             device_keyframes=self.device_keyframes, landmarks=landmarks,
-                            landmark_capacity=landmark_capacity, odometry=odometry, zupt=zupt, aiding=aiding)
+                            landmark_capacity=landmark_capacity, odometry=odometry, zupt=zupt, aiding=aiding,
+                            anchors=anchors)
                       for i in range(n)]
         self.launches = defaultdict(int)       # batched device calls per request kind
 
@@ -139,6 +148,9 @@ class MultiMSCKF:
 
     def aiding_callback(self, i, fix):
         self.lanes[i].aiding_callback(fix)
+
+    def anchor_callback(self, i, fix):
+        self.lanes[i].anchor_callback(fix)
 
     def feature_callbacks(self, msgs):
         """``msgs``: {lane index: feature_msg}.  Returns {lane index:
@@ -198,6 +210,12 @@ class MultiMSCKF:
         if kind == "aid_results":
             app, gam, rows, cnt = ctx.aid_results(slots)
             return [(bool(app[w]), float(gam[w]), int(rows[w]), int(cnt[w])) for w in range(len(group))]
+        if kind == "anchor":   # the lanes share the parameters (one AnchorConfig), each has its own anchors
+            ctx.anchor_batch(slots, [r[1] for r in reqs], self.lanes[group[0]]._anchor_prm)
+            return [None] * len(group)
+        if kind == "anchor_results":
+            app, used, rows, cnt = ctx.anchor_results(slots)
+            return [(bool(app[w]), int(used[w]), int(rows[w]), int(cnt[w])) for w in range(len(group))]
         if kind == "triangulate":
             self._load(slots, reqs, with_pw=False)
             ctx.batch_triangulate()

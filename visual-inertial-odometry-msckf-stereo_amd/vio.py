@@ -54,12 +54,13 @@ class MultiStereoVIO:
     def __init__(self, n, filter_config=None, frontend_config=None, lane_filter_configs=None,
                  lane_frontend_configs=None, dtype=np.float64, device=0, map_capacity=1024, device_keyframes=True,
                  handoff="device", landmarks=None, landmark_capacity=4096, odometry=False, zupt=None,
-                 aiding=None):
+                 aiding=None, anchors=None):
         """``landmarks`` / ``landmark_capacity`` / ``odometry``: as
         ``MultiMSCKF``'s (msckf_odometry.h); ``zupt``: as ``MultiMSCKF``'s
         (msckf_zupt.h; ``zupt_log(i)`` reads lane i's decisions); ``aiding``:
         as ``MultiMSCKF``'s (msckf_aid.h; ``aiding_callback(i, fix)``,
-        ``aid_log(i)``).
+        ``aid_log(i)``); ``anchors``: as ``MultiMSCKF``'s (msckf_anchor.h;
+        ``anchor_callback(i, fix)``, ``anchor_log(i)``).
         ``filter_config`` / ``lane_filter_configs``: as ``MultiMSCKF``'s
         ``config`` / ``lane_configs``; ``frontend_config`` /
         ``lane_frontend_configs``: as ``MultiImageProcessor``'s (device_pipeline
@@ -76,7 +77,7 @@ class MultiStereoVIO:
                                       lane_configs=lane_filter_configs, device_map=True, map_capacity=map_capacity,
                                       device_keyframes=device_keyframes, landmarks=landmarks,
                                       landmark_capacity=landmark_capacity, odometry=odometry, zupt=zupt,
-                                      aiding=aiding)
+                                      aiding=aiding, anchors=anchors)
         except BaseException:
             self.frontend.close()
             raise
@@ -121,6 +122,10 @@ class MultiStereoVIO:
         """Lane i's aiding decisions, (frame, rows, applied, gamma) per fix enqueued."""
         return self.filters.lanes[i].aid_log
 
+    def anchor_log(self, i):
+        """Lane i's anchor decisions, (frame, n, used, applied) per message enqueued."""
+        return self.filters.lanes[i].anchor_log
+
     # ------------------------------------------------------------ callbacks --
     def imu_callback(self, i, msg):
         self.frontend.imu_callback(i, msg)
@@ -128,6 +133,9 @@ class MultiStereoVIO:
 
     def aiding_callback(self, i, fix):
         self.filters.aiding_callback(i, fix)
+
+    def anchor_callback(self, i, fix):
+        self.filters.anchor_callback(i, fix)
 
     def stereo_callbacks(self, msgs):
         """``msgs``: {lane index: stereo_msg}.  Returns {lane index:
@@ -173,11 +181,11 @@ class StereoVIO:
 
     def __init__(self, filter_config=None, frontend_config=None, dtype=np.float64, device=0, map_capacity=1024,
                  device_keyframes=True, handoff="device", landmarks=None, landmark_capacity=4096, odometry=False,
-                 zupt=None, aiding=None):
+                 zupt=None, aiding=None, anchors=None):
         self.multi = MultiStereoVIO(1, filter_config=filter_config, frontend_config=frontend_config, dtype=dtype,
                                     device=device, map_capacity=map_capacity, device_keyframes=device_keyframes,
                                     handoff=handoff, landmarks=landmarks, landmark_capacity=landmark_capacity,
-                                    odometry=odometry, zupt=zupt, aiding=aiding)
+                                    odometry=odometry, zupt=zupt, aiding=aiding, anchors=anchors)
         self.handoff = self.multi.handoff
 
     def __enter__(self):
@@ -223,8 +231,22 @@ class StereoVIO:
     def aid_count(self):
         return self.filter.aid_count
 
+    @property
+    def anchor_log(self):
+        return self.multi.anchor_log(0)
+
+    @property
+    def anchor_count(self):
+        return self.filter.anchor_count
+
+    def anchor_status(self):
+        return self.filter.anchor_status()
+
     def imu_callback(self, msg):
         self.multi.imu_callback(0, msg)
+
+    def anchor_callback(self, fix):
+        self.multi.anchor_callback(0, fix)
 
     def aiding_callback(self, fix):
         self.multi.aiding_callback(0, fix)
