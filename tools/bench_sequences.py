@@ -25,7 +25,12 @@ the device applied; --static-s S is the streams' time at rest before they move
 (msckf_aid.h; kernels aid_gain and aid_apply): position + velocity messages
 from the streams' ground truth at --aid-rate Hz (default 5), 12 ms before a
 frame, with 2 cm / 2 cm/s noise, rotated into each filter's world frame, and
-reports how many fixes the device applied.  --anchors turns the anchor fixes on
+reports how many fixes the device applied.  --aid-latency S (with --aiding)
+hands every fix over S seconds after its stamp (AidingFix.received) and turns
+AidingConfig.delayed on: the fixes older than max_age take the delayed path on
+the window's clones (msckf_aid_delayed.h; kernels aid_delayed_gain and
+aid_delayed_apply; their velocity rows are left out), and the line reports how
+many of them the device applied.  --anchors turns the anchor fixes on
 (msckf_anchor.h; kernels anchor_gain and anchor_apply): --anchor-n (default 8)
 points per stream surveyed to 5 mm, their stereo observations from the ground
 truth with the streams' pixel noise at --anchor-rate Hz (default 5), at the
@@ -54,14 +59,15 @@ from msckf_amd.scheduler import MultiMSCKF  # noqa: E402
 from msckf_amd.trajectory import ate  # noqa: E402
 
 
-def aiding_fixes(seq, static_s, rate, seed, lead=0.012, sigma=0.02, t_start=100.0):
+def aiding_fixes(seq, static_s, rate, seed, lead=0.012, sigma=0.02, t_start=100.0, latency=None):
     """Position + velocity messages for ``seq`` from its ground truth, in the
     filter's world frame: ``lead`` before every (20 / rate)-th frame from the
     first one the filter publishes (one second of gravity initialisation), with
     ``sigma`` noise.  The two world frames are aligned by A = R_filter_iw
     R_truth_iw^T at that frame, where both origins are 0 (the stream rests): the
     filter's initial attitude is the one its gravity initialisation will
-    compute from the first 200 IMU samples."""
+    compute from the first 200 IMU samples.  ``latency``: the messages reach the
+    filter that many seconds after their stamp."""
     A, first = _alignment(seq)
     rng = np.random.default_rng(seed)
     t0, h, out = t_start + static_s, 1e-4, []
@@ -71,7 +77,8 @@ def aiding_fixes(seq, static_s, rate, seed, lead=0.012, sigma=0.02, t_start=100.
         v = (synth._traj(t + h, t0)[0] - synth._traj(t - h, t0)[0]) / (2 * h)
         out.append(msckf_amd.AidingFix(t, position=A @ p + sigma * rng.standard_normal(3),
                                        velocity=A @ v + sigma * rng.standard_normal(3),
-                                       position_var=sigma ** 2, velocity_var=sigma ** 2))
+                                       position_var=sigma ** 2, velocity_var=sigma ** 2,
+                                       received=None if latency is None else t + latency))
     return out
 
 
@@ -135,6 +142,9 @@ def main():
     ap.add_argument("--aiding", action="store_true",
                     help="aiding fixes (msckf_aid.h): synthetic position + velocity messages from the ground truth")
     ap.add_argument("--aid-rate", type=float, default=5.0, help="fixes per second and stream with --aiding")
+    ap.add_argument("--aid-latency", type=float, default=None,
+                    help="with --aiding: the fixes arrive this many seconds late and AidingConfig.delayed is on "
+                         "(msckf_aid_delayed.h)")
     ap.add_argument("--anchors", action="store_true",
                     help="anchor fixes (msckf_anchor.h): synthetic surveyed points observed from the ground truth")
     ap.add_argument("--anchor-n", type=int, default=8, help="anchors per stream with --anchors")
@@ -144,13 +154,15 @@ def main():
     a = ap.parse_args()
     if a.device_keyframes and not a.device_map:
         ap.error("--device-keyframes needs --device-map")
+    if a.aid_latency is not None and not a.aiding:
+        ap.error("--aid-latency needs --aiding")
     if a.landmarks == "device" and not a.device_map:
         ap.error("--landmarks device needs --device-map")
     opt = dict(landmarks=a.landmarks, odometry=a.odometry) if a.landmarks or a.odometry else {}
     if a.zupt:
         opt["zupt"] = msckf_amd.ZuptConfig()
     if a.aiding:
-        opt["aiding"] = msckf_amd.AidingConfig()
+        opt["aiding"] = msckf_amd.AidingConfig(delayed=a.aid_latency is not None)
     if a.anchors:
         opt["anchors"] = msckf_amd.AnchorConfig()
     seq_kw = {} if a.static_s is None else dict(static_s=a.static_s)
@@ -159,7 +171,7 @@ def main():
     mine = replicas.shard(list(range(a.seqs)), grp.rank, grp.world)
     seqs = [synth.make_sequence(a.frames, 100 + i, **seq_kw) for i in mine]
     streams = [FeatureStream.from_synthetic(q) for q in seqs]
-    fixes = [aiding_fixes(q, 1.2 if a.static_s is None else a.static_s, a.aid_rate, 1000 + i)
+    fixes = [aiding_fixes(q, 1.2 if a.static_s is None else a.static_s, a.aid_rate, 1000 + i, latency=a.aid_latency)
              for q, i in zip(seqs, mine)] if a.aiding else None
     anchor_msgs = [anchor_fixes(q, a.anchor_rate, a.anchor_n, 2000 + i) for q, i in zip(seqs, mine)] if a.anchors else None
     n_frames = sum(s.n_frames for s in streams)
@@ -193,6 +205,8 @@ def main():
     archived = [int(multi.landmarks(i).next_seq) for i in range(len(streams))] if multi and a.landmarks else None
     zupt_applied = [[int(ln.zupt_count), len(ln.zupt_log)] for ln in multi.lanes] if multi and a.zupt else None
     aid_applied = [[int(ln.aid_count), len(ln.aid_log)] for ln in multi.lanes] if multi and a.aiding else None
+    delayed_applied = [[int(ln.aid_delayed_count), len(ln.aid_delayed_log)] for ln in multi.lanes] \
+        if multi and a.aid_latency is not None else None
     anchor_applied = [[int(ln.anchor_count), len(ln.anchor_log)] for ln in multi.lanes] if multi and a.anchors else None
     if multi:
         multi.close()
@@ -224,6 +238,9 @@ def main():
         out["zupt_applied_of_rank0"] = zupt_applied
     if aid_applied is not None:   # per lane: fixes applied, fixes enqueued
         out["aid_applied_of_rank0"] = aid_applied
+    if delayed_applied is not None:   # per lane: late fixes applied, late fixes enqueued
+        out["aid_latency_s"] = a.aid_latency
+        out["aid_delayed_applied_of_rank0"] = delayed_applied
     if anchor_applied is not None:   # per lane: updates applied, messages enqueued
         out["anchor_applied_of_rank0"] = anchor_applied
     if archived is not None:

@@ -251,6 +251,33 @@ AID_SIGS = {
 }
 AID_EXPORTED = tuple(AID_SIGS)
 
+# the delayed aiding fixes (include/msckf_aid_delayed.h), same library and context
+AID_DELAYED_POS, AID_DELAYED_DIR = 0x07, 0x38
+AID_DELAYED_NONE, AID_DELAYED_APPLIED, AID_DELAYED_GATED, AID_DELAYED_NOT_PD, AID_DELAYED_BAD_SLOT = -1, 0, 1, 2, 3
+
+
+class MsckfAidDelayedFixT(C.Structure):
+    _fields_ = [("z", C.c_double * 6), ("var", C.c_double * 6), ("lam", C.c_double), ("rows", C.c_int32),
+                ("slot", C.c_int32)]
+
+
+def aid_delayed_fix(z, var, slot, lam, rows):
+    """A msckf_aid_delayed_fix_t from z (6), var (6), the clone slot, the
+    fraction lambda towards slot + 1 and the 6-bit row mask."""
+    f = MsckfAidDelayedFixT()
+    f.z[:] = [float(x) for x in z]
+    f.var[:] = [float(x) for x in var]
+    f.lam, f.rows, f.slot = float(lam), int(rows), int(slot)
+    return f
+
+
+AID_DELAYED_SIGS = {
+    "msckf_aid_delayed_batch": (C.c_int, [_P, C.c_int, _I, C.POINTER(MsckfAidDelayedFixT),
+                                          C.POINTER(MsckfAidParamsT)]),
+    "msckf_aid_delayed_results": (C.c_int, [_P, C.c_int, _I, _I, _D, _I, _I, _I64]),
+}
+AID_DELAYED_EXPORTED = tuple(AID_DELAYED_SIGS)
+
 # the anchor fixes (include/msckf_anchor.h), same library and context
 ANCHOR_MAX = 64
 ANCHOR_USED, ANCHOR_GATED, ANCHOR_DEPTH, ANCHOR_NOT_PD = 0, 1, 2, 3
@@ -316,6 +343,7 @@ def load_library(path: str = LIB_PATH):
                                   list(MAP_SIGS.items()) + list(KEYFRAME_SIGS.items()) + list(HANDOFF_SIGS.items()) +
                                   list(EQUALIZE_SIGS.items()) + list(ODOMETRY_SIGS.items()) +
                                   list(ZUPT_SIGS.items()) + list(AID_SIGS.items()) + list(ANCHOR_SIGS.items()) +
+                                  list(AID_DELAYED_SIGS.items()) +
                                   list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
             fn.restype = res
@@ -858,6 +886,39 @@ class Context:
                                                    _ptr(gam, C.c_double), _ptr(rows, C.c_int32),
                                                    _ptr(cnt, C.c_int64)))
         return app.astype(bool), gam, rows, cnt
+
+    # ---- the delayed aiding fixes (msckf_aid_delayed.h) ----
+    def aid_delayed_batch(self, filters, fixes, prm):
+        """msckf_aid_delayed_batch: the gated update of the listed filters on
+        their window clones, each with its own fix (``MsckfAidDelayedFixT``, see
+        ``aid_delayed_fix``), and the parameters ``prm`` (a ``MsckfAidParamsT``
+        or a ``config.AidingConfig``).  Asynchronous, nothing comes back
+        (``aid_delayed_results``)."""
+        filters = _i32(filters)
+        n = len(filters)
+        fixes = list(fixes)
+        if len(fixes) != n:
+            raise ValueError("aid_delayed_batch: %d filters but %d fixes" % (n, len(fixes)))
+        arr = (MsckfAidDelayedFixT * max(n, 1))(*fixes)
+        if not isinstance(prm, MsckfAidParamsT):
+            prm = prm.params()
+        with self.lock:
+            self._check(self.lib.msckf_aid_delayed_batch(self.h, n, _ptr(filters, C.c_int32), arr, C.byref(prm)))
+
+    def aid_delayed_results(self, filters):
+        """msckf_aid_delayed_results (synchronises): (applied bool [n], gamma
+        [n], rows int32 [n] -- the last fix's mask, status int32 [n] --
+        ``AID_DELAYED_*``, count int64 [n] -- delayed fixes ever applied) of the
+        listed filters."""
+        filters = _i32(filters)
+        n = len(filters)
+        app, gam, rows, sta, cnt = (np.zeros(n, np.int32), np.zeros(n), np.zeros(n, np.int32), np.zeros(n, np.int32),
+                                    np.zeros(n, np.int64))
+        with self.lock:
+            self._check(self.lib.msckf_aid_delayed_results(self.h, n, _ptr(filters, C.c_int32), _ptr(app, C.c_int32),
+                                                           _ptr(gam, C.c_double), _ptr(rows, C.c_int32),
+                                                           _ptr(sta, C.c_int32), _ptr(cnt, C.c_int64)))
+        return app.astype(bool), gam, rows, sta, cnt
 
     # ---- the anchor fixes (msckf_anchor.h) ----
     def anchor_batch(self, filters, anchors, prm):

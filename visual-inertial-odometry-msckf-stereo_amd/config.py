@@ -138,6 +138,7 @@ class ZuptConfig:
 
 
 AID_GROUPS = ("position", "velocity", "body_velocity", "direction")   # rows 3 g + axis (include/msckf_aid.h)
+AID_TIME_TOL = 1e-9   # a delayed fix stamped this close to a clone's time is taken at the clone (lambda = 0)
 
 
 def _orthonormal(R, what):
@@ -154,7 +155,9 @@ class AidingFix:
     odometer frame and the reference direction as seen in the IMU frame, taken
     at ``timestamp``.  ``*_var``: the variance, a scalar or one per axis;
     ``*_axes``: which axes are used (a barometer is ``position`` with
-    ``position_axes=(0, 0, 1)``)."""
+    ``position_axes=(0, 0, 1)``).  ``received`` (optional) is the time the
+    message reached the host: no frame before it sees the fix, so a replay can
+    hand late messages over up front (``AidingConfig.delayed``)."""
     timestamp: float
     position: "np.ndarray | None" = None
     velocity: "np.ndarray | None" = None
@@ -168,6 +171,7 @@ class AidingFix:
     velocity_axes: tuple = (1, 1, 1)
     body_velocity_axes: tuple = (1, 1, 1)
     direction_axes: tuple = (1, 1, 1)
+    received: "float | None" = None
 
 
 @dataclass
@@ -186,6 +190,10 @@ class AidingConfig:
     chi2: "float | None" = None
     max_age: float = 0.05
     world_from_ext: tuple = field(default_factory=lambda: (np.eye(3), np.zeros(3)))
+    # include/msckf_aid_delayed.h: a fix older than max_age is applied at its own timestamp, on the window's clones
+    delayed: bool = False
+    max_delay: float = 1.0    # the largest age of a delayed fix
+    max_gap: float = 0.15     # the largest time between the two clones a delayed fix is interpolated between
 
     def gates(self):
         """The gate by the number of kept rows, 1..12."""
@@ -200,6 +208,9 @@ class AidingConfig:
             raise ValueError("AidingConfig.dir_w must be a unit vector (to 1e-6)")
         if not (self.max_age >= 0.0):
             raise ValueError("AidingConfig.max_age = %r must be >= 0" % (self.max_age,))
+        if not (self.max_delay >= 0.0) or not (self.max_gap > 0.0):
+            raise ValueError("AidingConfig.max_delay = %r must be >= 0 and max_gap = %r > 0"
+                             % (self.max_delay, self.max_gap))
         if np.isnan(self.gates()).any():
             raise ValueError("AidingConfig.chi2 is NaN")
         R, t = self.world_from_ext
@@ -262,6 +273,37 @@ class AidingConfig:
                     if g == 0:
                         dt = t_frame - fix.timestamp
         return (z, var, float(dt), mask) if mask else None
+
+    def route(self, timestamp, mask, t_frame, cam_times):
+        """Where a buffered fix (its timestamp <= t_frame and its 12-bit mask)
+        goes at the frame t_frame, ``cam_times`` being the live clones' times,
+        oldest first: ("current",) -- into ``merge``; ("delayed", slot, lambda,
+        rows, dropped) -- include/msckf_aid_delayed.h's update on the clones
+        ``slot`` and ``slot + 1`` with the 6-bit mask ``rows``, ``dropped`` the
+        VEL / BVEL bits it cannot use; ("wait",) -- stale but newer than the
+        newest clone, the next frame brackets it; ("drop", reason)."""
+        age = t_frame - timestamp
+        if age <= self.max_age:
+            return ("current",)
+        if not self.delayed:
+            return ("drop", "stale")
+        rows = (mask & 0x007) | (((mask >> 9) & 0x7) << 3)
+        if not rows:
+            return ("drop", "no delayed rows")
+        if age > self.max_delay:
+            return ("drop", "older than max_delay")
+        if not len(cam_times) or timestamp < cam_times[0] - AID_TIME_TOL:
+            return ("drop", "older than the window")
+        if timestamp > cam_times[-1] + AID_TIME_TOL:
+            return ("wait",)
+        for s, ts in enumerate(cam_times):
+            if abs(timestamp - ts) <= AID_TIME_TOL:
+                return ("delayed", s, 0.0, rows, mask & 0x1f8)
+        s = max(k for k, ts in enumerate(cam_times) if ts < timestamp)
+        gap = cam_times[s + 1] - cam_times[s]
+        if gap > self.max_gap + AID_TIME_TOL:
+            return ("drop", "clones too far apart")
+        return ("delayed", s, float((timestamp - cam_times[s]) / gap), rows, mask & 0x1f8)
 
 
 ANCHOR_MAX = 64   # MSCKF_ANCHOR_MAX: anchors per filter and call (include/msckf_anchor.h)

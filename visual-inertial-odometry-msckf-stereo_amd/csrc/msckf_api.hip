@@ -21,6 +21,8 @@
 #include "msckf_aid_dev.h"
 #include "../../include/msckf_anchor.h"
 #include "msckf_anchor_dev.h"
+#include "../../include/msckf_aid_delayed.h"
+#include "msckf_aid_delayed_dev.h"
 #include "msckf_common.h"
 #include "msckf_handoff_dev.h"
 #include "msckf_launch.h"
@@ -266,6 +268,12 @@ struct msckf_ctx {
         DBuf<unsigned char> store, in;     // W and the records; a call's input block
         AnchorDev dev{};
     } anchor;
+    // the delayed aiding fixes (msckf_aid_delayed.h): absent until the first msckf_aid_delayed_batch
+    struct AidDelayed {
+        bool on = false;
+        DBuf<unsigned char> store, in;     // W and the records; a call's input block
+        AidDelayedDev dev{};
+    } aid_delayed;
 };
 
 namespace {
@@ -1428,7 +1436,8 @@ int msckf_destroy(msckf_ctx_t* c) {
     for (auto* b : {&c->P, &c->imu, &c->cams, &c->P_snap, &c->imu_snap, &c->cams_snap, &c->Hthin, &c->Lc, &c->Vi, &c->Sii, &c->G, &c->Tm, &c->W, &c->Wk,
                     &c->dx, &c->batch, &c->obs_ws, &c->obs_ht, &c->obs_g, &c->fqr, &c->tau, &c->ysq, &c->scratch,
                     &c->map.store, &c->map.in, &c->map.out, &c->map.aux, &c->lm.store, &c->lm.in, &c->zupt.store, &c->zupt.in,
-                    &c->aid.store, &c->aid.in, &c->anchor.store, &c->anchor.in})
+                    &c->aid.store, &c->aid.in, &c->anchor.store, &c->anchor.in,
+                    &c->aid_delayed.store, &c->aid_delayed.in})
         b->release();
     c->map.chi2.release();
     for (auto* b : {&c->ncams, &c->ncams_snap, &c->ident, &c->info, &c->afail, &c->row_off, &c->iscratch, &c->ill_list,
@@ -1791,3 +1800,5 @@ int msckf_debug_kalman(msckf_ctx_t* c) {
 #include "msckf_aid_api.inc"
 
 #include "msckf_anchor_api.inc"
+
+#include "msckf_aid_delayed_api.inc"

@@ -144,7 +144,13 @@ class MSCKF:
         ``aiding_callback`` are applied by the frame that follows them within
         ``max_age`` (msckf_aid.h), after propagation (and the zero-velocity
         update) and before augmentation; the device gates them, the decisions
-        are read with the frame's state into ``aid_log``.
+        are read with the frame's state into ``aid_log``.  With
+        ``AidingConfig(delayed=True)`` a fix older than ``max_age`` is not dropped
+        but applied at its own timestamp, on the pose interpolated between the two
+        window clones that bracket it (msckf_aid_delayed.h; position and
+        direction rows only), oldest first and before the frame's own fix; the
+        records go to ``aid_delayed_log``, what no path takes to
+        ``aid_dropped_log``.
         ``anchors`` (an ``AnchorConfig``; None: off): the messages given to
         ``anchor_callback`` are applied by the frame whose timestamp lies within
         ``time_tol`` of theirs (msckf_anchor.h), after propagation (and the
@@ -174,6 +180,10 @@ class MSCKF:
         self._aid_buffer = []              # AidingFix messages not yet past a frame
         self.aid_log = []                  # (frame, rows, applied, gamma), one per fix enqueued
         self._aid_count = 0
+        # the delayed path (msckf_aid_delayed.h), AidingConfig(delayed=True)
+        self.aid_delayed_log = []          # (frame, rows, applied, gamma, slot, lambda, status), one per fix enqueued
+        self.aid_dropped_log = []          # (frame, timestamp, reason): fixes no path took, and VEL / BVEL rows left out
+        self._aid_delayed_count = 0
         if anchors is not None and not isinstance(anchors, AnchorConfig):
             raise TypeError("anchors must be an AnchorConfig or None, not %r" % (anchors,))
         self.anchors = anchors
@@ -204,6 +214,7 @@ class MSCKF:
         else:
             self.map_server: "OrderedDict[int, Feature]" = OrderedDict()
         self.cam_ids: list = []            # cam-state ids in slot order (oldest first)
+        self.cam_times: list = []          # their frame times, in step with cam_ids
         self.imu_timestamp = None
         self.imu_id = None
         self._next_id = 0
@@ -285,6 +296,11 @@ class MSCKF:
         if kind == "aid_results":
             app, gam, rows, cnt = ctx.aid_results([f])
             return bool(app[0]), float(gam[0]), int(rows[0]), int(cnt[0])
+        if kind == "aid_delayed":   # (kind, one late fix on its clone pair)
+            return ctx.aid_delayed_batch([f], [req[1]], self._aid_prm)
+        if kind == "aid_delayed_results":
+            app, gam, rows, sta, cnt = ctx.aid_delayed_results([f])
+            return bool(app[0]), float(gam[0]), int(rows[0]), int(sta[0]), int(cnt[0])
         if kind == "anchor":   # (kind, the frame's msckf_anchor_t records)
             return ctx.anchor_batch([f], [req[1]], self._anchor_prm)
         if kind == "anchor_results":
@@ -378,9 +394,46 @@ class MSCKF:
         n = 1
         while n < len(buf) and buf[n].timestamp <= t_frame:
             n += 1
-        self._aid_buffer = buf[n:]
-        merged = self.aiding.merge(buf[:n], t_frame)
+        held = [f for f in buf[:n] if f.received is not None and f.received > t_frame]   # not handed over yet
+        seen = [f for f in buf[:n] if not (f.received is not None and f.received > t_frame)]
+        self._aid_buffer = held + buf[n:]
+        merged = self.aiding.merge(seen, t_frame)
         return _lib.aid_fix(*merged) if merged is not None else None
+
+    def _take_fixes(self, t_frame):
+        """``_take_fix`` with ``AidingConfig.route`` in front (delayed=True):
+        (the late fixes as [(msckf_aid_delayed_fix_t, slot, lambda)], oldest
+        first, the frame's merged fix or None).  A stale fix newer than the
+        newest clone stays in the buffer for the next frame; what no path takes
+        goes to ``aid_dropped_log``."""
+        cfg, buf = self.aiding, self._aid_buffer
+        keep, cur, late = [], [], []
+        for fix in buf:
+            if fix.timestamp > t_frame or (fix.received is not None and fix.received > t_frame):
+                keep.append(fix)
+                continue
+            z, var, mask = cfg.rows_of(fix)
+            rt = cfg.route(fix.timestamp, mask, t_frame, self.cam_times)
+            if rt[0] == "current":
+                cur.append(fix)
+            elif rt[0] == "wait":
+                keep.append(fix)
+            elif rt[0] == "drop":
+                self.aid_dropped_log.append((self._n_published, fix.timestamp, rt[1]))
+            else:
+                _, slot, lam, rows, other = rt
+                if other:
+                    self.aid_dropped_log.append((self._n_published, fix.timestamp,
+                                                 "velocity rows 0x%03x of a delayed fix" % other))
+                late.append((_lib.aid_delayed_fix(np.r_[z[0:3], z[9:12]], np.r_[var[0:3], var[9:12]], slot, lam, rows),
+                             slot, lam))
+        self._aid_buffer = keep
+        merged = cfg.merge(cur, t_frame) if cur else None
+        return late, (_lib.aid_fix(*merged) if merged is not None else None)
+
+    def _log_delayed(self, slot, lam, rec):
+        app, gam, rows, status, self._aid_delayed_count = rec
+        self.aid_delayed_log.append((self._n_published, rows, app, gam, slot, lam, status))
 
     def anchor_callback(self, fix):
         """Buffers an ``AnchorFix``; the frame whose timestamp lies within
@@ -458,13 +511,21 @@ class MSCKF:
         zupt = self.zupt is not None and len(ws) > 0
         if zupt:   # the standstill update with the means of exactly the samples propagated (msckf_zupt.h)
             yield ("zupt", np.mean(np.array(ws).reshape(-1, 3), axis=0), np.mean(np.array(accs).reshape(-1, 3), axis=0))
-        fix = self._take_fix(feature_msg.timestamp) if self.aiding is not None else None
+        late = []
+        if self.aiding is not None and self.aiding.delayed:   # late fixes on their clones first, oldest first
+            late, fix = self._take_fixes(feature_msg.timestamp)
+            for k, (f, slot, lam) in enumerate(late):   # one request each (msckf_aid_delayed.h)
+                yield ("aid_delayed", f)
+                if k + 1 < len(late):   # the next fix overwrites the slot's record: read it now (synchronises; rare)
+                    self._log_delayed(slot, lam, (yield ("aid_delayed_results",)))
+        else:
+            fix = self._take_fix(feature_msg.timestamp) if self.aiding is not None else None
         if fix is not None:   # the frame's aiding fix (msckf_aid.h)
             yield ("aid", fix)
         anc = self._take_anchors(feature_msg.timestamp) if self.anchors is not None else None
         if anc is not None:   # the frame's anchor message (msckf_anchor.h)
             yield ("anchor", anc)
-        yield from self._state_augmentation()
+        yield from self._state_augmentation(feature_msg.timestamp)
         if self.device_map:
             yield from self._map_add_and_remove_lost(feature_msg)
             yield from self._map_prune_cam_state_buffer()
@@ -482,6 +543,8 @@ class MSCKF:
         if zupt:   # the device has drained: the update's record
             app, gam, self._zupt_count = yield ("zupt_results",)
             self.zupt_log.append((self._n_published, app, gam))
+        if late:   # the last late fix's record (the earlier ones were read behind their calls)
+            self._log_delayed(late[-1][1], late[-1][2], (yield ("aid_delayed_results",)))
         if fix is not None:
             app, gam, rows, self._aid_count = yield ("aid_results",)
             self.aid_log.append((self._n_published, rows, app, gam))
@@ -522,10 +585,17 @@ class MSCKF:
         self.imu_msg_buffer = self.imu_msg_buffer[used:]
         return ws, accs
 
-    def _state_augmentation(self):
+    def _state_augmentation(self, time):
         """msckf.py:385-407"""
         yield ("augment",)
         self.cam_ids.append(self.imu_id)
+        self.cam_times.append(time)
+
+    def _drop_cams(self, ids):
+        """The pruned cam states leave ``cam_ids`` and ``cam_times`` together."""
+        for c in ids:
+            k = self.cam_ids.index(c)
+            del self.cam_ids[k], self.cam_times[k]
 
     def _add_feature_observations(self, feature_msg):
         """msckf.py:409-427"""
@@ -740,8 +810,7 @@ class MSCKF:
                 del feat.observations[c]
         slots = [self.cam_ids.index(c) for c in rm]
         yield ("prune", np.array(slots, np.int32))
-        for c in rm:
-            self.cam_ids.remove(c)
+        self._drop_cams(rm)
 
     # ------------------------------------------------- the map on the device --
     def _log_update(self, pend, ids, counts, dofs, row_cap):
@@ -819,8 +888,7 @@ class MSCKF:
             self.shape_log.append((self._n_published, 0, 21 + 6 * len(self.cam_ids)))
         yield ("map_prune_commit", info[tri, 3], ok[tri], pw[tri])
         yield ("prune", slots)
-        for c in rm:
-            self.cam_ids.remove(c)
+        self._drop_cams(rm)
 
     # ------------------------------------------------------ output / reset --
     def publish(self, time):
@@ -873,6 +941,12 @@ class MSCKF:
         return self._aid_count
 
     @property
+    def aid_delayed_count(self):
+        """Delayed aiding fixes applied to this filter's slot (the device's
+        counter as of the last record read)."""
+        return self._aid_delayed_count
+
+    @property
     def anchor_count(self):
         """Anchor updates applied to this filter's slot (the device's counter
         as of the last frame's read)."""
@@ -898,6 +972,7 @@ class MSCKF:
         if np.max(np.sqrt(d)) < thr:
             return
         self.cam_ids.clear()
+        self.cam_times.clear()
         if self.device_map:
             yield ("map_clear",)
         else:

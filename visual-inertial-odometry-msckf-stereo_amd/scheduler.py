@@ -15,6 +15,11 @@ with ONE batched launch:
   aid         -> msckf_aid_batch         (aiding=AidingConfig: the lanes that have
                  a fix at this frame, each with its own; aid_results ->
                  msckf_aid_results, behind the frame's states read)
+  aid_delayed -> msckf_aid_delayed_batch (AidingConfig(delayed=True): the lanes'
+                 j-th late fix of the frame step, one call per j, before aid;
+                 aid_delayed_results -> msckf_aid_delayed_results, behind the
+                 frame's states read, and behind the call when a lane has
+                 another late fix in the same frame)
   anchor      -> msckf_anchor_batch      (anchors=AnchorConfig: the lanes that
                  have an anchor message at this frame, each with its own;
                  anchor_results -> msckf_anchor_results, behind the frame's
@@ -55,7 +60,7 @@ from .trajectory import Trajectory
 
 # pipeline order: a lane waiting at an earlier stage is served first
 _ORDER = {"set_state": 0, "propagate": 1, "zupt": 1.5, "zupt_results": 5.1, "aid": 1.7, "aid_results": 5.2,
-          "anchor": 1.8, "anchor_results": 5.25,
+          "anchor": 1.8, "anchor_results": 5.25, "aid_delayed": 1.6, "aid_delayed_results": 1.65,
           "augment": 2, "map_add_lost": 2.5, "map_add_lost_tracks": 2.5, "triangulate": 3,
           "map_triangulate": 3, "update": 4, "map_update": 4, "states": 5, "map_prune_select": 5.3,
           "map_keyframe_select": 5.3,
@@ -210,6 +215,12 @@ class MultiMSCKF:
         if kind == "aid_results":
             app, gam, rows, cnt = ctx.aid_results(slots)
             return [(bool(app[w]), float(gam[w]), int(rows[w]), int(cnt[w])) for w in range(len(group))]
+        if kind == "aid_delayed":   # the lanes' j-th late fix of the frame step, each on its own clone pair
+            ctx.aid_delayed_batch(slots, [r[1] for r in reqs], self.lanes[group[0]]._aid_prm)
+            return [None] * len(group)
+        if kind == "aid_delayed_results":
+            app, gam, rows, sta, cnt = ctx.aid_delayed_results(slots)
+            return [(bool(app[w]), float(gam[w]), int(rows[w]), int(sta[w]), int(cnt[w])) for w in range(len(group))]
         if kind == "anchor":   # the lanes share the parameters (one AnchorConfig), each has its own anchors
             ctx.anchor_batch(slots, [r[1] for r in reqs], self.lanes[group[0]]._anchor_prm)
             return [None] * len(group)

@@ -122,6 +122,11 @@ class MultiStereoVIO:
         """Lane i's aiding decisions, (frame, rows, applied, gamma) per fix enqueued."""
         return self.filters.lanes[i].aid_log
 
+    def aid_delayed_log(self, i):
+        """Lane i's delayed aiding decisions (``AidingConfig(delayed=True)``),
+        (frame, rows, applied, gamma, slot, lambda, status) per late fix enqueued."""
+        return self.filters.lanes[i].aid_delayed_log
+
     def anchor_log(self, i):
         """Lane i's anchor decisions, (frame, n, used, applied) per message enqueued."""
         return self.filters.lanes[i].anchor_log
@@ -230,6 +235,14 @@ class StereoVIO:
     @property
     def aid_count(self):
         return self.filter.aid_count
+
+    @property
+    def aid_delayed_log(self):
+        return self.multi.aid_delayed_log(0)
+
+    @property
+    def aid_delayed_count(self):
+        return self.filter.aid_delayed_count
 
     @property
     def anchor_log(self):
