@@ -16,7 +16,8 @@ HDRS     := $(SRC)/msckf_common.h $(SRC)/msckf_launch.h $(SRC)/msckf_gate_routes
             include/msckf_zupt.h $(SRC)/msckf_zupt_dev.h $(SRC)/msckf_zupt_api.inc $(SRC)/msckf_correct.h \
             include/msckf_aid.h $(SRC)/msckf_aid_dev.h $(SRC)/msckf_aid_api.inc $(SRC)/msckf_rank_apply.h \
             include/msckf_anchor.h $(SRC)/msckf_anchor_dev.h $(SRC)/msckf_anchor_api.inc \
-            include/msckf_aid_delayed.h $(SRC)/msckf_aid_delayed_dev.h $(SRC)/msckf_aid_delayed_api.inc
+            include/msckf_aid_delayed.h $(SRC)/msckf_aid_delayed_dev.h $(SRC)/msckf_aid_delayed_api.inc \
+            include/msckf_standstill.h $(SRC)/msckf_standstill_dev.h
 
 all: $(LIB)
 

@@ -15,6 +15,11 @@ ends) and the calls among them that end with a synchronisation.  (b) and (c)
 must publish (a)'s poses bit for bit; the tool exits non-zero otherwise.
 
     python tools/bench_vio.py [--frames 60] [--lanes 1 11] [--repeat R] [--dtype f64|f32]
+                              [--zupt [--zupt-cue veto|either]]
+
+--zupt adds the zero-velocity update (msckf_zupt.h) to every composition;
+--zupt-cue gates it on the front-end's track motion as well (msckf_standstill.h,
+VisionCue's defaults in the given mode).
 
 --repeat R runs (a), (b), (c), (a), (b), (c), ... R times over, alternating, on
 the same rendered streams in one process, one JSON line per run (every run of
@@ -45,7 +50,11 @@ class Wired:
     """(a): the two classes joined by hand, behind MultiStereoVIO's interface."""
 
     def __init__(self, n, frontend_config, dtype, opt):
-        cfg = fe_mod.FrontendConfig(**{**vars(frontend_config), "device_pipeline": True, "device_tracks": True})
+        extra = {"device_pipeline": True, "device_tracks": True}
+        vision = getattr(opt.get("zupt"), "vision", None)
+        if vision is not None:   # as MultiStereoVIO switches it on
+            extra.update(track_motion=True, track_motion_quantile=float(vision.quantile))
+        cfg = fe_mod.FrontendConfig(**{**vars(frontend_config), **extra})
         self.frontend = fe_mod.MultiImageProcessor(n, config=cfg)
         self.filters = MultiMSCKF(n, dtype=dtype, device_map=True, device_keyframes=True, **opt)
 
@@ -115,8 +124,18 @@ def main():
     ap.add_argument("--landmarks", choices=("host", "device"), default=None,
                     help="keep the landmark archive (msckf_odometry.h) in every composition")
     ap.add_argument("--odometry", action="store_true", help="the frames' reads bring the pose covariance along")
+    ap.add_argument("--zupt", action="store_true", help="the zero-velocity update (msckf_zupt.h) in every composition")
+    ap.add_argument("--zupt-cue", choices=("veto", "either"), default=None,
+                    help="with --zupt: the vision standstill cue (msckf_standstill.h) in this mode")
     a = ap.parse_args()
+    if a.zupt_cue and not a.zupt:
+        ap.error("--zupt-cue needs --zupt")
     opt = dict(landmarks=a.landmarks, odometry=a.odometry) if a.landmarks or a.odometry else {}
+    tag = {}
+    if a.zupt:
+        from msckf_amd import VisionCue, ZuptConfig
+        opt["zupt"] = ZuptConfig(vision=VisionCue(mode=a.zupt_cue) if a.zupt_cue else None)
+        tag = {"zupt": True, "zupt_cue": a.zupt_cue}
     dtype = np.float64 if a.dtype == "f64" else np.float32
     W, H = 752, 480
     K = np.array([450.0, 450.0, 376.0, 240.0])
@@ -141,7 +160,8 @@ def main():
                               "frames_per_lane": a.frames, "dtype": a.dtype, "resolution": [W, H],
                               "lane_frames_per_s": round(fps, 1), "device_calls_per_step": per,
                               "synchronisations_per_step": syncs, "poses": n_poses,
-                              "poses_identical_to_first_wired": same, **opt,
+                              "poses_identical_to_first_wired": same,
+                              **{k: v for k, v in opt.items() if k != "zupt"}, **tag,
                               "note": "timed from step 2 on; host bookkeeping in Python; synthetic stream"}),
                   flush=True)
             bad |= n_poses == 0

@@ -223,6 +223,26 @@ ZUPT_SIGS = {
 }
 ZUPT_EXPORTED = tuple(ZUPT_SIGS)
 
+# the vision standstill cue (include/msckf_standstill.h): the front-end's motion statistic and the cued ZUPT
+CUE_MOVING, CUE_STILL, CUE_UNKNOWN = 0, 1, 2
+CUE_MODES = {"veto": 0, "either": 1}        # MSCKF_CUE_MODE_*
+CUE_UNKNOWNS = {"imu": 0, "reject": 1}      # MSCKF_CUE_UNKNOWN_*
+
+
+class MsckfZuptCueT(C.Structure):
+    _fields_ = [("max_px", C.c_double), ("min_tracks", C.c_int32), ("mode", C.c_int32), ("unknown", C.c_int32)]
+
+
+STANDSTILL_SIGS = {
+    "mfe_motion_sets": (C.c_int, [_P, C.c_int, _I, _F, _F, C.c_double, _I, _F]),
+    "mfe_tracks_motion_enable": (C.c_int, [_P, C.c_int, C.c_double]),
+    "mfe_tracks_motion_get": (C.c_int, [_P, C.c_int, _I, _I, _F]),
+    "msckf_zupt_batch_cued": (C.c_int, [_P, _P, C.c_int, _I, _I, _I, _F, _D, _D, C.POINTER(MsckfZuptParamsT),
+                                        C.POINTER(MsckfZuptCueT)]),
+    "msckf_zupt_cue_results": (C.c_int, [_P, C.c_int, _I, _I, _D, _I64, _I, _I, _F]),
+}
+STANDSTILL_EXPORTED = tuple(STANDSTILL_SIGS)
+
 # the aiding fixes (include/msckf_aid.h), same library and context
 AID_POS, AID_VEL, AID_BVEL, AID_DIR = 0x007, 0x038, 0x1c0, 0xe00
 
@@ -342,7 +362,7 @@ def load_library(path: str = LIB_PATH):
                                   list(FRONTEND_LANES_SIGS.items()) + list(FRONTEND_TRACKS_SIGS.items()) +
                                   list(MAP_SIGS.items()) + list(KEYFRAME_SIGS.items()) + list(HANDOFF_SIGS.items()) +
                                   list(EQUALIZE_SIGS.items()) + list(ODOMETRY_SIGS.items()) +
-                                  list(ZUPT_SIGS.items()) + list(AID_SIGS.items()) + list(ANCHOR_SIGS.items()) +
+                                  list(ZUPT_SIGS.items()) + list(STANDSTILL_SIGS.items()) + list(AID_SIGS.items()) + list(ANCHOR_SIGS.items()) +
                                   list(AID_DELAYED_SIGS.items()) +
                                   list(REPLICA_SIGS.items())):
             fn = getattr(lib, name)
@@ -856,6 +876,52 @@ class Context:
             self._check(self.lib.msckf_zupt_results(self.h, n, _ptr(filters, C.c_int32), _ptr(app, C.c_int32),
                                                     _ptr(gam, C.c_double), _ptr(cnt, C.c_int64)))
         return app.astype(bool), gam, cnt
+
+    # ---- the cued zero-velocity update (msckf_standstill.h) ----
+    def zupt_batch_cued(self, filters, gyro_mean, acc_mean, prm, cue, fe=None, lanes=None, cue_n=None, cue_d2=None):
+        """msckf_zupt_batch_cued: ``zupt_batch`` with the vision cue ``cue`` (a
+        ``MsckfZuptCueT`` or a ``config.VisionCue``) in the decision.  The cue's
+        source is either the front-end context ``fe`` (a ``frontend.Frontend``)
+        with listed filter w reading lane ``lanes[w]``'s motion record on the
+        device, or the host arrays ``cue_n`` int32 [n] (< 0: no record) and
+        ``cue_d2`` float32 [n].  Asynchronous (``zupt_cue_results``)."""
+        filters = _i32(filters)
+        n = len(filters)
+        gyro_mean, acc_mean = _f64(gyro_mean, (n, 3)), _f64(acc_mean, (n, 3))
+        if not isinstance(prm, MsckfZuptParamsT):
+            prm = prm.params()
+        if not isinstance(cue, MsckfZuptCueT):
+            cue = cue.params()
+        if fe is not None:
+            lanes = _i32(lanes)
+            if len(lanes) != n:
+                raise ValueError("%d lanes for %d filters" % (len(lanes), n))
+            cn = cd = None
+        else:
+            lanes = None
+            cn = None if cue_n is None else _i32(cue_n)
+            cd = None if cue_d2 is None else np.ascontiguousarray(cue_d2, np.float32).reshape(-1)
+            if (cn is not None and len(cn) != n) or (cd is not None and len(cd) != n):
+                raise ValueError("cue arrays do not match the %d filters" % n)
+        with self.lock:
+            self._check(self.lib.msckf_zupt_batch_cued(
+                self.h, fe.h if fe is not None else None, n, _ptr(filters, C.c_int32), _ptr(lanes, C.c_int32),
+                _ptr(cn, C.c_int32), _ptr(cd, C.c_float), _ptr(gyro_mean, C.c_double), _ptr(acc_mean, C.c_double),
+                C.byref(prm), C.byref(cue)))
+
+    def zupt_cue_results(self, filters):
+        """msckf_zupt_cue_results (synchronises, one read): (applied bool [n],
+        gamma [n], count int64 [n], cue int32 [n], cue_n int32 [n], cue_d2
+        float32 [n]) of the listed filters."""
+        filters = _i32(filters)
+        n = len(filters)
+        app, gam, cnt = np.zeros(n, np.int32), np.zeros(n), np.zeros(n, np.int64)
+        cue, cn, cd = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float32)
+        with self.lock:
+            self._check(self.lib.msckf_zupt_cue_results(
+                self.h, n, _ptr(filters, C.c_int32), _ptr(app, C.c_int32), _ptr(gam, C.c_double),
+                _ptr(cnt, C.c_int64), _ptr(cue, C.c_int32), _ptr(cn, C.c_int32), _ptr(cd, C.c_float)))
+        return app.astype(bool), gam, cnt, cue, cn, cd
 
     # ---- the aiding fixes (msckf_aid.h) ----
     def aid_batch(self, filters, fixes, prm):

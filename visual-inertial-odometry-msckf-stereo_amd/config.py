@@ -100,18 +100,75 @@ def _default_T_cn_cnm1():
 _ZUPT_ROWS = {"vel": 1, "gyro": 2, "acc": 4}   # MSCKF_ZUPT_VEL / GYRO / ACC (include/msckf_zupt.h)
 
 
+_CUE_MODES = ("veto", "either")       # MSCKF_CUE_MODE_VETO / EITHER (include/msckf_standstill.h)
+_CUE_UNKNOWNS = ("imu", "reject")     # MSCKF_CUE_UNKNOWN_IMU / REJECT
+
+
+@dataclass
+class VisionCue:
+    """The vision standstill cue of the zero-velocity update
+    (include/msckf_standstill.h): the ``quantile`` of the squared frame-to-frame
+    pixel displacement of the front-end's tracks says STILL when it is at most
+    ``max_px``^2, provided at least ``min_tracks`` tracks stand behind it.
+
+    ``mode``: "veto" -- the update needs the IMU gate AND a still image;
+    "either" -- a still image applies it even where the speed or chi^2 gate
+    refuses.  ``unknown``: what a frame without a usable cue does, "imu" (the
+    IMU gate alone decides, as without a cue) or "reject".
+
+    The defaults are reasoned, not measured.  ``max_px`` = 0.5: the LK tracker
+    stops when an iteration moves a point by less than ``track_precision`` =
+    0.01 px, so a point at rest comes back within a few hundredths of a pixel
+    of where it was; half a pixel is 50 termination steps above that floor and
+    still below the one pixel at which the image itself resolves motion.
+    ``min_tracks`` = 20: the default grid (4 x 5 cells, at least 3 features
+    each) keeps 60 features or more, and 20 is one per cell -- below that the
+    median stands on a few cells and one moving object can own it.  No
+    reference counterpart."""
+    max_px: float = 0.5
+    quantile: float = 0.5
+    min_tracks: int = 20
+    mode: str = "veto"
+    unknown: str = "imu"
+
+    def __post_init__(self):
+        if not float(self.max_px) >= 0.0:
+            raise ValueError("VisionCue.max_px = %r must be >= 0" % (self.max_px,))
+        if not 0.0 <= float(self.quantile) <= 1.0:
+            raise ValueError("VisionCue.quantile = %r outside [0, 1]" % (self.quantile,))
+        if int(self.min_tracks) < 1:
+            raise ValueError("VisionCue.min_tracks = %r must be >= 1" % (self.min_tracks,))
+        if self.mode not in _CUE_MODES:
+            raise ValueError("VisionCue.mode = %r, expected one of %r" % (self.mode, _CUE_MODES))
+        if self.unknown not in _CUE_UNKNOWNS:
+            raise ValueError("VisionCue.unknown = %r, expected one of %r" % (self.unknown, _CUE_UNKNOWNS))
+
+    def params(self):
+        """The C-ABI's msckf_zupt_cue_t."""
+        from ._lib import MsckfZuptCueT
+        return MsckfZuptCueT(float(self.max_px), int(self.min_tracks), _CUE_MODES.index(self.mode),
+                             _CUE_UNKNOWNS.index(self.unknown))
+
+
 @dataclass
 class ZuptConfig:
     """Parameters of the zero-velocity update (include/msckf_zupt.h): the noise
     variances of the three row groups, the gate on gamma (``chi2``; None: the
     reference's table at the kept rows' count, ``chi2_threshold(m)``), the gate
-    on the speed and the groups kept.  No reference counterpart."""
+    on the speed and the groups kept.  ``vision`` (None or a ``VisionCue``):
+    the front-end's track motion takes part in the decision
+    (include/msckf_standstill.h).  No reference counterpart."""
     vel_noise: float = 1e-4
     gyro_noise: float = 4e-6
     acc_noise: float = 4e-4
     chi2: "float | None" = None
     max_speed: float = 0.1
     rows: tuple = ("vel", "gyro", "acc")
+    vision: "VisionCue | None" = None
+
+    def __post_init__(self):
+        if self.vision is not None and not isinstance(self.vision, VisionCue):
+            raise TypeError("ZuptConfig.vision must be a VisionCue or None, not %r" % (self.vision,))
 
     def mask(self) -> int:
         rows = (self.rows,) if isinstance(self.rows, str) else tuple(self.rows)

@@ -17,6 +17,7 @@
 #include "../../include/msckf_map.h"
 #include "../../include/msckf_odometry.h"
 #include "../../include/msckf_zupt.h"
+#include "../../include/msckf_standstill.h"
 #include "../../include/msckf_aid.h"
 #include "msckf_aid_dev.h"
 #include "../../include/msckf_anchor.h"

@@ -39,6 +39,9 @@
 //               lk_point, stereo_point, k_two_point_ransac and the detection stages;
 //               k_trk_assemble and k_trk_uv write the published ids / uv into the
 //               call's block or into the lanes' message tables (include/msckf_handoff.h)
+//   k_motion_sets / k_trk_motion   the motion statistic of include/msckf_standstill.h:
+//               a quantile of the squared pixel displacement of point pairs, one
+//               workgroup per set or lane, an exact radix select over LDS
 // Images are 8-bit, small (752 x 480 for EuRoC) and read through the cache:
 // these kernels are latency-class work, not HBM-bound.
 #include <hip/hip_runtime.h>
@@ -57,7 +60,9 @@
 #include "../../include/msckf_handoff.h"
 #include "../../include/msckf_tracks.h"
 #include "../../include/msckf_equalize.h"
+#include "../../include/msckf_standstill.h"
 #include "msckf_handoff_dev.h"
+#include "msckf_standstill_dev.h"
 
 namespace {
 
@@ -1345,6 +1350,99 @@ __global__ void __launch_bounds__(TRK_THREADS) k_trk_compact(TrkDev d, const Trk
     if (tid == 0) d.cnt[stage * d.n_lanes + l] = n_out;
 }
 
+// ------------------------------------------- the motion statistic (msckf_standstill.h) --
+// The k-th smallest (k = floor(q (n - 1))) of d2_j = |curr_j - prev_j|^2, j < n <=
+// MOT_MAXN, in float32 with each product and the sum rounded once, by one workgroup of
+// MOT_THREADS.  Pair j is row (idx ? idx[j] : j) of prev and curr.  The values live in
+// LDS as their bit patterns (d2 >= +0, and non-negative floats order as their bits); the
+// selection fixes one bit per pass from the most significant down: the candidates whose
+// bit is 0 are counted from ballots, per wave in a register, the wave counts through LDS
+// in wave order.  A wave whose first row lies beyond n returns at once (the barriers
+// wait on the waves that remain); for n = 0 the value is NaN.  Thread 0 returns true
+// and the value in `out`.  A caller must do nothing after the call but thread 0's stores of
+// the result: no barrier, no LDS, no work that counts on the waves that have returned.
+constexpr int MOT_THREADS = 256, MOT_WAVES = MOT_THREADS / 64, MOT_MAXN = MFE_RANSAC_MAX_SET_POINTS;
+
+__device__ __forceinline__ bool motion_quantile(int n, double q, const float* __restrict__ prev,
+                                                const float* __restrict__ curr, const int* __restrict__ idx,
+                                                float& out) {
+#pragma clang fp contract(off)
+    __shared__ unsigned s_key[MOT_MAXN];
+    __shared__ int s_wcnt[2][MOT_WAVES];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    n = min(n, MOT_MAXN);
+    if (n <= 0) {
+        out = __builtin_nanf("");
+        return tid == 0;
+    }
+    if (wave * 64 >= n) return false;
+    const int nw = min(MOT_WAVES, (n + 63) >> 6);   // the waves that stay: the first nw
+    for (int j = tid; j < n; j += MOT_THREADS) {
+        const size_t r = idx ? (size_t)idx[j] : (size_t)j;
+        const float dx = curr[2 * r] - prev[2 * r], dy = curr[2 * r + 1] - prev[2 * r + 1];
+        const float xx = dx * dx, yy = dy * dy;
+        s_key[j] = __float_as_uint(xx + yy);
+    }
+    __syncthreads();
+    int k = (int)floor(q * (double)(n - 1));
+    k = max(0, min(k, n - 1));
+    unsigned prefix = 0u, mask = 0u;
+    for (int bit = 31, it = 0; bit >= 0; --bit, ++it) {
+        const unsigned b = 1u << bit;
+        int c = 0;
+        for (int j0 = wave * 64; j0 < n; j0 += MOT_THREADS) {   // wave-uniform bounds: every lane ballots
+            const int j = j0 + (tid & 63);
+            bool zero = false;
+            if (j < n) {
+                const unsigned key = s_key[j];
+                zero = (key & mask) == prefix && !(key & b);
+            }
+            c += __popcll(__ballot(zero));
+        }
+        if ((tid & 63) == 0) s_wcnt[it & 1][wave] = c;
+        __syncthreads();
+        int zeros = 0;
+        for (int w = 0; w < nw; ++w) zeros += s_wcnt[it & 1][w];
+        if (k >= zeros) {
+            k -= zeros;
+            prefix |= b;
+        }
+        mask |= b;
+    }
+    out = __uint_as_float(prefix);
+    return tid == 0;
+}
+
+// mfe_motion_sets: one workgroup per set
+__global__ void __launch_bounds__(MOT_THREADS) k_motion_sets(const int32_t* __restrict__ set_off,
+                                                             const float* __restrict__ prev,
+                                                             const float* __restrict__ curr, double q,
+                                                             int32_t* __restrict__ n_out, float* __restrict__ d2_out) {
+    const int s = blockIdx.x;
+    const size_t o = (size_t)set_off[s];
+    const int n = set_off[s + 1] - set_off[s];
+    float v;
+    if (motion_quantile(n, q, prev + 2 * o, curr + 2 * o, nullptr, v)) {
+        n_out[s] = n;
+        d2_out[s] = v;
+    }
+}
+
+// behind step 4's compaction, one workgroup per lane of the call: the survivors' cam0 in the
+// current table against their tracked point; writes the lane's record
+__global__ void __launch_bounds__(MOT_THREADS) k_trk_motion(TrkDev d, const TrkLane* __restrict__ lanes, double q,
+                                                            msckf::MotionRec* __restrict__ rec) {
+    const int l = blockIdx.x;
+    const TrkLane& L = lanes[l];
+    const size_t row = ((size_t)L.cur * d.n_lanes + L.lane) * d.cap, w = (size_t)l * d.cap;
+    const int n = min(d.cnt[2 * d.n_lanes + l], d.cap);
+    float v;
+    if (motion_quantile(n, q, d.cam0 + 2 * row, d.c0 + 2 * w, d.idx + ((size_t)2 * d.n_lanes + l) * d.cap, v)) {
+        rec[L.lane].n = n;
+        rec[L.lane].d2 = v;
+    }
+}
+
 // step 4, before k_two_point_ransac: set_off of the call's 2 n_rs sets
 __global__ void __launch_bounds__(64) k_trk_rs_off(TrkDev d, const int32_t* __restrict__ rs_lane, int n_rs) {
     if (threadIdx.x != 0) return;
@@ -1577,6 +1675,12 @@ struct mfe_ctx {
     double* msg_uv = nullptr;
     std::vector<int> msg_n;
     std::vector<unsigned char> msg_valid;
+    // the lanes' motion records (msckf_standstill.h), in the same block: {n, d2} [lane]; the switch, its
+    // quantile and the valid flags are the host's record
+    msckf::MotionRec* mot = nullptr;
+    std::vector<unsigned char> mot_valid;
+    bool mot_on = false;
+    double mot_q = 0.5;
 };
 
 // msckf_handoff_dev.h: the message tables as msckf_map_add_lost_tracks reads them
@@ -1589,6 +1693,16 @@ bool msckf::mfe_track_messages(const mfe_ctx* c, msckf::TrackMsgView& v) {
     v.uv = c->msg_uv;
     v.n = c->msg_n.data();
     v.valid = c->msg_valid.data();
+    return true;
+}
+
+// msckf_standstill_dev.h: the motion records as msckf_zupt_batch_cued reads them
+bool msckf::mfe_track_motion(const mfe_ctx* c, msckf::TrackMotionView& v) {
+    if (!c || !c->trk.ids) return false;
+    v.device = c->device;
+    v.n_lanes = c->trk.n_lanes;
+    v.rec = c->mot;
+    v.valid = c->mot_valid.data();
     return true;
 }
 
@@ -2332,7 +2446,8 @@ int mfe_tracks_create(mfe_ctx_t* c, int n_lanes, int cap, int grid_row, int grid
                  o_cinl = b.add(NL * CK), o_noff = b.add(4 * NL * cells), o_ooff = b.add(4 * NL * cells),
                  o_rsoff = b.add(4 * (2 * NL + 1)), o_rsprev = b.add(16 * 2 * NL * C), o_rscurr = b.add(16 * 2 * NL * C),
                  o_rswork = b.add(32 * 2 * NL * C), o_rsinfo = b.add(8 * MFE_RANSAC_INFO_LEN * 2 * NL),
-                 o_rsinl = b.add(2 * NL * C), o_mids = b.add(8 * NL * C), o_muv = b.add(32 * NL * C);
+                 o_rsinl = b.add(2 * NL * C), o_mids = b.add(8 * NL * C), o_muv = b.add(32 * NL * C),
+                 o_mot = b.add(sizeof(msckf::MotionRec) * NL);
     void* p;
     if (int rc = dev_alloc(c, &p, b.size)) return rc;
     MFE_HIP(hipMemset(p, 0, b.size));   // every lane empty, next_id = 0
@@ -2356,6 +2471,8 @@ int mfe_tracks_create(mfe_ctx_t* c, int n_lanes, int cap, int grid_row, int grid
     c->msg_uv = (double*)(m + o_muv);
     c->msg_n.assign(n_lanes, 0);
     c->msg_valid.assign(n_lanes, 0);
+    c->mot = (msckf::MotionRec*)(m + o_mot);
+    c->mot_valid.assign(n_lanes, 0);
     return 0;
 }
 
@@ -2375,6 +2492,7 @@ int mfe_tracks_put(mfe_ctx_t* c, int lane, int n, const int64_t* ids, const int3
                  (long long)d.cap - (long long)d.cells * d.grid_min, d.cap);
     if (n > 0 && (!ids || !lifetimes || !cam0 || !cam1)) MFE_FAIL(-1, "null table array");
     c->msg_valid[lane] = 0;   // the lane's message described the table this call replaces
+    c->mot_valid[lane] = 0;   // and so did its motion record (msckf_standstill.h)
     MFE_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t t = (size_t)c->trk_cur[lane] * d.n_lanes + lane, row = t * d.cap, N = (size_t)n;
@@ -2459,7 +2577,7 @@ static int tracks_step_body(mfe_ctx_t* c, bool to_msg, int n_lanes, const int32_
     if (c->W < 16 || c->H < 16) MFE_FAIL(-1, "image %dx%d is smaller than 16x16", c->W, c->H);
     if (max_kp < 1 || max_kp > c->kp_cap) MFE_FAIL(-1, "max_kp = %d outside [1, %d]", max_kp, c->kp_cap);
     // a lane's message describes its current table, which this call replaces (msckf_handoff.h)
-    for (int l = 0; l < n_lanes; ++l) c->msg_valid[lanes[l]] = 0;
+    for (int l = 0; l < n_lanes; ++l) c->msg_valid[lanes[l]] = 0, c->mot_valid[lanes[l]] = 0;
     MFE_HIP(hipSetDevice(c->device));
     if (int rc = grow_grid_work(c, n_lanes)) return rc;
     hipStream_t s = c->stream;
@@ -2539,6 +2657,8 @@ static int tracks_step_body(mfe_ctx_t* c, bool to_msg, int n_lanes, const int32_
     }
     hipLaunchKernelGGL(k_trk_rs_flag, per256, dim3(256), 0, s, d, dl);
     hipLaunchKernelGGL(k_trk_compact, dim3(n_lanes), dim3(TRK_THREADS), 0, s, d, dl, 2);
+    if (c->mot_on)   // the motion statistic of step 4's survivors (msckf_standstill.h)
+        hipLaunchKernelGGL(k_trk_motion, dim3(n_lanes), dim3(MOT_THREADS), 0, s, d, dl, c->mot_q, c->mot);
     // step 6: the stages of mfe_fast_grid_sets
     const GridWork& g = c->work;
     MFE_HIP(hipMemsetAsync(g.mask, 1, NL * W * H, s));
@@ -2584,6 +2704,7 @@ static int tracks_step_body(mfe_ctx_t* c, bool to_msg, int n_lanes, const int32_
         }
         c->trk_cur[lanes[i]] ^= 1;
         c->trk_n[lanes[i]] = hn[i];
+        if (c->mot_on) c->mot_valid[lanes[i]] = 1;
     }
     return 0;
 }
@@ -2655,6 +2776,75 @@ int mfe_tracks_msg_get(mfe_ctx_t* c, int lane, int32_t* valid, int32_t* n, int64
     MFE_HIP(hipMemcpyAsync(ids, c->msg_ids + row, 8 * N, hipMemcpyDeviceToHost, s));
     MFE_HIP(hipMemcpyAsync(uv, c->msg_uv + 4 * row, 32 * N, hipMemcpyDeviceToHost, s));
     MFE_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// ------------------------------------- the motion statistic (msckf_standstill.h) --
+int mfe_motion_sets(mfe_ctx_t* c, int n_sets, const int32_t* set_off, const float* prev, const float* curr, double q,
+                    int32_t* n_out, float* d2_out) {
+    if (!c) MFE_FAIL(-1, "null context");
+    if (n_sets < 0 || n_sets > MFE_MAX_SETS) MFE_FAIL(-1, "n_sets = %d outside [0, %d]", n_sets, MFE_MAX_SETS);
+    if (!(q >= 0.0 && q <= 1.0)) MFE_FAIL(-1, "q = %g outside [0, 1]", q);
+    if (n_sets == 0) return 0;
+    if (check_set_off(c, n_sets, set_off, "set_off")) return -1;
+    if (!n_out || !d2_out) MFE_FAIL(-1, "null output");
+    const size_t T = (size_t)set_off[n_sets], S = (size_t)n_sets;
+    if (T > 0 && (!prev || !curr)) MFE_FAIL(-1, "null point array");
+    for (int s = 0; s < n_sets; ++s)
+        if (set_off[s + 1] - set_off[s] > MFE_RANSAC_MAX_SET_POINTS)
+            MFE_FAIL(-1, "set %d: %d pairs, above %d", s, set_off[s + 1] - set_off[s], MFE_RANSAC_MAX_SET_POINTS);
+    for (size_t i = 0; i < 2 * T; ++i)
+        if (!std::isfinite(prev[i]) || !std::isfinite(curr[i]))
+            MFE_FAIL(-1, "pair %zu: a coordinate is not finite", i / 2);
+    MFE_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    Block b;
+    const size_t o_off = b.add(4 * (S + 1)), o_prev = b.add(8 * T), o_curr = b.add(8 * T), in_bytes = b.size,
+                 o_n = b.add(4 * S), o_d2 = b.add(4 * S), out_bytes = b.size - o_n;
+    if (int rc = grow_scratch(c, b.size)) return rc;
+    unsigned char *h = c->rs_host, *d = c->rs_dev;
+    memcpy(h + o_off, set_off, 4 * (S + 1));
+    if (T > 0) {
+        memcpy(h + o_prev, prev, 8 * T);
+        memcpy(h + o_curr, curr, 8 * T);
+    }
+    MFE_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_motion_sets, dim3(n_sets), dim3(MOT_THREADS), 0, s, (const int32_t*)(d + o_off),
+                       (const float*)(d + o_prev), (const float*)(d + o_curr), q, (int32_t*)(d + o_n),
+                       (float*)(d + o_d2));
+    MFE_HIP(hipGetLastError());
+    MFE_HIP(hipMemcpyAsync(h + o_n, d + o_n, out_bytes, hipMemcpyDeviceToHost, s));
+    MFE_HIP(hipStreamSynchronize(s));
+    memcpy(n_out, h + o_n, 4 * S);
+    memcpy(d2_out, h + o_d2, 4 * S);
+    return 0;
+}
+
+int mfe_tracks_motion_enable(mfe_ctx_t* c, int on, double q) {
+    if (!c) MFE_FAIL(-1, "null context");
+    if (!c->trk.ids) MFE_FAIL(-1, "the context has no track tables (mfe_tracks_create)");
+    if (!(q >= 0.0 && q <= 1.0)) MFE_FAIL(-1, "q = %g outside [0, 1]", q);
+    c->mot_on = on != 0;
+    c->mot_q = q;
+    return 0;
+}
+
+int mfe_tracks_motion_get(mfe_ctx_t* c, int lane, int32_t* valid, int32_t* n, float* d2) {
+    if (check_trk_lane(c, lane)) return -1;
+    if (!valid || !n || !d2) MFE_FAIL(-1, "null output");
+    *valid = c->mot_valid[lane] ? 1 : 0;
+    *n = 0;
+    *d2 = std::nanf("");
+    MFE_HIP(hipSetDevice(c->device));
+    if (!*valid) {
+        MFE_HIP(hipStreamSynchronize(c->stream));
+        return 0;
+    }
+    msckf::MotionRec r;
+    MFE_HIP(hipMemcpyAsync(&r, c->mot + lane, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    MFE_HIP(hipStreamSynchronize(c->stream));
+    *n = r.n;
+    *d2 = r.d2;
     return 0;
 }
 

@@ -14,6 +14,12 @@
 // The gain reads rows 0:12 of P, which the rank-m update rewrites: with more than
 // one workgroup per filter they have to be separate launches.  All arithmetic is
 // fp64 whatever T; no atomics, no data-dependent order.
+//
+// k_zupt_gain<T, true> is the cued form (include/msckf_standstill.h): the same
+// kernel with the vision cue's status in the decision and three more record words;
+// <T, false> is msckf_zupt_batch's: the same body and arithmetic as before the cue, with
+// one more kernel argument, placed last and never read, and three more pointers in ZuptDev.
+#include "../../include/msckf_standstill.h"
 #include "../../include/msckf_zupt.h"
 #include "msckf_common.h"
 #include "msckf_correct.h"
@@ -26,9 +32,9 @@ constexpr int ZG_NT = 256;                                   // k_zupt_gain's wo
 constexpr int ZG_DMAX = 21 + 6 * 128;                        // the largest window (msckf_create)
 constexpr int ZG_ROWS = (ZG_DMAX + ZG_NT - 1) / ZG_NT;       // rows of P H^T per thread
 
-template <typename T>
+template <typename T, bool CUED>
 __global__ void __launch_bounds__(ZG_NT) k_zupt_gain(DevState<T> st, ZuptDev z, ZuptArgs a, const int* filters,
-                                                      const double* means) {
+                                                      const double* means, ZuptCueArgs q) {
     const int w = blockIdx.x, b = filters[w], tid = threadIdx.x;
     const int D = 21 + 6 * st.ncams[b], ld = st.Dmax, m = a.m;
     const T* P = st.P + (size_t)b * ld * ld;
@@ -136,7 +142,29 @@ __global__ void __launch_bounds__(ZG_NT) k_zupt_gain(DevState<T> st, ZuptDev z, 
                 gamma += y[i] * y[i];
             }
         }
-        const int app = (pd && gamma < a.chi2 && s_speed <= a.max_speed) ? 1 : 0;
+        int app = (pd && gamma < a.chi2 && s_speed <= a.max_speed) ? 1 : 0;
+        if constexpr (CUED) {   // the cue's status and the decision rules of msckf_standstill.h
+            int cn = -1;
+            float cd = __builtin_nanf("");
+            if (q.rec) {
+                const int ln = q.lane[w];
+                if (ln >= 0) cn = q.rec[ln].n, cd = q.rec[ln].d2;
+            } else if (q.n[w] >= 0) {
+                cn = q.n[w], cd = q.d2[w];
+            }
+            const int status = (cn < 0 || cn < q.min_tracks) ? MSCKF_CUE_UNKNOWN
+                               : ((double)cd <= q.max_px2)   ? MSCKF_CUE_STILL
+                                                             : MSCKF_CUE_MOVING;
+            const bool imu_ok = app != 0, still = status == MSCKF_CUE_STILL, unk = status == MSCKF_CUE_UNKNOWN;
+            const bool fall = q.unknown == MSCKF_CUE_UNKNOWN_IMU;
+            if (q.mode == MSCKF_CUE_MODE_VETO)
+                app = (imu_ok && (still || (unk && fall))) ? 1 : 0;
+            else
+                app = ((pd && still) || (imu_ok && (!unk || fall))) ? 1 : 0;
+            z.cue[b] = status;
+            z.cue_n[b] = cn;
+            z.cue_d2[b] = cd;
+        }
         z.applied[b] = app;
         z.gamma[b] = gamma;
         if (app) z.count[b] += 1;
@@ -188,7 +216,14 @@ template <typename T>
 void launch_zupt_gain(hipStream_t s, const DevState<T>& st, const ZuptDev& z, const ZuptArgs& a, int nfilt,
                       const int* filters, const double* means) {
     if (nfilt <= 0) return;
-    hipLaunchKernelGGL(k_zupt_gain<T>, dim3(nfilt), dim3(ZG_NT), 0, s, st, z, a, filters, means);
+    hipLaunchKernelGGL((k_zupt_gain<T, false>), dim3(nfilt), dim3(ZG_NT), 0, s, st, z, a, filters, means,
+                       ZuptCueArgs{});
+}
+template <typename T>
+void launch_zupt_gain_cued(hipStream_t s, const DevState<T>& st, const ZuptDev& z, const ZuptArgs& a,
+                           const ZuptCueArgs& q, int nfilt, const int* filters, const double* means) {
+    if (nfilt <= 0) return;
+    hipLaunchKernelGGL((k_zupt_gain<T, true>), dim3(nfilt), dim3(ZG_NT), 0, s, st, z, a, filters, means, q);
 }
 template <typename T>
 void launch_zupt_apply(hipStream_t s, const DevState<T>& st, const ZuptDev& z, int m, int nfilt, const int* filters,
@@ -201,6 +236,8 @@ void launch_zupt_apply(hipStream_t s, const DevState<T>& st, const ZuptDev& z, i
 #define INSTANTIATE(T)                                                                                           \
     template void launch_zupt_gain<T>(hipStream_t, const DevState<T>&, const ZuptDev&, const ZuptArgs&, int,     \
                                       const int*, const double*);                                                \
+    template void launch_zupt_gain_cued<T>(hipStream_t, const DevState<T>&, const ZuptDev&, const ZuptArgs&,     \
+                                           const ZuptCueArgs&, int, const int*, const double*);                  \
     template void launch_zupt_apply<T>(hipStream_t, const DevState<T>&, const ZuptDev&, int, int, const int*, int);
 INSTANTIATE(float)
 INSTANTIATE(double)

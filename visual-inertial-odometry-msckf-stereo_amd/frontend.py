@@ -152,6 +152,11 @@ class FrontendConfig:
     equalize: str = "none"
     clahe_clip_limit: float = 40.0
     clahe_tiles: tuple = (8, 8)
+    # not in the reference: a device_tracks lane also leaves the frame's motion statistic on the
+    # device (include/msckf_standstill.h): the track_motion_quantile of the squared pixel
+    # displacement of the tracks that survived the frame's tracking; the messages are the same
+    track_motion: bool = False
+    track_motion_quantile: float = 0.5
 
     @property
     def grid_num(self):
@@ -602,6 +607,38 @@ class Frontend:
                                             C.byref(nxt)))
         k = n.value
         return ids[:k].copy(), life[:k].copy(), c0[:k].copy(), c1[:k].copy(), nxt.value
+
+    # ---- the motion statistic (include/msckf_standstill.h) ----
+    def motion_sets(self, sets, q=0.5):
+        """mfe_motion_sets: per set (prev, curr) of float32 (n, 2) pixel pairs
+        the q-quantile (k = floor(q (n - 1))) of the squared displacement.
+        Returns (n int32 [S], d2 float32 [S]); an empty set gives NaN."""
+        prev = [np.asarray(p, np.float32).reshape(-1, 2) for p, _ in sets]
+        curr = [np.asarray(c, np.float32).reshape(-1, 2) for _, c in sets]
+        if any(len(p) != len(c) for p, c in zip(prev, curr)):
+            raise ValueError("a set's prev and curr differ in length")
+        S = len(sets)
+        off = self._set_off([len(p) for p in prev])
+        P = np.ascontiguousarray(np.concatenate(prev) if S else np.zeros((0, 2)), np.float32)
+        Q = np.ascontiguousarray(np.concatenate(curr) if S else np.zeros((0, 2)), np.float32)
+        n, d2 = np.zeros(S, np.int32), np.zeros(S, np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.mfe_motion_sets(self.h, S, off.ctypes.data_as(_I32P), P.ctypes.data_as(fp),
+                                             Q.ctypes.data_as(fp), float(q), n.ctypes.data_as(_I32P),
+                                             d2.ctypes.data_as(fp)))
+        return n, d2
+
+    def tracks_motion_enable(self, on=True, q=0.5):
+        """mfe_tracks_motion_enable: the steps of this context leave each named
+        lane's motion record on the device (needs tracks_create)."""
+        self._check(self.lib.mfe_tracks_motion_enable(self.h, int(bool(on)), float(q)))
+
+    def tracks_motion_get(self, lane):
+        """mfe_tracks_motion_get (synchronises): (valid, n, d2 float32) of the
+        lane's record; (False, 0, NaN) without a valid one."""
+        valid, n, d2 = C.c_int32(0), C.c_int32(0), C.c_float(0.0)
+        self._check(self.lib.mfe_tracks_motion_get(self.h, int(lane), C.byref(valid), C.byref(n), C.byref(d2)))
+        return bool(valid.value), int(n.value), np.float32(d2.value)
 
     def tracks_msg_put(self, lane, ids, uv):
         """mfe_tracks_msg_put (msckf_handoff.h): the lane's message, ids int64
@@ -1214,7 +1251,14 @@ class MultiImageProcessor:
     ``mfe_tracks_step`` for all tracking lanes; a lane's first frame runs as
     above and enters its table through ``mfe_tracks_put``.  The lanes then
     also agree on grid_min / grid_max_feature_num and, among the RANSAC lanes,
-    on the threshold and success probability.  ``tracks(i)`` reads a table."""
+    on the threshold and success probability.  ``tracks(i)`` reads a table.
+
+    With ``track_motion`` (all lanes, needs ``device_tracks``) every tracked
+    frame also leaves the lane's motion record on the device
+    (include/msckf_standstill.h): the ``track_motion_quantile`` of the squared
+    pixel displacement of the tracks that survived the frame.
+    ``track_motion(i)`` reads it; an array message carries it as ``motion``,
+    a ``TrackMessage`` names the lane whose record the filter reads in place."""
 
     def __init__(self, n, config=None, lane_configs=None, device=0):
         if lane_configs is None:
@@ -1252,8 +1296,12 @@ class MultiImageProcessor:
                 raise ValueError("lane %d: device_tracks = %r differs from lane 0's %r"
                                  % (i, c.device_tracks, cfgs[0].device_tracks))
             if not self.device_tracks:
+                if c.track_motion:
+                    raise ValueError("lane %d: track_motion needs device_tracks" % i)
                 continue
-            shared = [("grid_min_feature_num", 0), ("grid_max_feature_num", 0)]
+            # the motion statistic is a switch of the context (msckf_standstill.h)
+            shared = [("grid_min_feature_num", 0), ("grid_max_feature_num", 0), ("track_motion", 0),
+                      ("track_motion_quantile", 0)]
             if c.ransac_enabled:   # the RANSAC lanes among themselves
                 shared += [("ransac_threshold", ransac[0]), ("ransac_success_probability", ransac[0])]
             for f, j in shared:
@@ -1272,6 +1320,13 @@ class MultiImageProcessor:
                                   c.grid_col, c.grid_min_feature_num, c.grid_max_feature_num)
             self._tracks_ransac = ((cfgs[ransac[0]].ransac_threshold, self.lanes[ransac[0]].ransac_n_hyp)
                                    if ransac else (0.0, 0))
+        self.track_motion_on = bool(self.device_tracks and cfgs[0].track_motion)
+        if self.track_motion_on:
+            try:
+                self.fe.tracks_motion_enable(True, cfgs[0].track_motion_quantile)
+            except BaseException:
+                self.fe.close()
+                raise
 
     def __len__(self):
         return len(self.lanes)
@@ -1324,6 +1379,14 @@ class MultiImageProcessor:
         cam0, cam1, next_id), rows in publish order."""
         return self.fe.tracks_get(i)
 
+    def track_motion(self, i):
+        """Lane i's motion record (``FrontendConfig.track_motion``): (valid, n,
+        d2) -- d2 the configured quantile of the squared pixel displacement of
+        the n tracks that survived the last frame's tracking; synchronises."""
+        if not self.track_motion_on:
+            raise ValueError("track_motion needs FrontendConfig(device_tracks=True, track_motion=True)")
+        return self.fe.tracks_motion_get(i)
+
     def _tracks_callbacks(self, msgs, arrays=False, handoff=False):
         """stereo_callbacks with the tracks on the device: one upload for all
         lanes, the first-frame lanes on their generators (then tracks_put, and
@@ -1350,8 +1413,13 @@ class MultiImageProcessor:
                 if handoff:
                     out[i] = TrackMessage(ip.cam0_curr_img_msg.vio_timestamp__, self.fe, i, r.n)
                 elif arrays:
+                    motion = None
+                    if self.track_motion_on:   # the record the step just wrote, for the host's cue
+                        self.launches["tracks_motion_get"] += 1
+                        _, mn, md2 = self.fe.tracks_motion_get(i)
+                        motion = (mn, md2)
                     out[i] = FeatureArrays(ip.cam0_curr_img_msg.vio_timestamp__, np.asarray(r.ids, np.int64),
-                                           np.asarray(r.uv, np.float64).reshape(-1, 4))
+                                           np.asarray(r.uv, np.float64).reshape(-1, 4), motion)
                 else:
                     out[i] = FeatureMsg(ip.cam0_curr_img_msg.vio_timestamp__,
                                         [FeatureMeasurement(k, *u) for k, u in zip(r.ids.tolist(), r.uv.tolist())])

@@ -61,10 +61,24 @@ VioOdometry = namedtuple("vio_odometry", ["timestamp", "pose", "velocity", "cam0
                                           "velocity_covariance"])
 # A feature message as arrays: ids int64 [n], uv float64 [n][4] (u0 v0 u1 v1).
 # Accepted wherever the reference's feature_msg tuple is.
-FeatureArrays = namedtuple("FeatureArrays", ["timestamp", "ids", "uv"])
+# ``motion``: None, or the front-end's motion record (n, d2) of the frame (include/msckf_standstill.h)
+FeatureArrays = namedtuple("FeatureArrays", ["timestamp", "ids", "uv", "motion"], defaults=(None,))
 # A feature message that stayed on the device (include/msckf_handoff.h): the n-row message of lane
 # ``lane`` of the front-end context ``frontend`` (a frontend.Frontend).  Accepted with device_map=True only.
 TrackMessage = namedtuple("TrackMessage", ["timestamp", "frontend", "lane", "n"])
+
+
+def _cue_source(feature_msg):
+    """Where the frame's vision cue comes from (msckf_standstill.h): (front-end
+    context, lane, None) for a message on the device -- its lane's motion record
+    is read there, and a lane's first frame has none -- or (None, n, d2) for the
+    host: an array message's ``motion``, else (-1, NaN), "no record"."""
+    if isinstance(feature_msg, TrackMessage):
+        return (feature_msg.frontend, int(feature_msg.lane), None)
+    motion = getattr(feature_msg, "motion", None)
+    if motion is None:
+        return (None, -1, float("nan"))
+    return (None, int(motion[0]), np.float32(motion[1]))
 
 
 def message_arrays(feature_msg):
@@ -171,7 +185,11 @@ class MSCKF:
             raise TypeError("zupt must be a ZuptConfig or None, not %r" % (zupt,))
         self.zupt = zupt
         self._zupt_prm = zupt.params() if zupt is not None else None   # checks the row names and chi2's table
-        self.zupt_log = []                 # (frame, applied, gamma), one per zero-velocity update enqueued
+        # the vision cue (msckf_standstill.h): the frame's message names or carries the front-end's motion record
+        self._cue_prm = zupt.vision.params() if zupt is not None and zupt.vision is not None else None
+        # (frame, applied, gamma), one per zero-velocity update enqueued; with zupt.vision
+        # (frame, applied, gamma, cue, n, d2) -- the cue's status and record as the device saw them
+        self.zupt_log = []
         self._zupt_count = 0
         if aiding is not None and not isinstance(aiding, AidingConfig):
             raise TypeError("aiding must be an AidingConfig or None, not %r" % (aiding,))
@@ -286,8 +304,16 @@ class MSCKF:
             return ctx.propagate(f, req[1], req[2], req[3])
         if kind == "augment":
             return ctx.augment(f)
+        if kind == "zupt" and len(req) > 3:   # (kind, means, the frame's cue source): msckf_standstill.h
+            fe, a, b = req[3]
+            if fe is not None:
+                return ctx.zupt_batch_cued([f], req[1], req[2], self._zupt_prm, self._cue_prm, fe=fe, lanes=[a])
+            return ctx.zupt_batch_cued([f], req[1], req[2], self._zupt_prm, self._cue_prm, cue_n=[a], cue_d2=[b])
         if kind == "zupt":   # (kind, mean angular rate, mean specific force)
             return ctx.zupt_batch([f], req[1], req[2], self._zupt_prm)
+        if kind == "zupt_results" and self._cue_prm is not None:   # the six records in one read
+            app, gam, cnt, cue, cn, cd = ctx.zupt_cue_results([f])
+            return bool(app[0]), float(gam[0]), int(cnt[0]), int(cue[0]), int(cn[0]), float(cd[0])
         if kind == "zupt_results":
             app, gam, cnt = ctx.zupt_results([f])
             return bool(app[0]), float(gam[0]), int(cnt[0])
@@ -510,7 +536,11 @@ class MSCKF:
         ws, accs = yield from self._batch_imu_processing(feature_msg.timestamp)
         zupt = self.zupt is not None and len(ws) > 0
         if zupt:   # the standstill update with the means of exactly the samples propagated (msckf_zupt.h)
-            yield ("zupt", np.mean(np.array(ws).reshape(-1, 3), axis=0), np.mean(np.array(accs).reshape(-1, 3), axis=0))
+            means = (np.mean(np.array(ws).reshape(-1, 3), axis=0), np.mean(np.array(accs).reshape(-1, 3), axis=0))
+            if self._cue_prm is not None:
+                yield ("zupt",) + means + (_cue_source(feature_msg),)
+            else:
+                yield ("zupt",) + means
         late = []
         if self.aiding is not None and self.aiding.delayed:   # late fixes on their clones first, oldest first
             late, fix = self._take_fixes(feature_msg.timestamp)
@@ -541,8 +571,9 @@ class MSCKF:
             st = yield (("states", 12, 3) if thr > 0 else ("states",))
         self._settle()
         if zupt:   # the device has drained: the update's record
-            app, gam, self._zupt_count = yield ("zupt_results",)
-            self.zupt_log.append((self._n_published, app, gam))
+            rec = yield ("zupt_results",)
+            self._zupt_count = rec[2]
+            self.zupt_log.append((self._n_published, rec[0], rec[1]) + tuple(rec[3:]))
         if late:   # the last late fix's record (the earlier ones were read behind their calls)
             self._log_delayed(late[-1][1], late[-1][2], (yield ("aid_delayed_results",)))
         if fix is not None:

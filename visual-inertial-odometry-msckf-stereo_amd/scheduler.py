@@ -11,7 +11,11 @@ with ONE batched launch:
   propagate   -> msckf_propagate_batch   (IMU propagation fused across filters)
   zupt        -> msckf_zupt_batch        (zupt=ZuptConfig: the standstill update,
                  gated on the device; zupt_results -> msckf_zupt_results, behind
-                 the frame's states read)
+                 the frame's states read; with ZuptConfig(vision=VisionCue) the
+                 request carries the frame's cue source and the call is
+                 msckf_zupt_batch_cued, one per source -- a front-end context's
+                 motion records read on the device, or host arrays -- and the
+                 read is msckf_zupt_cue_results, msckf_standstill.h)
   aid         -> msckf_aid_batch         (aiding=AidingConfig: the lanes that have
                  a fix at this frame, each with its own; aid_results ->
                  msckf_aid_results, behind the frame's states read)
@@ -176,6 +180,8 @@ class MultiMSCKF:
                 group = [i for i in group if _read_key(pending[i]) == key]
             elif kind == "map_add_lost_tracks":   # one front-end context per call
                 group = [i for i in group if pending[i][1] is pending[group[0]][1]]
+            elif kind == "zupt" and len(pending[group[0]]) > 3:   # one cue source per call: a front-end context or the host
+                group = [i for i in group if pending[i][3][0] is pending[group[0]][3][0]]
             results = self._serve(kind, group, [pending[i] for i in group])
             for i, res in zip(group, results):
                 del pending[i]
@@ -202,10 +208,24 @@ class MultiMSCKF:
         if kind == "augment":
             ctx.augment_batch(slots)
             return [None] * len(group)
+        if kind == "zupt" and len(reqs[0]) > 3:   # with the vision cue (msckf_standstill.h): one msckf_zupt_batch_cued
+            ln0 = self.lanes[group[0]]
+            w, a = np.array([r[1] for r in reqs]), np.array([r[2] for r in reqs])
+            fe = reqs[0][3][0]
+            if fe is not None:   # the lanes' motion records read where the front-end left them
+                ctx.zupt_batch_cued(slots, w, a, ln0._zupt_prm, ln0._cue_prm, fe=fe, lanes=[r[3][1] for r in reqs])
+            else:
+                ctx.zupt_batch_cued(slots, w, a, ln0._zupt_prm, ln0._cue_prm, cue_n=[r[3][1] for r in reqs],
+                                    cue_d2=[r[3][2] for r in reqs])
+            return [None] * len(group)
         if kind == "zupt":   # the lanes share the parameters (one ZuptConfig)
             ctx.zupt_batch(slots, np.array([r[1] for r in reqs]), np.array([r[2] for r in reqs]),
                            self.lanes[group[0]]._zupt_prm)
             return [None] * len(group)
+        if kind == "zupt_results" and self.lanes[group[0]]._cue_prm is not None:   # the six records in one read
+            app, gam, cnt, cue, cn, cd = ctx.zupt_cue_results(slots)
+            return [(bool(app[w]), float(gam[w]), int(cnt[w]), int(cue[w]), int(cn[w]), float(cd[w]))
+                    for w in range(len(group))]
         if kind == "zupt_results":
             app, gam, cnt = ctx.zupt_results(slots)
             return [(bool(app[w]), float(gam[w]), int(cnt[w])) for w in range(len(group))]

@@ -21,6 +21,14 @@ Both give every lane the poses the two classes wired by hand give it, bit for
 bit.  ``StereoVIO`` is the one-lane form with the reference's call shape
 (``imu_callback(msg)``, ``stereo_callback(msg)``).
 
+With ``zupt=ZuptConfig(vision=VisionCue(...))`` the front-end also leaves each
+lane's track motion on the device and the filters' zero-velocity update reads
+it there (include/msckf_standstill.h; under handoff="host" the two numbers
+travel with the array message).  The update is asynchronous and reads the
+record in place: the frame's ``feature_callbacks`` ends in synchronising calls
+(add_lost, the states read), so it has drained before the next frame's step
+rewrites the record.
+
 What still synchronises per frame: the front-end's step returns synchronised
 (the host needs each lane's n and next_id, and the message must be complete
 before another context's stream reads it), and so does the filters' add_lost
@@ -36,8 +44,9 @@ from .trajectory import Trajectory
 HANDOFFS = ("device", "host")
 
 
-def _frontend_configs(n, config, lane_configs):
-    """The lanes' front-end configs with device_pipeline and device_tracks forced on."""
+def _frontend_configs(n, config, lane_configs, vision=None):
+    """The lanes' front-end configs with device_pipeline and device_tracks forced on --
+    and, with a ``VisionCue``, the motion statistic at its quantile."""
     if lane_configs is None:
         if config is None:
             config = FrontendConfig()
@@ -45,7 +54,10 @@ def _frontend_configs(n, config, lane_configs):
             config = FrontendConfig.from_reference(config)
         lane_configs = [config] * n
     cfgs = [c if isinstance(c, FrontendConfig) else FrontendConfig.from_reference(c) for c in lane_configs]
-    return [FrontendConfig(**{**vars(c), "device_pipeline": True, "device_tracks": True}) for c in cfgs]
+    extra = {"device_pipeline": True, "device_tracks": True}
+    if vision is not None:   # the cue of the zero-velocity update (msckf_standstill.h), for both handoffs
+        extra.update(track_motion=True, track_motion_quantile=float(vision.quantile))
+    return [FrontendConfig(**{**vars(c), **extra}) for c in cfgs]
 
 
 class MultiStereoVIO:
@@ -57,7 +69,10 @@ class MultiStereoVIO:
                  aiding=None, anchors=None):
         """``landmarks`` / ``landmark_capacity`` / ``odometry``: as
         ``MultiMSCKF``'s (msckf_odometry.h); ``zupt``: as ``MultiMSCKF``'s
-        (msckf_zupt.h; ``zupt_log(i)`` reads lane i's decisions); ``aiding``:
+        (msckf_zupt.h; ``zupt_log(i)`` reads lane i's decisions; with
+        ``ZuptConfig(vision=VisionCue(...))`` the front-end's lanes leave their
+        track motion on the device and the update is gated on it too,
+        msckf_standstill.h, under either handoff); ``aiding``:
         as ``MultiMSCKF``'s (msckf_aid.h; ``aiding_callback(i, fix)``,
         ``aid_log(i)``); ``anchors``: as ``MultiMSCKF``'s (msckf_anchor.h;
         ``anchor_callback(i, fix)``, ``anchor_log(i)``).
@@ -70,8 +85,10 @@ class MultiStereoVIO:
         if handoff not in HANDOFFS:
             raise ValueError("handoff = %r, expected one of %r" % (handoff, HANDOFFS))
         self.handoff = handoff
+        vision = getattr(zupt, "vision", None)
         self.frontend = MultiImageProcessor(n, lane_configs=_frontend_configs(n, frontend_config,
-                                                                              lane_frontend_configs), device=device)
+                                                                              lane_frontend_configs, vision),
+                                            device=device)
         try:
             self.filters = MultiMSCKF(n, config=filter_config, dtype=dtype, device=device,
                                       lane_configs=lane_filter_configs, device_map=True, map_capacity=map_capacity,
@@ -115,7 +132,8 @@ class MultiStereoVIO:
         self.filters.clear_landmarks(i)
 
     def zupt_log(self, i):
-        """Lane i's zero-velocity decisions, (frame, applied, gamma) per update enqueued."""
+        """Lane i's zero-velocity decisions, (frame, applied, gamma) per update
+        enqueued -- with a vision cue (frame, applied, gamma, cue, n, d2)."""
         return self.filters.lanes[i].zupt_log
 
     def aid_log(self, i):
